@@ -1,10 +1,17 @@
 """bench.py -- frames/sec of one training step (fwd + bwd + update) of the
 BASELINE stack Conv(40x11x3, 8x1, 128) -> Maxpool(1x1x4) -> FC(11616 -> 1024)
-on MI355X through libkcnn.so, plus the dominant hot-path kernel's roofline
-fraction (HIP events over the timed region) and the CPU oracle timed on the
-host beside it.
+on MI355X through libkcnn.so.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-gpu B]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed steps, times K steps and prints one JSON
+line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR then writes
+what the last timed step computed (DIR/<name>.npy, see dump_outputs).  --full
+adds everything that takes runs of its own: the same K steps again with HIP
+events around every component scope (per-kernel times, the dominant hot-path
+kernel's roofline fraction), the data-parallel exchange measured alone
+(N > 1) and the CPU oracle timed on the host (unless --no-cpu-baseline).
 
 N > 1 runs under torch.distributed.run, one process per GPU (started by
 bench.py itself as a child `python -m torch.distributed.run` when no launcher
@@ -618,6 +625,56 @@ def dp_report(dist, grads, marks, steps, reps=5):
                     "back to back with nothing else running"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all of --dump-outputs' files together stay below this
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(net, out_dir):
+    """What a caller of the step holds after it, as out_dir/<name>.npy
+    (float32): the last layer's output of the step's Propagate, the input
+    derivative of its Backprop and the parameters of every updatable
+    component as that Backprop left them.  The arrays share
+    DUMP_BUDGET_BYTES equally: one above its share is written as a 1-D
+    sample of that many elements at fixed (seeded, sorted) flat indices, the
+    others whole.  Returns {name: [elements written, elements of the array]}."""
+    import numpy as np
+    import torch
+    arrays = [("output", net.Output()), ("input_deriv", net.InputDeriv(0))]
+    for i, c in enumerate(net.components):
+        if c.NumGradientParams() > 0:
+            arrays += [(f"component{i}_linear_params", c.LinearParams()),
+                       (f"component{i}_bias_params", c.BiasParams())]
+    arrays = [(name, t) for name, t in arrays if t.numel() > 0]
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        total = t.numel()
+        if total > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+                total, share, replace=False))
+            t = t.contiguous().view(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.detach().cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = [int(a.size), int(total)]
+    return written
+
+
+def describe(config):
+    """(metric, workload) of a --config, as the result line names them."""
+    if config == "nnet":
+        return ("frames/sec fwd+bwd, reference egs/exp/nnet/nnet.config model",
+                "nnet.config: Splice(40,+-10) 6x(Conv+ReLU) Maxpool(1x2x1) "
+                "FC 1024-4096-4096-3454 (+ReLU); no Dropout/Softmax")
+    if config == "c5":
+        return ("frames/sec fwd+bwd, c5 deep Conv/Maxpool stack (BASELINE configs[4])",
+                "c5: C1(40x11x3,8x1,256) P1(3x1x4) C2(11x11x64,4x3,256) "
+                "C3(8x9x256,3x3,pad1,256) P2(2x1x4) C4(4x9x64,4x3,256) FC(1792->1024)")
+    return ("frames/sec fwd+bwd, Conv+Maxpool+FC stack, 4096-frame batch @1/2/4/8 GPU",
+            "c2: Conv(40x11x3, 8x1, 128) -> Maxpool(1x1x4) -> "
+            "FC(11616->1024), fwd+bwd+update")
+
+
 def launch_ranks(n):
     """Run this script under `python -m torch.distributed.run` with n ranks
     on this node (rendezvous on 127.0.0.1, a free port) as a child process;
@@ -648,7 +705,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--frames-per-gpu", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled pass (per-kernel "
+                         "times, roofline), the data-parallel exchange alone (N > 1) and "
+                         "the CPU baseline; a plain run reports the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as "
+                         "DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--graph", action="store_true",
                     help="one GPU: capture the step once as a HIP graph and replay it "
                          "(measured slower than host-issued steps at c2: 2.75-2.80 M vs "
@@ -664,6 +729,8 @@ def main():
                     help="c2 (default, BASELINE's metric), the c5 deep stack, or the "
                          "reference's egs/exp/nnet/nnet.config model")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks
@@ -812,10 +879,43 @@ def main():
             el = float(t.item())
         return el, pr
 
-    # headline: profiling off (no events in the stream); then the same K steps
-    # again with hipEvents around every component scope, for the per-kernel
-    # times of the roofline
+    # headline: profiling off (no events in the stream)
     elapsed, _ = timed(False)
+    dumped = dump_outputs(net, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    metric, workload = describe(args.config)
+
+    if not args.full:
+        if rank == 0:
+            config = {"workload": workload, "frames_per_gpu": B, "parallelism": f"dp{world}"}
+            if args.config == "c2":
+                config.update({"baseline_config": baseline_config(B, world),
+                               "global_batch": B * world,
+                               "conv_maxpool_fusion": not args.no_fusion,
+                               "conv_output_stored": args.no_fusion or args.store_conv_out})
+            result = {
+                "metric": metric,
+                "value": round(B * world * args.steps / elapsed, 1), "unit": "frames/sec",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                "data": "synthetic N(0,1) frames, a ring of 4 N(0,1)*1e-2 output derivatives "
+                        "and their negations, one per step",
+                "hip_graph": graph is not None, "config": config,
+            }
+            if dumped is not None:
+                result["dumped_outputs"] = dumped
+            line = json.dumps(result)
+            print(line, flush=True)
+            if args.json_out:
+                with open(args.json_out, "w") as f:
+                    f.write(line + "\n")
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full: the same K steps again with hipEvents around every component
+    # scope, for the per-kernel times of the roofline
     profiling_dp = True
     kcnn.conv_fix_counts(reset=True)
     elapsed_prof, prof = timed(True)
@@ -845,14 +945,6 @@ def main():
         mix = {}
         for _, f, e in passes:
             mix[e] = mix.get(e, 0) + f
-        if args.config == "nnet":
-            metric = "frames/sec fwd+bwd, reference egs/exp/nnet/nnet.config model"
-            workload = ("nnet.config: Splice(40,+-10) 6x(Conv+ReLU) Maxpool(1x2x1) "
-                        "FC 1024-4096-4096-3454 (+ReLU); no Dropout/Softmax")
-        else:
-            metric = "frames/sec fwd+bwd, c5 deep Conv/Maxpool stack (BASELINE configs[4])"
-            workload = ("c5: C1(40x11x3,8x1,256) P1(3x1x4) C2(11x11x64,4x3,256) "
-                        "C3(8x9x256,3x3,pad1,256) P2(2x1x4) C4(4x9x64,4x3,256) FC(1792->1024)")
         if rank == 0:
             result = {
                 "metric": metric,
@@ -900,6 +992,8 @@ def main():
                             "passes"}
             if dp:
                 result["dp"] = dp
+            if dumped is not None:
+                result["dumped_outputs"] = dumped
             if not args.no_cpu_baseline and world == 1:
                 text = NNET_CONFIG if args.config == "nnet" else c5_config()[0]
                 result["cpu_baseline"] = cpu_baseline_stack(
@@ -1029,7 +1123,7 @@ def main():
 
     if rank == 0:
         result = {
-            "metric": "frames/sec fwd+bwd, Conv+Maxpool+FC stack, 4096-frame batch @1/2/4/8 GPU",
+            "metric": metric,
             "value": round(value, 1), "unit": "frames/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
@@ -1040,8 +1134,7 @@ def main():
             # (kernel times below come from it)
             "profiled_ms_per_step": round(elapsed_prof / args.steps * 1e3, 4),
             "hip_graph": graph is not None,
-            "config": {"workload": "c2: Conv(40x11x3, 8x1, 128) -> Maxpool(1x1x4) -> "
-                                   "FC(11616->1024), fwd+bwd+update",
+            "config": {"workload": workload,
                        "baseline_config": baseline_config(B, world),
                        "frames_per_gpu": B, "global_batch": B * world,
                        "parallelism": f"dp{world}",
@@ -1052,6 +1145,8 @@ def main():
         }
         if dp:
             result["dp"] = dp
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(B)
         line = json.dumps(result)

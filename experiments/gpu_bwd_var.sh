@@ -12,7 +12,7 @@ for lib in ${LIBS:-libkcnn.so}; do
 done
 for rep in 1 2 3; do
 for lib in ${LIBS:-libkcnn.so}; do
-  KCNN_LIB=$PWD/kaldi-cnn_amd/$lib timeout -k 10 200 python bench.py --no-cpu-baseline --steps 40 --warmup 10 --json-out $O/b.json > $O/b.log 2>&1 || exit 5
+  KCNN_LIB=$PWD/kaldi-cnn_amd/$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 40 --warmup 10 --json-out $O/b.json > $O/b.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/b.json'));k=d['kernels']
 print('$lib', d['value'], d['ms_per_step'], 'bwd', k['conv_bwd_pooled']['ms'], 'fwd', k['conv_fwd_maxpool']['ms'])"

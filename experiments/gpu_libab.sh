@@ -12,7 +12,7 @@ done
 for rep in 1 2; do
 for lib in ${LIBS:-libkcnn.so}; do
   for c in ${CFGS:-c2 c5 nnet}; do
-    KCNN_LIB=$PWD/kaldi-cnn_amd/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --config $c --json-out $O/b.json > $O/b.log 2>&1 || exit 5
+    KCNN_LIB=$PWD/kaldi-cnn_amd/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --config $c --json-out $O/b.json > $O/b.log 2>&1 || exit 5
     python -c "
 import json;d=json.load(open('$O/b.json'));s=d.get('scopes_ms_per_step') or {};k=d.get('kernels') or {}
 print('$c $lib', d['value'], d['ms_per_step'], {n:v.get('ms', v.get('ms_per_step')) for n,v in k.items()} if k else {a.split('::')[1]:b for a,b in s.items() if a.startswith('Conv')})"

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 9
 O=gpurun_out/${TAG:-r05ab}; mkdir -p $O; export TMPDIR=/tmp
 for i in 1 2 3; do for lib in prev new; do
   L=$PWD/kaldi-cnn_amd/libkcnn.so; [ $lib = prev ] && L=$PWD/kaldi-cnn_amd/libkcnn_prev.so
-  KCNN_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
+  KCNN_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/ab_${lib}_$i.json'));print('$lib', d['value'], d['ms_per_step'])"
 done; done

@@ -10,12 +10,12 @@ rc=$?; echo "pytest rc $rc"; grep -E "FAILED|ERROR|differs" $O/pytest.txt | head
 fi
 for i in 1 2; do for lib in r04 new; do
   L=$PWD/kaldi-cnn_amd/libkcnn.so; [ $lib = r04 ] && L=$PWD/kaldi-cnn_amd/libkcnn_r04.so
-  KCNN_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
+  KCNN_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/ab_${lib}_$i.json'));print('$lib', d['value'], d['ms_per_step'])"
 done; done
 if [ -n "$NNET" ]; then
-  timeout -k 10 300 python bench.py --config nnet --no-cpu-baseline --json-out $O/nnet.json > $O/nnet.log 2>&1 || exit 5
+  timeout -k 10 300 python bench.py --full --config nnet --no-cpu-baseline --json-out $O/nnet.json > $O/nnet.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/nnet.json'));print('nnet', d['value'], d['ms_per_step'])"
 fi

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" || exit 9
 O=gpurun_out/${TAG:-r06ab}; mkdir -p $O; export TMPDIR=/tmp
 for i in $(seq 1 ${ROUNDS:-2}); do for lib in ${LIBS:-new}; do
   L=$PWD/kaldi-cnn_amd/libkcnn_$lib.so; [ $lib = new ] && L=$PWD/kaldi-cnn_amd/libkcnn.so
-  KCNN_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline $BARGS --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
+  KCNN_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline $BARGS --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/ab_${lib}_$i.json'));k=d.get('kernels',{});print('$lib', d['value'], d['ms_per_step'], d['profiled_ms_per_step'], k.get('fc_gemms',{}).get('ms_per_step'))"
 done; done

@@ -10,7 +10,7 @@ rc=$?; echo "pytest rc $rc"; grep -E "FAILED|ERROR|Error|passed|failed" $O/pytes
 fi
 for i in 1 2; do for lib in r05 new; do
   L=$PWD/kaldi-cnn_amd/libkcnn.so; [ $lib = r05 ] && L=$PWD/kaldi-cnn_amd/libkcnn_r05.so
-  KCNN_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline $BARGS --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
+  KCNN_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline $BARGS --json-out $O/ab_${lib}_$i.json > $O/ab_${lib}_$i.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/ab_${lib}_$i.json'));print('$lib', d['value'], d['ms_per_step'], d['profiled_ms_per_step'])"
 done; done

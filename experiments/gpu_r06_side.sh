@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest -x -q -p no:cacheprovider --timeout 120 --
 tail -1 $O/pytest.log
 fi
 for i in $(seq 1 ${ROUNDS:-2}); do for s in 0 1; do
-  KCNN_SIDE_STREAM=$s timeout -k 10 300 python bench.py --no-cpu-baseline $BARGS --json-out $O/ab_${s}_$i.json > $O/ab_${s}_$i.log 2>&1 || exit 5
+  KCNN_SIDE_STREAM=$s timeout -k 10 300 python bench.py --full --no-cpu-baseline $BARGS --json-out $O/ab_${s}_$i.json > $O/ab_${s}_$i.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/ab_${s}_$i.json'));k=d.get('kernels',{});r=d.get('roofline',{})
 print('side=$s', d['value'], d['ms_per_step'], d.get('profiled_ms_per_step'), r.get('achieved'), r.get('frac'))"

@@ -5,7 +5,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 9
 O=gpurun_out/${TAG:-r06skip}; mkdir -p $O; export TMPDIR=/tmp
 for d in ${DBGS:-0 64 128 512 1024 32 256 0}; do
-  KCNN_LIB=$PWD/kaldi-cnn_amd/libkcnn_timing.so KCNN_BWD_DEBUG=$d timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 5 --json-out $O/skip_$d.json > $O/skip_$d.log 2>&1 || exit 5
+  KCNN_LIB=$PWD/kaldi-cnn_amd/libkcnn_timing.so KCNN_BWD_DEBUG=$d timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --json-out $O/skip_$d.json > $O/skip_$d.log 2>&1 || exit 5
   python -c "
 import json;d=json.load(open('$O/skip_$d.json'));k=d['kernels'];print('dbg $d', 'bwd %.1f us' % (1e3*k['conv_bwd_pooled']['ms']), 'step', d['ms_per_step'])"
 done

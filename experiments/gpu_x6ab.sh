@@ -9,7 +9,7 @@ tail -1 $O/pytest.log
 [ $rc -ne 0 ] && { grep -E "Error|assert|FAILED" $O/pytest.log | head -30; exit 3; }
 for v in ${VALS:-1 0 1 0}; do
   for c in ${CFGS:-c5 nnet}; do
-    env $VAR=$v timeout -k 10 300 python bench.py --no-cpu-baseline --config $c --json-out $O/b.json > $O/b.log 2>&1 || exit 5
+    env $VAR=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --config $c --json-out $O/b.json > $O/b.log 2>&1 || exit 5
     python -c "
 import json;d=json.load(open('$O/b.json'));s=d.get('scopes_ms_per_step') or {}
 k=d.get('kernels') or {}

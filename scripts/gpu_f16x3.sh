@@ -16,7 +16,7 @@ fi
 GEMM_MODES=2,1 timeout -k 10 120 python scripts/gemm_bench.py > $O/gemm_bench.log 2>&1 || exit 4
 cat $O/gemm_bench.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2/prof -o run -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/c2.prof.log 2>&1 || exit 7
-timeout -k 10 300 python bench.py --no-cpu-baseline --json-out $O/bench.json > $O/bench.log 2>&1 || exit 6
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --json-out $O/bench.json > $O/bench.log 2>&1 || exit 6
 python -c "import json;[print(f, json.load(open('$O/'+f))['value']) for f in ('bench.json',)]"
 echo done
 if [ -n "$CLOCK" ]; then

@@ -14,7 +14,7 @@ tail -1 $O/pytest.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2/prof -o run -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/c2.prof.log 2>&1 || exit 7
 python scripts/kstats.py $(ls $O/c2/prof/*/run_kernel_stats.csv 2>/dev/null || ls $O/c2/prof/run_kernel_stats.csv) 25 16
 for v in 2 1 2 1; do
-  KCNN_FWD_X6=$v timeout -k 10 300 python bench.py --no-cpu-baseline --json-out $O/bench_$v.json > $O/bench_$v.log 2>&1 || exit 6
+  KCNN_FWD_X6=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --json-out $O/bench_$v.json > $O/bench_$v.log 2>&1 || exit 6
   python -c "import json;d=json.load(open('$O/bench_$v.json'));print('fwd_x6=$v', d['value'], d['ms_per_step'])"
 done
 if [ -n "$AB" ]; then DBGS="0 256 512" PHASE=16 bash scripts/gpu_fwd_ab.sh $O/ab || exit 8; fi

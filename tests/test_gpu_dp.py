@@ -64,7 +64,7 @@ def test_bench_gpus_n_launches_n_ranks():
     env["OMP_NUM_THREADS"] = "2"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--frames-per-gpu", "256", "--no-cpu-baseline"],
+                        "--frames-per-gpu", "256", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
