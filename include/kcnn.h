@@ -252,6 +252,24 @@ int kcnn_component_backprop_gradient(const kcnn_component *c,
 /* ConvolutionComponent only: 1 if Backprop's reference branch is
  * "flip kernel" (nnet-component-nnet0.cc:489-497). */
 int kcnn_component_conv_flip_branch(const kcnn_component *c);
+/* DropoutComponent only.  SetDropoutScale (reference nnet-component.h:1611):
+ * a scale of 1.0 makes Propagate the identity (inference).  The mask of
+ * Propagate call k is a pure function of (seed, k, row, column): the seed is
+ * drawn from the host generator (kcnn_set_randn_seed) by Init, Copy and Read;
+ * setting it also restarts the call count. */
+int kcnn_component_set_dropout_scale(kcnn_component *c, float scale);
+int kcnn_component_dropout_seed(const kcnn_component *c, uint64_t *seed);
+int kcnn_component_set_dropout_seed(kcnn_component *c, uint64_t seed);
+
+/* CuMatrix::CompObjfAndDeriv (reference cudamatrix/cu-matrix.h:624-637) for
+ * num HOST elements {rows[i], cols[i], weights[i]} with no repeated (row,
+ * col), all inside the matrix (checked; an error runs no kernel): on the
+ * DEVICE matrices, deriv(row, col) += weight / probs(row, col); *tot_objf =
+ * sum weight * log probs(row, col) and *tot_weight = sum weight (host fp64,
+ * reduced in a fixed order).  Synchronises. */
+int kcnn_comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const float *weights,
+                             int num, const float *probs, MatrixDim p_dim, float *deriv,
+                             MatrixDim d_dim, double *tot_objf, double *tot_weight);
 
 /* ---- component stack (NnetUpdater-style) -------------------------------- */
 typedef struct kcnn_nnet kcnn_nnet;
@@ -290,6 +308,23 @@ int kcnn_nnet_backprop_split(kcnn_nnet *n, int i, const float *out_deriv, Matrix
                              float *grad, int skip_first_dx, void (*between)(void *),
                              void *ctx);
 int kcnn_nnet_backprop(kcnn_nnet *n, const float *out_deriv, MatrixDim od_dim);
+/* A training step's backward from labels (upstream NnetUpdater::
+ * ComputeObjfAndDeriv + Backprop): num HOST elements {row, col, weight} of
+ * the last Propagate's output, rows non-decreasing, every (row, col) inside
+ * the output and none repeated -- checked on the host before anything is
+ * launched; a violation is an error that runs no kernel.  The objective
+ * sum weight * log output(row, col) and the weight are added to device fp64
+ * totals (kcnn_nnet_objf_total); the call does not synchronise.  The output
+ * derivative weight / output(row, col) is backpropagated through every
+ * component in mode 0.  When the last component is a SoftmaxComponent the
+ * derivative, the objective and its Backprop run as one kernel, unless
+ * kcnn_set_literal_path(1) asks for the literal sequence. */
+int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
+                            const float *weights, int num, int skip_first_dx);
+/* out[0] = the objective, out[1] = the weight accumulated by
+ * kcnn_nnet_backprop_xent since the last reset (their ratio is the average
+ * log-probability per frame); reset != 0 zeroes them.  Synchronises. */
+int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset);
 
 #ifdef __cplusplus
 }

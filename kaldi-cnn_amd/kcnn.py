@@ -577,6 +577,53 @@ class Component:
             check(rc)
         return bool(rc)
 
+    # DropoutComponent
+    def SetDropoutScale(self, scale: float):
+        """DropoutComponent::SetDropoutScale; 1.0 is inference (identity)."""
+        check(lib().kcnn_component_set_dropout_scale(self._h, ctypes.c_float(scale)))
+
+    def DropoutSeed(self) -> int:
+        seed = ctypes.c_uint64()
+        check(lib().kcnn_component_dropout_seed(self._h, ctypes.byref(seed)))
+        return seed.value
+
+    def SetDropoutSeed(self, seed: int):
+        """Sets the mask generator's seed and restarts its call count: the
+        mask of Propagate call k is a function of (seed, k, row, column)."""
+        check(lib().kcnn_component_set_dropout_seed(self._h, ctypes.c_uint64(seed)))
+
+
+def _label_arrays(labels):
+    """labels: a sequence of (row, col, weight) triples (the reference's
+    std::vector<MatrixElement>), or a tuple of three arrays (rows, cols,
+    weights) -> contiguous int32, int32, float32 host arrays."""
+    import numpy as np
+    if isinstance(labels, tuple) and len(labels) == 3 and np.ndim(labels[0]) == 1:
+        rows, cols, weights = labels
+    else:
+        a = np.asarray(labels, np.float64).reshape(-1, 3)
+        rows, cols, weights = a[:, 0], a[:, 1], a[:, 2]
+    rows = np.ascontiguousarray(rows, np.int32)
+    cols = np.ascontiguousarray(cols, np.int32)
+    weights = np.ascontiguousarray(weights, np.float32)
+    if not (rows.shape == cols.shape == weights.shape):
+        raise KcnnError("labels: rows, cols and weights differ in length")
+    return rows, cols, weights
+
+
+def comp_objf_and_deriv(probs, labels, deriv):
+    """CuMatrix::CompObjfAndDeriv: deriv(row, col) += weight / probs(row, col)
+    for the (row, col, weight) elements of `labels` (host; see
+    Nnet.BackpropXent); returns (tot_objf, tot_weight)."""
+    _ensure_init()
+    rows, cols, weights = _label_arrays(labels)
+    objf, weight = ctypes.c_double(), ctypes.c_double()
+    check(lib().kcnn_comp_objf_and_deriv(
+        rows.ctypes.data_as(ctypes.c_void_p), cols.ctypes.data_as(ctypes.c_void_p),
+        weights.ctypes.data_as(ctypes.c_void_p), len(rows), ptr(probs), dim(probs),
+        ptr(deriv), dim(deriv), ctypes.byref(objf), ctypes.byref(weight)))
+    return objf.value, weight.value
+
 
 class Nnet:
     """A stack of components run like upstream nnet2's NnetUpdater."""
@@ -658,6 +705,24 @@ class Nnet:
             return
         for i in reversed(range(self.NumComponents())):
             self.BackpropComponent(i, out_deriv, 0, None, skip_first_dx)
+
+    def BackpropXent(self, labels, skip_first_dx=False):
+        """The backward of a training step from labels (kcnn_nnet_backprop_xent):
+        `labels` are (row, col, weight) elements of the last Propagate's
+        output, sorted by row, as a sequence of triples or a tuple of three
+        arrays.  Adds to the totals ObjfTotal returns; does not synchronise."""
+        rows, cols, weights = _label_arrays(labels)
+        check(lib().kcnn_nnet_backprop_xent(
+            self._h, rows.ctypes.data_as(ctypes.c_void_p),
+            cols.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
+            len(rows), int(skip_first_dx)))
+
+    def ObjfTotal(self, reset=False):
+        """(sum of weight * log-probability, sum of weight) over the
+        BackpropXent calls since the last reset; synchronises."""
+        out = (ctypes.c_double * 2)()
+        check(lib().kcnn_nnet_objf_total(self._h, out, int(bool(reset))))
+        return out[0], out[1]
 
 
 def _device_view(addr, d: MatrixDim):

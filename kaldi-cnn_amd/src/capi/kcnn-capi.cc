@@ -22,6 +22,8 @@
 #include "../kaldi-lite/kaldi-io.h"
 #include "../nnet0/nnet-component-nnet0.h"
 #include "../nnet2/nnet-component.h"
+#include "../nnet2/nnet-kernels.h"
+#include "xent-labels.h"
 
 using namespace kaldi;
 using namespace kaldi::nnet2;
@@ -70,7 +72,23 @@ struct kcnn_nnet {
   std::vector<PoolColDeferred> fdefer;
   std::vector<void *> fpart;
   std::vector<size_t> fpart_bytes;
+  // kcnn_nnet_backprop_xent: the label list's pinned staging buffer and its
+  // device image (xent-labels.h), the event after which the staging buffer
+  // may be rewritten, the fp64 {objective, weight} totals on the device and
+  // the literal path's derivative matrix
+  void *lab_host = nullptr, *lab_dev = nullptr;
+  size_t lab_host_bytes = 0, lab_dev_bytes = 0;
+  hipEvent_t lab_copied = nullptr;
+  double *objf_tot = nullptr;
+  CuMatrix<BaseFloat> xent_deriv;
   ~kcnn_nnet() {
+    if (lab_copied) {
+      (void)hipEventSynchronize(lab_copied);
+      (void)hipEventDestroy(lab_copied);
+    }
+    if (lab_host) (void)hipHostFree(lab_host);
+    if (lab_dev) CuDevice::Instantiate().Free(lab_dev);
+    if (objf_tot) CuDevice::Instantiate().Free(objf_tot);
     for (auto *m : mask)
       if (m) CuDevice::Instantiate().Free(m);
     for (auto *f : fstat)
@@ -620,6 +638,58 @@ int kcnn_component_conv_flip_branch(const kcnn_component *c) {
   return cc->FlipKernelBranch() ? 1 : 0;
 }
 
+namespace {
+DropoutComponent *dropout(const kcnn_component *c) {
+  KALDI_ASSERT(c && c->c);
+  DropoutComponent *d = dynamic_cast<DropoutComponent *>(c->c);
+  if (!d) KALDI_ERR << c->c->Type() << " is not a DropoutComponent";
+  return d;
+}
+}  // namespace
+
+int kcnn_component_set_dropout_scale(kcnn_component *c, float scale) {
+  return guard([&] { dropout(c)->SetDropoutScale(scale); });
+}
+int kcnn_component_dropout_seed(const kcnn_component *c, uint64_t *seed) {
+  return guard([&] { *seed = dropout(c)->Seed(); });
+}
+int kcnn_component_set_dropout_seed(kcnn_component *c, uint64_t seed) {
+  return guard([&] { dropout(c)->SetSeed(seed); });
+}
+
+int kcnn_comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const float *weights,
+                             int num, const float *probs, MatrixDim p_dim, float *deriv,
+                             MatrixDim d_dim, double *tot_objf, double *tot_weight) {
+  return guard([&] {
+    KALDI_ASSERT(p_dim.rows == d_dim.rows && p_dim.cols == d_dim.cols);
+    const std::string bad = kcnn::check_labels(rows, cols, num, p_dim.rows, p_dim.cols, false);
+    if (!bad.empty()) KALDI_ERR << "kcnn_comp_objf_and_deriv: " << bad;
+    CuDevice &d = CuDevice::Instantiate();
+    hipStream_t st = d.Stream();
+    double tot[2] = {0.0, 0.0};
+    if (num > 0) {
+      const size_t n = (size_t)num;
+      CuScratch el(n * 12), ws(kn_objf_ws(kn_comp_objf_blocks(num))), dtot(sizeof(tot));
+      int32_t *dr = static_cast<int32_t *>(el.p), *dc = dr + n;
+      float *dw = reinterpret_cast<float *>(dc + n);
+      CU_SAFE_CALL(hipMemcpyAsync(dr, rows, n * 4, hipMemcpyHostToDevice, st));
+      CU_SAFE_CALL(hipMemcpyAsync(dc, cols, n * 4, hipMemcpyHostToDevice, st));
+      CU_SAFE_CALL(hipMemcpyAsync(dw, weights, n * 4, hipMemcpyHostToDevice, st));
+      CU_SAFE_CALL(hipMemsetAsync(dtot.p, 0, sizeof(tot), st));
+      {
+        CuProfileScope prof("kn_comp_objf_and_deriv");
+        CNSL_SAFE_CALL(kn_comp_objf_and_deriv(dr, dc, dw, num, probs, p_dim, deriv, d_dim,
+                                              static_cast<double *>(dtot.p), ws.p,
+                                              reinterpret_cast<kcnn_stream_t>(st)));
+      }
+      CU_SAFE_CALL(hipMemcpyAsync(tot, dtot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+      CU_SAFE_CALL(hipStreamSynchronize(st));
+    }
+    if (tot_objf) *tot_objf = tot[0];
+    if (tot_weight) *tot_weight = tot[1];
+  });
+}
+
 // ---- component stack ---------------------------------------------------------------
 kcnn_nnet *kcnn_nnet_new(const char *config) {
   std::unique_ptr<kcnn_nnet> n(new kcnn_nnet());
@@ -945,6 +1015,91 @@ int kcnn_nnet_backprop(kcnn_nnet *n, const float *out_deriv, MatrixDim od_dim) {
     if (rc) return rc;
   }
   return 0;
+}
+
+static double *nnet_objf_tot(kcnn_nnet *n) {
+  if (!n->objf_tot) {
+    n->objf_tot = static_cast<double *>(CuDevice::Instantiate().Malloc(2 * sizeof(double)));
+    CU_SAFE_CALL(hipMemsetAsync(n->objf_tot, 0, 2 * sizeof(double),
+                                CuDevice::Instantiate().Stream()));
+  }
+  return n->objf_tot;
+}
+
+int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
+                            const float *weights, int num, int skip_first_dx) {
+  const int nc = (int)n->comps.size();
+  int first = nc - 1;  // the component the generic backward starts at
+  int rc = guard([&] {
+    const CuMatrix<BaseFloat> &out = n->fwd[nc];
+    const int N = out.NumRows(), dim = n->comps[nc - 1]->OutputDim();
+    if (N == 0 || out.NumCols() != dim) KALDI_ERR << "kcnn_nnet_backprop_xent: no Propagate ran";
+    if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_nnet_backprop_xent: bad label arrays";
+    // every check before any launch
+    const std::string bad = kcnn::check_labels(rows, cols, num, N, dim, true);
+    if (!bad.empty()) KALDI_ERR << "kcnn_nnet_backprop_xent: " << bad;
+    CuDevice &d = CuDevice::Instantiate();
+    hipStream_t st = d.Stream();
+    // the list -> pinned staging buffer -> device, on the library's stream
+    const kcnn::LabelLayout lay = kcnn::label_layout(num, N);
+    if (n->lab_copied == nullptr)
+      CU_SAFE_CALL(hipEventCreateWithFlags(&n->lab_copied, hipEventDisableTiming));
+    else
+      CU_SAFE_CALL(hipEventSynchronize(n->lab_copied));  // the last copy has left the buffer
+    if (n->lab_host_bytes < lay.bytes) {
+      if (n->lab_host) CU_SAFE_CALL(hipHostFree(n->lab_host));
+      n->lab_host = nullptr;
+      n->lab_host_bytes = 0;
+      CU_SAFE_CALL(hipHostMalloc(&n->lab_host, lay.bytes, hipHostMallocDefault));
+      n->lab_host_bytes = lay.bytes;
+    }
+    if (n->lab_dev_bytes < lay.bytes) {
+      if (n->lab_dev) d.Free(n->lab_dev);
+      n->lab_dev = d.Malloc(lay.bytes);
+      n->lab_dev_bytes = lay.bytes;
+    }
+    kcnn::stage_labels(rows, cols, weights, num, N, n->lab_host);
+    CU_SAFE_CALL(hipMemcpyAsync(n->lab_dev, n->lab_host, lay.bytes, hipMemcpyHostToDevice, st));
+    CU_SAFE_CALL(hipEventRecord(n->lab_copied, st));
+    const char *base = static_cast<const char *>(n->lab_dev);
+    const int32_t *d_start = reinterpret_cast<const int32_t *>(base + lay.row_start);
+    const int32_t *d_row = reinterpret_cast<const int32_t *>(base + lay.row);
+    const int32_t *d_col = reinterpret_cast<const int32_t *>(base + lay.col);
+    const float *d_w = reinterpret_cast<const float *>(base + lay.weight);
+    double *tot = nnet_objf_tot(n);
+    auto *softmax = dynamic_cast<SoftmaxComponent *>(n->comps[nc - 1]);
+    if (softmax != nullptr && !cnsl::nnet0::LiteralPath()) {
+      // zeroed derivative + CompObjfAndDeriv + the Softmax's Backprop, fused
+      softmax->BackpropXent(out, d_start, d_col, d_w, tot, softmax, &n->deriv[nc - 1]);
+      first = nc - 2;
+    } else {
+      // NnetUpdater::ComputeObjfAndDeriv: a zeroed [rows x OutputDim] matrix,
+      // CompObjfAndDeriv against the last output; Backprop follows
+      n->xent_deriv.Resize(N, dim, kSetZero);
+      if (num > 0) {
+        CuScratch ws(kn_objf_ws(kn_comp_objf_blocks(num)));
+        CuProfileScope prof("kn_comp_objf_and_deriv");
+        CNSL_SAFE_CALL(kn_comp_objf_and_deriv(d_row, d_col, d_w, num, out.Data(), out.Dim(),
+                                              n->xent_deriv.Data(), n->xent_deriv.Dim(), tot,
+                                              ws.p, reinterpret_cast<kcnn_stream_t>(st)));
+      }
+    }
+  });
+  for (int i = first; rc == 0 && i >= 0; i--)
+    rc = kcnn_nnet_backprop_component(n, i, n->xent_deriv.Data(), n->xent_deriv.Dim(), 0,
+                                      nullptr, skip_first_dx);
+  return rc;
+}
+
+int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset) {
+  return guard([&] {
+    CuDevice &d = CuDevice::Instantiate();
+    hipStream_t st = d.Stream();
+    double *tot = nnet_objf_tot(n);
+    CU_SAFE_CALL(hipMemcpyAsync(out, tot, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (reset) CU_SAFE_CALL(hipMemsetAsync(tot, 0, 2 * sizeof(double), st));
+    CU_SAFE_CALL(hipStreamSynchronize(st));
+  });
 }
 
 }  // extern "C"

@@ -46,6 +46,11 @@ void SetRandnSeed(uint64_t seed) {
   g_rng_state = seed;
 }
 
+uint64_t RandU64() {
+  std::lock_guard<std::mutex> lk(g_rng_mu);
+  return splitmix64();
+}
+
 void RandnFill(float *dst, size_t n) {
   std::lock_guard<std::mutex> lk(g_rng_mu);
   for (size_t i = 0; i < n; i += 2) {

@@ -370,6 +370,8 @@ class CuGemmBackpropStats {
 /// Host N(0,1) generator shared by SetRandn (splitmix64 -> Box-Muller).
 void RandnFill(float *dst, size_t n);
 void SetRandnSeed(uint64_t seed);
+/// The next 64 bits of the same generator (the seeds of RandomComponents).
+uint64_t RandU64();
 
 }  // namespace kaldi
 

@@ -70,6 +70,10 @@ Component *Component::NewComponentOfType(const std::string &component_type) {
     ans = new RectifiedLinearComponent();
   } else if (component_type == "SpliceComponent") {
     ans = new SpliceComponent();
+  } else if (component_type == "SoftmaxComponent") {
+    ans = new SoftmaxComponent();
+  } else if (component_type == "DropoutComponent") {
+    ans = new DropoutComponent();
   }
   return ans;
 }
@@ -602,6 +606,162 @@ void RectifiedLinearComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
                                   ds, ws, NS());
   if (ws) CuDevice::Instantiate().Free(ws);
   CNSL_SAFE_CALL(rc);
+}
+
+namespace {
+bool SameDim(const CuMatrixBase<BaseFloat> &a, const CuMatrixBase<BaseFloat> &b) {
+  return a.NumRows() == b.NumRows() && a.NumCols() == b.NumCols();
+}
+}  // namespace
+
+// ---- SoftmaxComponent (reference nnet-component.cc:930-1000) ----------------
+void SoftmaxComponent::Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                                 const CuMatrixBase<BaseFloat> &in,
+                                 CuMatrixBase<BaseFloat> *out) const {
+  in_info.CheckSize(in);
+  out_info.CheckSize(*out);
+  KALDI_ASSERT(in_info.NumChunks() == out_info.NumChunks());
+  // out->ApplySoftMaxPerRow(in); out->ApplyFloor(1.0e-20) -- one pass
+  CuProfileScope prof("kn_softmax_prop");
+  CNSL_SAFE_CALL(kn_softmax_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), NS()));
+}
+
+// UpdateStats(out_value) with no derivative (:337-363, :995-999): the count
+// here, the column sums by the kernel that reads out_value anyway.
+void SoftmaxComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
+                                const CuMatrixBase<BaseFloat> &,
+                                const CuMatrixBase<BaseFloat> &out_value,
+                                const CuMatrixBase<BaseFloat> &out_deriv, Component *to_update,
+                                CuMatrix<BaseFloat> *in_deriv) const {
+  in_deriv->Resize(out_deriv.NumRows(), out_deriv.NumCols(), kUndefined);
+  KALDI_ASSERT(SameDim(out_value, out_deriv) && SameDim(out_value, *in_deriv));
+  NonlinearComponent *u = to_update ? dynamic_cast<NonlinearComponent *>(to_update) : nullptr;
+  double *vs = nullptr;
+  if (u != nullptr) {
+    KALDI_ASSERT(out_value.NumCols() == u->InputDim());
+    u->EnsureStats();
+    u->count_ += out_value.NumRows();
+    vs = u->value_sum_;
+  }
+  CuScratch ws(vs ? kn_softmax_stats_ws(out_value.Dim()) : 0);
+  CuProfileScope prof("kn_softmax_backprop");
+  CNSL_SAFE_CALL(kn_softmax_backprop(out_value.Data(), out_value.Dim(), out_deriv.Data(),
+                                     out_deriv.Dim(), in_deriv->Data(), in_deriv->Dim(), vs,
+                                     ws.p, NS()));
+}
+
+void SoftmaxComponent::BackpropXent(const CuMatrixBase<BaseFloat> &out_value,
+                                    const int32 *row_start, const int32 *label_col,
+                                    const BaseFloat *label_weight, double *tot,
+                                    Component *to_update, CuMatrix<BaseFloat> *in_deriv) const {
+  in_deriv->Resize(out_value.NumRows(), out_value.NumCols(), kUndefined);
+  NonlinearComponent *u = to_update ? dynamic_cast<NonlinearComponent *>(to_update) : nullptr;
+  double *vs = nullptr;
+  if (u != nullptr) {
+    KALDI_ASSERT(out_value.NumCols() == u->InputDim());
+    u->EnsureStats();
+    u->count_ += out_value.NumRows();
+    vs = u->value_sum_;
+  }
+  CuScratch stats_ws(vs ? kn_softmax_stats_ws(out_value.Dim()) : 0);
+  CuScratch objf_ws(kn_objf_ws(kn_softmax_xent_blocks(out_value.Dim())));
+  CuProfileScope prof("kn_softmax_xent_backprop");
+  CNSL_SAFE_CALL(kn_softmax_xent_backprop(out_value.Data(), out_value.Dim(), in_deriv->Data(),
+                                          in_deriv->Dim(), row_start, label_col, label_weight,
+                                          vs, stats_ws.p, tot, objf_ws.p, NS()));
+}
+
+// ---- RandomComponent / DropoutComponent (reference nnet-component.cc:3540-3643) ----
+void RandomComponent::DrawSeed() { SetSeed(RandU64()); }
+
+std::string DropoutComponent::Info() const {
+  std::stringstream stream;
+  stream << Component::Info() << ", dropout_proportion = " << dropout_proportion_
+         << ", dropout_scale = " << dropout_scale_;
+  return stream.str();
+}
+
+void DropoutComponent::Init(int32 dim, BaseFloat dropout_proportion,
+                            BaseFloat dropout_scale) {
+  dim_ = dim;
+  dropout_proportion_ = dropout_proportion;
+  dropout_scale_ = dropout_scale;
+  DrawSeed();
+}
+
+void DropoutComponent::InitFromString(std::string args) {
+  std::string orig_args(args);
+  int32 dim = 0;
+  BaseFloat dropout_proportion = 0.5, dropout_scale = 0.0;
+  bool ok = ParseFromString("dim", &args, &dim);
+  ParseFromString("dropout-proportion", &args, &dropout_proportion);
+  ParseFromString("dropout-scale", &args, &dropout_scale);
+  if (!ok || !args.empty() || dim <= 0)
+    KALDI_ERR << "Invalid initializer for layer of type DropoutComponent: \""
+              << orig_args << "\"";
+  Init(dim, dropout_proportion, dropout_scale);
+}
+
+void DropoutComponent::Read(std::istream &is, bool binary) {
+  ExpectOneOrTwoTokens(is, binary, "<DropoutComponent>", "<Dim>");
+  ReadBasicType(is, binary, &dim_);
+  ExpectToken(is, binary, "<DropoutScale>");
+  ReadBasicType(is, binary, &dropout_scale_);
+  ExpectToken(is, binary, "<DropoutProportion>");
+  ReadBasicType(is, binary, &dropout_proportion_);
+  ExpectToken(is, binary, "</DropoutComponent>");
+  DrawSeed();
+}
+
+void DropoutComponent::Write(std::ostream &os, bool binary) const {
+  WriteToken(os, binary, "<DropoutComponent>");
+  WriteToken(os, binary, "<Dim>");
+  WriteBasicType(os, binary, dim_);
+  WriteToken(os, binary, "<DropoutScale>");
+  WriteBasicType(os, binary, dropout_scale_);
+  WriteToken(os, binary, "<DropoutProportion>");
+  WriteBasicType(os, binary, dropout_proportion_);
+  WriteToken(os, binary, "</DropoutComponent>");
+}
+
+// A fresh generator, as the reference's (:3639-3643).
+Component *DropoutComponent::Copy() const {
+  return new DropoutComponent(dim_, dropout_proportion_, dropout_scale_);
+}
+
+void DropoutComponent::Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                                 const CuMatrixBase<BaseFloat> &in,
+                                 CuMatrixBase<BaseFloat> *out) const {
+  in_info.CheckSize(in);
+  out_info.CheckSize(*out);
+  KALDI_ASSERT(in_info.NumChunks() == out_info.NumChunks());
+  KALDI_ASSERT(in.NumCols() == this->InputDim());
+  BaseFloat dp = dropout_proportion_;
+  KALDI_ASSERT(dp < 1.0 && dp >= 0.0);
+  KALDI_ASSERT(dropout_scale_ <= 1.0 && dropout_scale_ >= 0.0);
+  BaseFloat low_scale = dropout_scale_,
+            high_scale = (1.0 - (dp * low_scale)) / (1.0 - dp),
+            average = (low_scale * dp) + (high_scale * (1.0 - dp));
+  KALDI_ASSERT(fabs(average - 1.0) < 0.01);
+  // RandUniform; Add(-dp); ApplyHeaviside; Scale(high - low) unless 1;
+  // Add(low) unless 0; MulElements(in) -- one pass, the draw generated in it
+  CuProfileScope prof("kn_dropout_prop");
+  CNSL_SAFE_CALL(kn_dropout_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), dp,
+                                 high_scale - low_scale, low_scale, seed_, NextCall(), NS()));
+}
+
+void DropoutComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
+                                const CuMatrixBase<BaseFloat> &in_value,
+                                const CuMatrixBase<BaseFloat> &out_value,
+                                const CuMatrixBase<BaseFloat> &out_deriv, Component *,
+                                CuMatrix<BaseFloat> *in_deriv) const {
+  KALDI_ASSERT(SameDim(in_value, out_value) && SameDim(in_value, out_deriv));
+  in_deriv->Resize(out_deriv.NumRows(), out_deriv.NumCols(), kUndefined);
+  // in_deriv->AddMatMatDivMat(out_deriv, out_value, in_value)
+  CuProfileScope prof("kn_dropout_backprop");
+  CNSL_SAFE_CALL(kn_dropout_backprop(in_value.Data(), in_value.Dim(), out_value.Data(),
+                                     out_value.Dim(), out_deriv.Data(), out_deriv.Dim(),
+                                     in_deriv->Data(), in_deriv->Dim(), NS()));
 }
 
 // ---- SpliceComponent (reference nnet-component.cc:2524-2866) ----------------

@@ -7,6 +7,7 @@
 #ifndef KCNN_NNET2_NNET_COMPONENT_H_
 #define KCNN_NNET2_NNET_COMPONENT_H_
 
+#include <atomic>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -252,6 +253,7 @@ class NonlinearComponent : public Component {
 
  protected:
   friend class RectifiedLinearComponent;  // UpdateStats on to_update (:821)
+  friend class SoftmaxComponent;          // (:995-999)
   // Make the fp64 stat vectors dim_ long (zeroed) if they are not.
   void EnsureStats();
   int32 dim_;
@@ -322,6 +324,99 @@ class SpliceComponent : public Component {
   int32 input_dim_;
   std::vector<int32> context_;
   int32 const_component_dim_;
+};
+
+// reference nnet-component.h:642-662, nnet-component.cc:930-1000.  Read,
+// Write, Scale and Add are NonlinearComponent's.
+class SoftmaxComponent : public NonlinearComponent {
+ public:
+  explicit SoftmaxComponent(int32 dim) : NonlinearComponent(dim) {}
+  explicit SoftmaxComponent(const SoftmaxComponent &other) : NonlinearComponent(other) {}
+  SoftmaxComponent() {}
+  virtual std::string Type() const { return "SoftmaxComponent"; }
+  virtual Component *Copy() const { return new SoftmaxComponent(*this); }
+  virtual bool BackpropNeedsInput() const { return false; }
+  virtual bool BackpropNeedsOutput() const { return true; }
+  using Component::Propagate;
+  virtual void Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                         const CuMatrixBase<BaseFloat> &in,
+                         CuMatrixBase<BaseFloat> *out) const;
+  virtual void Backprop(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                        const CuMatrixBase<BaseFloat> &in_value,
+                        const CuMatrixBase<BaseFloat> &out_value,
+                        const CuMatrixBase<BaseFloat> &out_deriv,
+                        Component *to_update,
+                        CuMatrix<BaseFloat> *in_deriv) const;
+  // ---- MI355X build: the loss and this Backprop in one pass ---------------
+  // NnetUpdater's zeroed derivative, CompObjfAndDeriv on out_value and
+  // Backprop, for labels sorted by row (DEVICE arrays: row r's columns and
+  // weights at [row_start[r], row_start[r + 1])).  Adds the objective and the
+  // weight to the device fp64 pair tot; stats on to_update as Backprop does.
+  void BackpropXent(const CuMatrixBase<BaseFloat> &out_value, const int32 *row_start,
+                    const int32 *label_col, const BaseFloat *label_weight, double *tot,
+                    Component *to_update, CuMatrix<BaseFloat> *in_deriv) const;
+
+ private:
+  SoftmaxComponent &operator=(const SoftmaxComponent &other);
+};
+
+// reference nnet-component.h:1555-1582: a component that draws random
+// numbers.  Here the generator is counter-based: the state is a 64-bit seed
+// and the number of Propagate calls so far, the draw of an element a pure
+// function of (seed, call, row, column).  The seed comes from the host
+// generator (SetRandnSeed makes it reproducible); the file format has none.
+class RandomComponent : public Component {
+ public:
+  RandomComponent() : dim_(0), seed_(0), calls_(0) {}
+  virtual int32 InputDim() const { return dim_; }
+  virtual int32 OutputDim() const { return dim_; }
+  uint64_t Seed() const { return seed_; }
+  // Also restarts the call count.
+  void SetSeed(uint64_t seed) { seed_ = seed; calls_.store(0); }
+
+ protected:
+  void DrawSeed();
+  // The call number of this Propagate (Propagate is const and may run from
+  // several host threads).
+  uint64_t NextCall() const { return calls_.fetch_add(1); }
+  int32 dim_;
+  uint64_t seed_;
+  mutable std::atomic<uint64_t> calls_;
+};
+
+// reference nnet-component.h:1584-1630, nnet-component.cc:3540-3643.  The
+// file's token order is <Dim> <DropoutScale> <DropoutProportion>: scale
+// before proportion, unlike upstream.
+class DropoutComponent : public RandomComponent {
+ public:
+  DropoutComponent(int32 dim, BaseFloat dp = 0.5, BaseFloat sc = 0.0) { Init(dim, dp, sc); }
+  DropoutComponent() : dropout_proportion_(0.5), dropout_scale_(0.0) {}
+  void Init(int32 dim, BaseFloat dropout_proportion = 0.5, BaseFloat dropout_scale = 0.0);
+  virtual std::string Type() const { return "DropoutComponent"; }
+  virtual std::string Info() const;
+  virtual void InitFromString(std::string args);
+  virtual void Read(std::istream &is, bool binary);
+  virtual void Write(std::ostream &os, bool binary) const;
+  void SetDropoutScale(BaseFloat scale) { dropout_scale_ = scale; }
+  BaseFloat DropoutScale() const { return dropout_scale_; }
+  BaseFloat DropoutProportion() const { return dropout_proportion_; }
+  virtual bool BackpropNeedsInput() const { return true; }
+  virtual bool BackpropNeedsOutput() const { return true; }
+  virtual Component *Copy() const;
+  using Component::Propagate;
+  virtual void Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                         const CuMatrixBase<BaseFloat> &in,
+                         CuMatrixBase<BaseFloat> *out) const;
+  virtual void Backprop(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                        const CuMatrixBase<BaseFloat> &in_value,
+                        const CuMatrixBase<BaseFloat> &out_value,
+                        const CuMatrixBase<BaseFloat> &out_deriv,
+                        Component *to_update,
+                        CuMatrix<BaseFloat> *in_deriv) const;
+
+ private:
+  BaseFloat dropout_proportion_;
+  BaseFloat dropout_scale_;
 };
 
 /// Shared by the components' Read functions (nnet-component-nnet0.cc:24-39).

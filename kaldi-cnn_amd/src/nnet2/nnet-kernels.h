@@ -6,6 +6,7 @@
 #define KCNN_NNET2_NNET_KERNELS_H_
 
 #include <stddef.h>
+#include <stdint.h>
 
 #include "cnsl-hip-kernels.h"
 
@@ -57,6 +58,60 @@ int kn_splice_backprop(const float *out_deriv, MatrixDim od_dim, float *in_deriv
  * y = beta * y + alpha * x  (x may be NULL: y = beta * y). */
 int kn_dvec_update(double *y, const double *x, double alpha, double beta, int n,
                    kcnn_stream_t st);
+
+/* ---- nnet-loss-kernels.hip: Softmax, Dropout and the cross-entropy objective ---- */
+
+/* SoftmaxComponent::Propagate (reference nnet-component.cc:930-947): per row
+ * y = exp(x - max x) / sum, then ApplyFloor(1e-20) (NaN stays). */
+int kn_softmax_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                    kcnn_stream_t st);
+
+/* SoftmaxComponent::Backprop (:949-1000): D = P o E - diag(rowdot(P, E)) P.
+ * With value_sum != NULL also UpdateStats(out_value): the column sums of P
+ * (fixed order) added to the fp64 value_sum.  ws: kn_softmax_stats_ws(dim)
+ * bytes. */
+size_t kn_softmax_stats_ws(MatrixDim dim);
+int kn_softmax_backprop(const float *out_value, MatrixDim ov_dim, const float *out_deriv,
+                        MatrixDim od_dim, float *in_deriv, MatrixDim id_dim, double *value_sum,
+                        void *ws, kcnn_stream_t st);
+
+/* CuMatrix::CompObjfAndDeriv (reference cu-matrix.h:624-637) for num DEVICE
+ * elements {row, col, weight} with no repeated (row, col): deriv(row, col) +=
+ * weight / probs(row, col); tot[0] += sum weight * log probs(row, col), tot[1]
+ * += sum weight (device fp64, reduced in a fixed order).  Elements outside
+ * the matrix are skipped.  ws: kn_objf_ws(kn_comp_objf_blocks(num)) bytes. */
+size_t kn_objf_ws(int num_blocks);
+int kn_comp_objf_blocks(int num);
+int kn_comp_objf_and_deriv(const int *el_row, const int *el_col, const float *el_w, int num,
+                           const float *probs, MatrixDim p_dim, float *deriv, MatrixDim d_dim,
+                           double *tot, void *ws, kcnn_stream_t st);
+
+/* Zeroed derivative + CompObjfAndDeriv + Softmax Backprop in one pass, for a
+ * SoftmaxComponent that is the last component.  Labels sorted by row: row r's
+ * are lab_col / lab_w [row_start[r], row_start[r + 1]) (device; row_start has
+ * rows + 1 entries).  S_r = sum of the row's weights; in_deriv = -P S_r, plus
+ * the weight at a label; tot as above; value_sum (nullable) as in
+ * kn_softmax_backprop.  objf_ws: kn_objf_ws(kn_softmax_xent_blocks(dim)). */
+int kn_softmax_xent_blocks(MatrixDim dim);
+int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in_deriv,
+                             MatrixDim id_dim, const int *row_start, const int *lab_col,
+                             const float *lab_w, double *value_sum, void *stats_ws, double *tot,
+                             void *objf_ws, kcnn_stream_t st);
+
+/* DropoutComponent::Propagate (:3592-3625).  The uniform draw of element
+ * (row, col) is output col % 4 of Philox4x32-10 with key = seed and counter =
+ * (col / 4, row, call low, call high), u = (x >> 8) * 2^-24; then in fp32
+ * mask = Heaviside(u - dropout_proportion), scaled by high_minus_low unless
+ * that is 1, plus low unless that is 0; out = mask * in. */
+int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                    float dropout_proportion, float high_minus_low, float low, uint64_t seed,
+                    uint64_t call, kcnn_stream_t st);
+
+/* DropoutComponent::Backprop (:3627-3637), upstream AddMatMatDivMat:
+ * in_deriv = in_value == 0 ? out_deriv : out_deriv * out_value / in_value. */
+int kn_dropout_backprop(const float *in_value, MatrixDim iv_dim, const float *out_value,
+                        MatrixDim ov_dim, const float *out_deriv, MatrixDim od_dim,
+                        float *in_deriv, MatrixDim id_dim, kcnn_stream_t st);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,810 @@
+// nnet2/nnet-loss-kernels.hip -- SoftmaxComponent, DropoutComponent and the
+// cross-entropy objective (CuMatrix::CompObjfAndDeriv) on gfx950.  All are
+// HBM-bound and built to touch every byte once:
+//   * softmax rows of up to 4096 columns live in one wave's registers (64
+//     values a lane): max, sum and the row dot product are cross-lane
+//     reductions, no LDS and no barrier; wider rows run a block-per-row form
+//     that re-reads the row;
+//   * lanes take 4, 2 or 1 consecutive columns (16-, 8- or 4-byte accesses)
+//     as the pointers and strides allow;
+//   * column sums of P (NonlinearComponent::UpdateStats) and the objective
+//     are reduced in a fixed order (per-part partials, then one ordered final
+//     pass), never with float atomics, so results repeat bit for bit;
+//   * the dropout mask is Philox4x32-10 of (seed, call, row, column / 4): a
+//     pure function of the element's position, not of the launch geometry.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <type_traits>
+
+#include "nnet-kernels.h"
+#include "../cnslmat/hip-util.h"
+
+using kcnn::FastDiv;
+
+namespace {
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ---- a row in one wave's registers -------------------------------------------
+// TOT values a lane, as TOT / V vectors of V consecutive columns: value
+// k * V + s of a lane is column (k * 64 + lane) * V + s.  A vector that
+// crosses the row's end is accessed element by element.
+template <int V, int TOT>
+__device__ __forceinline__ int row_col(int lane, int j) {
+  return ((j / V) * 64 + lane) * V + (j % V);
+}
+
+template <int V, int TOT>
+__device__ __forceinline__ void load_row(const float *__restrict__ row, int cols, int lane,
+                                         float fill, float (&v)[TOT]) {
+#pragma unroll
+  for (int k = 0; k < TOT / V; k++) {
+    const int c = (k * 64 + lane) * V;
+    if (c + V <= cols) {
+      if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(row + c);
+        v[k * 4] = t.x; v[k * 4 + 1] = t.y; v[k * 4 + 2] = t.z; v[k * 4 + 3] = t.w;
+      } else if constexpr (V == 2) {
+        const float2 t = *reinterpret_cast<const float2 *>(row + c);
+        v[k * 2] = t.x; v[k * 2 + 1] = t.y;
+      } else {
+        v[k] = row[c];
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < V; s++) v[k * V + s] = c + s < cols ? row[c + s] : fill;
+    }
+  }
+}
+
+template <int V, int TOT>
+__device__ __forceinline__ void store_row(float *__restrict__ row, int cols, int lane,
+                                          const float (&v)[TOT]) {
+#pragma unroll
+  for (int k = 0; k < TOT / V; k++) {
+    const int c = (k * 64 + lane) * V;
+    if (c + V <= cols) {
+      if constexpr (V == 4) {
+        *reinterpret_cast<float4 *>(row + c) =
+            make_float4(v[k * 4], v[k * 4 + 1], v[k * 4 + 2], v[k * 4 + 3]);
+      } else if constexpr (V == 2) {
+        *reinterpret_cast<float2 *>(row + c) = make_float2(v[k * 2], v[k * 2 + 1]);
+      } else {
+        row[c] = v[k];
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < V; s++)
+        if (c + s < cols) row[c + s] = v[k * V + s];
+    }
+  }
+}
+
+constexpr int kWaveRowMaxCols = 4096;  // 64 lanes x 64 values
+constexpr float kSoftmaxFloor = 1.0e-20f;
+
+// ---- Softmax Propagate ---------------------------------------------------------
+// One wave per row, four rows to a block.
+template <int V, int TOT>
+__global__ __launch_bounds__(256) void softmax_prop_wave_kernel(const float *__restrict__ in,
+                                                                int64_t is,
+                                                                float *__restrict__ out,
+                                                                int64_t os, int rows, int cols) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  float v[TOT];
+  load_row<V, TOT>(in + (int64_t)r * is, cols, lane, -INFINITY, v);
+  float m = v[0];
+#pragma unroll
+  for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
+  m = wave_max(m);
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TOT; j++) {
+    v[j] = expf(v[j] - m);  // the accurate exp: the 1e-5 bar holds down to x - m = -46
+    s += v[j];
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int j = 0; j < TOT; j++) {
+    float y = v[j] / s;
+    if (y < kSoftmaxFloor) y = kSoftmaxFloor;  // ApplyFloor(1e-20); NaN stays
+    v[j] = y;
+  }
+  store_row<V, TOT>(out + (int64_t)r * os, cols, lane, v);
+}
+
+// The four waves' values of a block reduction, combined in wave order.
+__device__ __forceinline__ float block_max(float v, float *red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float block_sum(float v, float *red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Rows wider than a wave holds: a block per row, the row read three times.
+__global__ __launch_bounds__(256) void softmax_prop_block_kernel(const float *__restrict__ in,
+                                                                 int64_t is,
+                                                                 float *__restrict__ out,
+                                                                 int64_t os, int rows, int cols) {
+  __shared__ float red[4];
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float *x = in + (int64_t)r * is;
+    float *y = out + (int64_t)r * os;
+    float m = -INFINITY;
+    for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
+    m = block_max(m, red);
+    float s = 0.0f;
+    for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
+    s = block_sum(s, red);
+    for (int c = threadIdx.x; c < cols; c += 256) {
+      float v = expf(x[c] - m) / s;
+      if (v < kSoftmaxFloor) v = kSoftmaxFloor;
+      y[c] = v;
+    }
+  }
+}
+
+// ---- column sums of P in a fixed order -------------------------------------------
+// A block of the wave-per-row kernels is one part of kSmRowsPerPart rows,
+// wave w taking rows w, w + 4, ...; a part's column sums are the four
+// waves' sums added in wave order, and the final pass adds the parts in
+// order (fp64).  16 rows, not the 64 of the element-wise ReLU kernel: a block
+// here spans whole rows, so 64-row parts would leave a 4096-row minibatch
+// with 64 blocks for 256 compute units.
+constexpr int kSmRowsPerPart = 16;
+constexpr int kColRowsPerPart = 64;  // parts of colsum_part_kernel
+
+template <int V, int TOT>
+__device__ __forceinline__ void part_colsum_store(float (&cs)[TOT], float *red, int lane, int w,
+                                                  float *__restrict__ part_row, int cols) {
+  if (w > 0) {
+#pragma unroll
+    for (int j = 0; j < TOT; j++) red[((w - 1) * TOT + j) * 64 + lane] = cs[j];
+  }
+  __syncthreads();
+  if (w > 0) return;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+#pragma unroll
+    for (int j = 0; j < TOT; j++) cs[j] += red[(k * TOT + j) * 64 + lane];
+  }
+#pragma unroll
+  for (int j = 0; j < TOT; j++) {
+    const int c = row_col<V, TOT>(lane, j);
+    if (c < cols) part_row[c] = cs[j];
+  }
+}
+
+// Column sums of one 64-row part, a thread per column (the wide-row path).
+__global__ __launch_bounds__(256) void colsum_part_kernel(const float *__restrict__ p, int64_t ps,
+                                                          int rows, int cols,
+                                                          float *__restrict__ part) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  const int r0 = blockIdx.y * kColRowsPerPart;
+  const int r1 = min(rows, r0 + kColRowsPerPart);
+  float s = 0.0f;
+  for (int r = r0; r < r1; r++) s += p[(int64_t)r * ps + c];
+  part[(int64_t)blockIdx.y * cols + c] = s;
+}
+
+// A block takes 64 columns: wave w of 16 adds its sixteenth of the parts in
+// order (fp64), then the first wave adds the 16 sums in wave order.  (A
+// thread per column alone leaves 54 waves walking 256 parts one load at a
+// time: 64 us at 4096 x 3454, twice the kernel that made the parts.)
+constexpr int kFinalWaves = 16;
+__global__ __launch_bounds__(1024) void colsum_final_kernel(const float *__restrict__ part,
+                                                            int nparts, int cols,
+                                                            double *__restrict__ value_sum) {
+  __shared__ double red[kFinalWaves][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const int per = (nparts + kFinalWaves - 1) / kFinalWaves;
+  const int p0 = w * per, p1 = min(nparts, p0 + per);
+  double s = 0.0;
+  if (c < cols)
+    for (int p = p0; p < p1; p++) s += (double)part[(int64_t)p * cols + c];
+  red[w][lane] = s;
+  __syncthreads();
+  if (w != 0 || c >= cols) return;
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < kFinalWaves; k++) t += red[k][lane];
+  value_sum[c] += t;
+}
+
+// ---- Softmax Backprop, general E ---------------------------------------------------
+// D = P o E - diag(rowdot(P, E)) P from one read of P and E.
+template <int V, int TOT, bool STATS>
+__global__ __launch_bounds__(256) void softmax_backprop_wave_kernel(
+    const float *__restrict__ P, int64_t ps, const float *__restrict__ E, int64_t es,
+    float *__restrict__ D, int64_t ds, int rows, int cols, float *__restrict__ part) {
+  __shared__ float red[STATS ? 3 * TOT * 64 : 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * kSmRowsPerPart;
+  const int r1 = min(rows, r0 + kSmRowsPerPart);
+  float cs[STATS ? TOT : 1];
+  if constexpr (STATS) {
+#pragma unroll
+    for (int j = 0; j < TOT; j++) cs[j] = 0.0f;
+  }
+  for (int r = r0 + w; r < r1; r += 4) {
+    float p[TOT], e[TOT];
+    load_row<V, TOT>(P + (int64_t)r * ps, cols, lane, 0.0f, p);
+    load_row<V, TOT>(E + (int64_t)r * es, cols, lane, 0.0f, e);
+    float dot = 0.0f;
+#pragma unroll
+    for (int j = 0; j < TOT; j++) {
+      e[j] = p[j] * e[j];
+      dot += e[j];
+    }
+    dot = wave_sum(dot);
+#pragma unroll
+    for (int j = 0; j < TOT; j++) {
+      e[j] = e[j] - dot * p[j];
+      if constexpr (STATS) cs[j] += p[j];
+    }
+    store_row<V, TOT>(D + (int64_t)r * ds, cols, lane, e);
+  }
+  if constexpr (STATS)
+    part_colsum_store<V, TOT>(cs, red, lane, w, part + (int64_t)blockIdx.x * cols, cols);
+}
+
+__global__ __launch_bounds__(256) void softmax_backprop_block_kernel(
+    const float *__restrict__ P, int64_t ps, const float *__restrict__ E, int64_t es,
+    float *__restrict__ D, int64_t ds, int rows, int cols) {
+  __shared__ float red[4];
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float *p = P + (int64_t)r * ps, *e = E + (int64_t)r * es;
+    float *d = D + (int64_t)r * ds;
+    float dot = 0.0f;
+    for (int c = threadIdx.x; c < cols; c += 256) dot += p[c] * e[c];
+    dot = block_sum(dot, red);
+    for (int c = threadIdx.x; c < cols; c += 256) d[c] = p[c] * e[c] - dot * p[c];
+  }
+}
+
+// ---- CompObjfAndDeriv ----------------------------------------------------------------
+// The objective terms of a block, reduced in a fixed order into its partial.
+__device__ __forceinline__ void block_objf_store(double objf, double wsum, double (*dred)[2],
+                                                 double *__restrict__ objf_part) {
+  objf = wave_sum(objf);
+  wsum = wave_sum(wsum);
+  if ((threadIdx.x & 63) == 0) {
+    dred[threadIdx.x >> 6][0] = objf;
+    dred[threadIdx.x >> 6][1] = wsum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    objf_part[2 * (size_t)blockIdx.x] = ((dred[0][0] + dred[1][0]) + dred[2][0]) + dred[3][0];
+    objf_part[2 * (size_t)blockIdx.x + 1] =
+        ((dred[0][1] + dred[1][1]) + dred[2][1]) + dred[3][1];
+  }
+}
+
+// deriv(row, col) += weight / A(row, col); elements outside the matrix are
+// skipped (the hosts validate before they launch).
+__global__ __launch_bounds__(256) void comp_objf_kernel(
+    const int *__restrict__ el_row, const int *__restrict__ el_col,
+    const float *__restrict__ el_w, int num, const float *__restrict__ A, int64_t as,
+    float *__restrict__ deriv, int64_t ds, int rows, int cols, double *__restrict__ objf_part) {
+  __shared__ double dred[4][2];
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  double objf = 0.0, wsum = 0.0;
+  if (e < num) {
+    const int r = el_row[e], c = el_col[e];
+    if (r >= 0 && r < rows && c >= 0 && c < cols) {
+      const float w = el_w[e];
+      const float a = A[(int64_t)r * as + c];
+      deriv[(int64_t)r * ds + c] += __fdiv_rn(w, a);
+      objf = (double)w * log((double)a);
+      wsum = (double)w;
+    }
+  }
+  block_objf_store(objf, wsum, dred, objf_part);
+}
+
+// tot[0] += the partials' objective, tot[1] += their weight: one wave, each
+// lane its partials in order, then the cross-lane sum.
+__global__ __launch_bounds__(64) void objf_final_kernel(const double *__restrict__ objf_part,
+                                                        int nparts, double *__restrict__ tot) {
+  double objf = 0.0, wsum = 0.0;
+  for (int p = threadIdx.x; p < nparts; p += 64) {
+    objf += objf_part[2 * (size_t)p];
+    wsum += objf_part[2 * (size_t)p + 1];
+  }
+  objf = wave_sum(objf);
+  wsum = wave_sum(wsum);
+  if (threadIdx.x == 0) {
+    tot[0] += objf;
+    tot[1] += wsum;
+  }
+}
+
+// ---- Softmax + cross-entropy backward, fused -------------------------------------------
+// Labels sorted by row, row r's at [row_start[r], row_start[r + 1]).  S_r =
+// sum of the row's weights; D = -P S_r, + w at a label; the objective terms
+// w log P at the labels; the column sums of P.  P read once, D written once.
+template <int V, int TOT, bool STATS>
+__global__ __launch_bounds__(256) void softmax_xent_wave_kernel(
+    const float *__restrict__ P, int64_t ps, float *__restrict__ D, int64_t ds, int rows,
+    int cols, const int *__restrict__ row_start, const int *__restrict__ lab_col,
+    const float *__restrict__ lab_w, float *__restrict__ part, double *__restrict__ objf_part) {
+  __shared__ float red[STATS ? 3 * TOT * 64 : 1];
+  __shared__ double dred[4][2];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r0 = blockIdx.x * kSmRowsPerPart;
+  const int r1 = min(rows, r0 + kSmRowsPerPart);
+  float cs[STATS ? TOT : 1];
+  if constexpr (STATS) {
+#pragma unroll
+    for (int j = 0; j < TOT; j++) cs[j] = 0.0f;
+  }
+  double objf = 0.0, wsum = 0.0;
+  for (int r = r0 + w; r < r1; r += 4) {
+    const float *prow = P + (int64_t)r * ps;
+    float p[TOT];
+    load_row<V, TOT>(prow, cols, lane, 0.0f, p);
+    const int lb = row_start[r], le = row_start[r + 1];
+    float S = 0.0f;
+    for (int l = lb; l < le; l++) S += lab_w[l];
+#pragma unroll
+    for (int j = 0; j < TOT; j++) {
+      if constexpr (STATS) cs[j] += p[j];
+      p[j] = -p[j] * S;
+    }
+    for (int l = lb; l < le; l++) {
+      // the label's column is value jl of lane `owner`: jl is wave-uniform,
+      // so the search over the register file is scalar compares
+      const int c = __builtin_amdgcn_readfirstlane(lab_col[l]);
+      const float lw = lab_w[l];
+      const int q = c / V;
+      const int jl = (q >> 6) * V + (c % V);
+      const float add = (lane == (q & 63)) ? lw : 0.0f;
+#pragma unroll
+      for (int j = 0; j < TOT; j++)
+        if (j == jl) p[j] += add;
+    }
+    for (int l = lb + lane; l < le; l += 64) {
+      const int c = lab_col[l];
+      if (c >= 0 && c < cols) {
+        const float lw = lab_w[l];
+        objf += (double)lw * log((double)prow[c]);
+        wsum += (double)lw;
+      }
+    }
+    store_row<V, TOT>(D + (int64_t)r * ds, cols, lane, p);
+  }
+  if constexpr (STATS)
+    part_colsum_store<V, TOT>(cs, red, lane, w, part + (int64_t)blockIdx.x * cols, cols);
+  block_objf_store(objf, wsum, dred, objf_part);
+}
+
+// The wide-row form: a block per row; partial r is the row's objective.
+__global__ __launch_bounds__(256) void softmax_xent_block_kernel(
+    const float *__restrict__ P, int64_t ps, float *__restrict__ D, int64_t ds, int rows,
+    int cols, const int *__restrict__ row_start, const int *__restrict__ lab_col,
+    const float *__restrict__ lab_w, double *__restrict__ objf_part) {
+  __shared__ double dred[4][2];
+  const int r = blockIdx.x;
+  const float *p = P + (int64_t)r * ps;
+  float *d = D + (int64_t)r * ds;
+  const int lb = row_start[r], le = row_start[r + 1];
+  float S = 0.0f;
+  for (int l = lb; l < le; l++) S += lab_w[l];
+  for (int c = threadIdx.x; c < cols; c += 256) d[c] = -p[c] * S;
+  __syncthreads();  // the label elements are rewritten below by other threads
+  double objf = 0.0, wsum = 0.0;
+  for (int l = lb + (int)threadIdx.x; l < le; l += 256) {
+    const int c = lab_col[l];
+    if (c >= 0 && c < cols) {
+      const float lw = lab_w[l];
+      d[c] = -p[c] * S + lw;
+      objf += (double)lw * log((double)p[c]);
+      wsum += (double)lw;
+    }
+  }
+  block_objf_store(objf, wsum, dred, objf_part);
+}
+
+// ---- Dropout -----------------------------------------------------------------------------
+struct Philox4 { uint32_t x, y, z, w; };
+
+// Philox4x32-10 (Salmon et al., SC'11).
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
+                                                 uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{c0, c1, c2, c3};
+}
+
+struct DropoutArgs {
+  float dp, hl, low;   // proportion, high - low, low
+  int scale_hl, add_low;
+  uint32_t k0, k1, call_lo, call_hi;
+};
+
+// The reference's sequence on one uniform draw (nnet-component.cc:3613-3622):
+// Add(-dp), ApplyHeaviside, Scale(high - low) unless 1, Add(low) unless 0.
+__device__ __forceinline__ float dropout_mask(uint32_t x, const DropoutArgs &a) {
+  const float u = (float)(x >> 8) * 5.9604644775390625e-8f;  // 2^-24, exact
+  float h = (u - a.dp) > 0.0f ? 1.0f : 0.0f;
+  if (a.scale_hl) h *= a.hl;
+  if (a.add_low) h += a.low;
+  return h;
+}
+
+// A thread per (row, block of four columns): one Philox call, one 16-byte
+// (VEC4) or four 4-byte accesses each way.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void dropout_prop_kernel(const float *__restrict__ in,
+                                                           int64_t is, float *__restrict__ out,
+                                                           int64_t os, int cols, FastDiv div_ncb,
+                                                           int64_t total, DropoutArgs a) {
+  // high == low: every mask value is the same and no draw is needed
+  const bool flat = a.scale_hl && a.hl == 0.0f;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * 256) {
+    uint32_t row, cb;
+    div_ncb.divmod((uint32_t)e, row, cb);
+    float m[4];
+    if (flat) {
+      float h = 0.0f * a.hl;
+      if (a.add_low) h += a.low;
+      m[0] = m[1] = m[2] = m[3] = h;
+    } else {
+      const Philox4 x = philox4x32_10(cb, row, a.call_lo, a.call_hi, a.k0, a.k1);
+      m[0] = dropout_mask(x.x, a);
+      m[1] = dropout_mask(x.y, a);
+      m[2] = dropout_mask(x.z, a);
+      m[3] = dropout_mask(x.w, a);
+    }
+    const int c = (int)cb * 4;
+    const float *x = in + (int64_t)row * is + c;
+    float *y = out + (int64_t)row * os + c;
+    if (VEC4 && c + 4 <= cols) {
+      const float4 v = *reinterpret_cast<const float4 *>(x);
+      *reinterpret_cast<float4 *>(y) = make_float4(m[0] * v.x, m[1] * v.y, m[2] * v.z, m[3] * v.w);
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; s++)
+        if (c + s < cols) y[s] = m[s] * x[s];
+    }
+  }
+}
+
+// AddMatMatDivMat: in_value == 0 ? out_deriv : out_deriv * out_value / in_value
+// (the product first, then an IEEE divide).
+__device__ __forceinline__ float dropout_dx(float od, float ov, float iv) {
+  return iv == 0.0f ? od : __fdiv_rn(__fmul_rn(od, ov), iv);
+}
+
+__global__ __launch_bounds__(256) void dropout_backprop_kernel(
+    const float *__restrict__ iv, int64_t ivs, const float *__restrict__ ov, int64_t ovs,
+    const float *__restrict__ od, int64_t ods, float *__restrict__ id, int64_t ids, int rows,
+    int cols) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  for (int r = blockIdx.y; r < rows; r += gridDim.y)
+    id[(int64_t)r * ids + c] =
+        dropout_dx(od[(int64_t)r * ods + c], ov[(int64_t)r * ovs + c], iv[(int64_t)r * ivs + c]);
+}
+
+__global__ __launch_bounds__(256) void dropout_backprop4_kernel(
+    const float *__restrict__ iv, int64_t ivs, const float *__restrict__ ov, int64_t ovs,
+    const float *__restrict__ od, int64_t ods, float *__restrict__ id, int64_t ids, int rows,
+    int cols) {
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (c >= cols) return;
+  for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+    const float4 i = *reinterpret_cast<const float4 *>(iv + (int64_t)r * ivs + c);
+    const float4 o = *reinterpret_cast<const float4 *>(ov + (int64_t)r * ovs + c);
+    const float4 d = *reinterpret_cast<const float4 *>(od + (int64_t)r * ods + c);
+    *reinterpret_cast<float4 *>(id + (int64_t)r * ids + c) =
+        make_float4(dropout_dx(d.x, o.x, i.x), dropout_dx(d.y, o.y, i.y),
+                    dropout_dx(d.z, o.z, i.z), dropout_dx(d.w, o.w, i.w));
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------
+struct Operand {
+  const void *p;
+  int stride;
+};
+
+// Columns a lane takes at once: 4 (16-byte accesses) when every operand's
+// base and row stride allow, else 2, else 1.
+template <size_t N>
+int lane_width(const Operand (&ops)[N]) {
+  int v = 4;
+  for (const Operand &o : ops) {
+    while (v > 1 && ((uintptr_t)o.p % (4 * v) != 0 || o.stride % v != 0)) v >>= 1;
+  }
+  return v;
+}
+
+// Values a lane holds (the kernels are built for 4, 16 and 64).
+int lane_values(int cols) { return cols <= 256 ? 4 : cols <= 1024 ? 16 : 64; }
+
+template <typename F>
+void dispatch_row_kernel(int v, int tot, F f) {
+  auto with_v = [&](auto vc) {
+    if (tot == 4) f(vc, std::integral_constant<int, 4>{});
+    else if (tot == 16) f(vc, std::integral_constant<int, 16>{});
+    else f(vc, std::integral_constant<int, 64>{});
+  };
+  if (v == 4) with_v(std::integral_constant<int, 4>{});
+  else if (v == 2) with_v(std::integral_constant<int, 2>{});
+  else with_v(std::integral_constant<int, 1>{});
+}
+
+bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols == b.cols; }
+
+unsigned row_blocks(int rows) { return (unsigned)(rows < 65535 ? rows : 65535); }
+
+int wave_parts(int rows) { return (rows + kSmRowsPerPart - 1) / kSmRowsPerPart; }
+
+}  // namespace
+
+extern "C" {
+
+int kn_softmax_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                    kcnn_stream_t st) {
+  if (!same_shape(in_dim, out_dim) || in_dim.stride < in_dim.cols ||
+      out_dim.stride < out_dim.cols)
+    return (int)hipErrorInvalidValue;
+  const int rows = in_dim.rows, cols = in_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  hipStream_t s = kcnn::as_stream(st);
+  if (cols > kWaveRowMaxCols) {
+    hipLaunchKernelGGL(softmax_prop_block_kernel, dim3(row_blocks(rows)), dim3(256), 0, s, in,
+                       (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, rows, cols);
+    return kcnn::launch_status();
+  }
+  const Operand ops[] = {{in, in_dim.stride}, {out, out_dim.stride}};
+  dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+    hipLaunchKernelGGL((softmax_prop_wave_kernel<decltype(V)::value, decltype(TOT)::value>),
+                       dim3((rows + 3) / 4), dim3(256), 0, s, in, (int64_t)in_dim.stride, out,
+                       (int64_t)out_dim.stride, rows, cols);
+  });
+  return kcnn::launch_status();
+}
+
+size_t kn_softmax_stats_ws(MatrixDim dim) {
+  return (size_t)(wave_parts(dim.rows) > 0 ? wave_parts(dim.rows) : 1) *
+         (dim.cols > 0 ? dim.cols : 1) * sizeof(float);
+}
+
+}  // extern "C"
+
+namespace {
+// The column sums of P for the wide-row path (the wave kernels make their
+// parts themselves), then the ordered final pass either way.
+int finish_colsum(const float *P, MatrixDim p_dim, bool wide, double *value_sum, float *part,
+                  hipStream_t s) {
+  int nparts = wave_parts(p_dim.rows);
+  if (wide) {
+    nparts = (p_dim.rows + kColRowsPerPart - 1) / kColRowsPerPart;
+    hipLaunchKernelGGL(colsum_part_kernel, dim3((p_dim.cols + 255) / 256, nparts), dim3(256), 0,
+                       s, P, (int64_t)p_dim.stride, p_dim.rows, p_dim.cols, part);
+    const int rc = kcnn::launch_status();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(colsum_final_kernel, dim3((p_dim.cols + 63) / 64), dim3(64 * kFinalWaves),
+                     0, s, part, nparts, p_dim.cols, value_sum);
+  return kcnn::launch_status();
+}
+}  // namespace
+
+extern "C" {
+
+int kn_softmax_backprop(const float *out_value, MatrixDim ov_dim, const float *out_deriv,
+                        MatrixDim od_dim, float *in_deriv, MatrixDim id_dim, double *value_sum,
+                        void *ws, kcnn_stream_t st) {
+  if (!same_shape(ov_dim, od_dim) || !same_shape(id_dim, od_dim) ||
+      ov_dim.stride < ov_dim.cols || od_dim.stride < od_dim.cols || id_dim.stride < id_dim.cols)
+    return (int)hipErrorInvalidValue;
+  const int rows = od_dim.rows, cols = od_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  const bool stats = value_sum != nullptr;
+  if (stats && ws == nullptr) return (int)hipErrorInvalidValue;
+  float *part = static_cast<float *>(ws);
+  hipStream_t s = kcnn::as_stream(st);
+  const bool wide = cols > kWaveRowMaxCols;
+  if (wide) {
+    hipLaunchKernelGGL(softmax_backprop_block_kernel, dim3(row_blocks(rows)), dim3(256), 0, s,
+                       out_value, (int64_t)ov_dim.stride, out_deriv, (int64_t)od_dim.stride,
+                       in_deriv, (int64_t)id_dim.stride, rows, cols);
+  } else {
+    const Operand ops[] = {
+        {out_value, ov_dim.stride}, {out_deriv, od_dim.stride}, {in_deriv, id_dim.stride}};
+    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+      constexpr int v = decltype(V)::value, tot = decltype(TOT)::value;
+      if (stats)
+        hipLaunchKernelGGL((softmax_backprop_wave_kernel<v, tot, true>), dim3(wave_parts(rows)),
+                           dim3(256), 0, s, out_value, (int64_t)ov_dim.stride, out_deriv,
+                           (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols,
+                           part);
+      else
+        hipLaunchKernelGGL((softmax_backprop_wave_kernel<v, tot, false>), dim3(wave_parts(rows)),
+                           dim3(256), 0, s, out_value, (int64_t)ov_dim.stride, out_deriv,
+                           (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols,
+                           part);
+    });
+  }
+  const int rc = kcnn::launch_status();
+  if (rc || !stats) return rc;
+  return finish_colsum(out_value, ov_dim, wide, value_sum, part, s);
+}
+
+size_t kn_objf_ws(int num_blocks) {
+  return (size_t)2 * (num_blocks > 0 ? num_blocks : 1) * sizeof(double);
+}
+
+int kn_comp_objf_blocks(int num) { return (num + 255) / 256; }
+
+int kn_comp_objf_and_deriv(const int *el_row, const int *el_col, const float *el_w, int num,
+                           const float *probs, MatrixDim p_dim, float *deriv, MatrixDim d_dim,
+                           double *tot, void *ws, kcnn_stream_t st) {
+  if (!same_shape(p_dim, d_dim) || num < 0 || tot == nullptr)
+    return (int)hipErrorInvalidValue;
+  if (num == 0) return 0;
+  if (ws == nullptr) return (int)hipErrorInvalidValue;
+  hipStream_t s = kcnn::as_stream(st);
+  const int nb = kn_comp_objf_blocks(num);
+  double *objf_part = static_cast<double *>(ws);
+  hipLaunchKernelGGL(comp_objf_kernel, dim3(nb), dim3(256), 0, s, el_row, el_col, el_w, num,
+                     probs, (int64_t)p_dim.stride, deriv, (int64_t)d_dim.stride, p_dim.rows,
+                     p_dim.cols, objf_part);
+  const int rc = kcnn::launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(objf_final_kernel, dim3(1), dim3(64), 0, s, objf_part, nb, tot);
+  return kcnn::launch_status();
+}
+
+int kn_softmax_xent_blocks(MatrixDim dim) {
+  return dim.cols > kWaveRowMaxCols ? dim.rows : wave_parts(dim.rows);
+}
+
+int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in_deriv,
+                             MatrixDim id_dim, const int *row_start, const int *lab_col,
+                             const float *lab_w, double *value_sum, void *stats_ws, double *tot,
+                             void *objf_ws, kcnn_stream_t st) {
+  if (!same_shape(ov_dim, id_dim) || ov_dim.stride < ov_dim.cols ||
+      id_dim.stride < id_dim.cols || tot == nullptr || objf_ws == nullptr ||
+      row_start == nullptr)
+    return (int)hipErrorInvalidValue;
+  const int rows = ov_dim.rows, cols = ov_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  const bool stats = value_sum != nullptr;
+  if (stats && stats_ws == nullptr) return (int)hipErrorInvalidValue;
+  float *part = static_cast<float *>(stats_ws);
+  double *objf_part = static_cast<double *>(objf_ws);
+  hipStream_t s = kcnn::as_stream(st);
+  const bool wide = cols > kWaveRowMaxCols;
+  const int nb = kn_softmax_xent_blocks(ov_dim);
+  if (wide) {
+    hipLaunchKernelGGL(softmax_xent_block_kernel, dim3(nb), dim3(256), 0, s, out_value,
+                       (int64_t)ov_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols,
+                       row_start, lab_col, lab_w, objf_part);
+  } else {
+    const Operand ops[] = {{out_value, ov_dim.stride}, {in_deriv, id_dim.stride}};
+    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+      constexpr int v = decltype(V)::value, tot_v = decltype(TOT)::value;
+      if (stats)
+        hipLaunchKernelGGL((softmax_xent_wave_kernel<v, tot_v, true>), dim3(nb), dim3(256), 0, s,
+                           out_value, (int64_t)ov_dim.stride, in_deriv, (int64_t)id_dim.stride,
+                           rows, cols, row_start, lab_col, lab_w, part, objf_part);
+      else
+        hipLaunchKernelGGL((softmax_xent_wave_kernel<v, tot_v, false>), dim3(nb), dim3(256), 0, s,
+                           out_value, (int64_t)ov_dim.stride, in_deriv, (int64_t)id_dim.stride,
+                           rows, cols, row_start, lab_col, lab_w, part, objf_part);
+    });
+  }
+  int rc = kcnn::launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(objf_final_kernel, dim3(1), dim3(64), 0, s, objf_part, nb, tot);
+  rc = kcnn::launch_status();
+  if (rc || !stats) return rc;
+  return finish_colsum(out_value, ov_dim, wide, value_sum, part, s);
+}
+
+int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                    float dropout_proportion, float high_minus_low, float low, uint64_t seed,
+                    uint64_t call, kcnn_stream_t st) {
+  if (!same_shape(in_dim, out_dim) || in_dim.stride < in_dim.cols ||
+      out_dim.stride < out_dim.cols)
+    return (int)hipErrorInvalidValue;
+  const int rows = in_dim.rows, cols = in_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  const int ncb = (cols + 3) / 4;
+  const int64_t total = (int64_t)rows * ncb;
+  if (total >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+  DropoutArgs a;
+  a.dp = dropout_proportion;
+  a.hl = high_minus_low;
+  a.low = low;
+  a.scale_hl = high_minus_low != 1.0f;
+  a.add_low = low != 0.0f;
+  a.k0 = (uint32_t)seed;
+  a.k1 = (uint32_t)(seed >> 32);
+  a.call_lo = (uint32_t)call;
+  a.call_hi = (uint32_t)(call >> 32);
+  const bool vec4 = in_dim.stride % 4 == 0 && out_dim.stride % 4 == 0 &&
+                    (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
+  hipStream_t s = kcnn::as_stream(st);
+  if (vec4)
+    hipLaunchKernelGGL(dropout_prop_kernel<true>, dim3(kcnn::grid_for(total)), dim3(256), 0, s,
+                       in, (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, cols,
+                       FastDiv((uint32_t)ncb), total, a);
+  else
+    hipLaunchKernelGGL(dropout_prop_kernel<false>, dim3(kcnn::grid_for(total)), dim3(256), 0, s,
+                       in, (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, cols,
+                       FastDiv((uint32_t)ncb), total, a);
+  return kcnn::launch_status();
+}
+
+int kn_dropout_backprop(const float *in_value, MatrixDim iv_dim, const float *out_value,
+                        MatrixDim ov_dim, const float *out_deriv, MatrixDim od_dim,
+                        float *in_deriv, MatrixDim id_dim, kcnn_stream_t st) {
+  if (!same_shape(iv_dim, od_dim) || !same_shape(ov_dim, od_dim) || !same_shape(id_dim, od_dim))
+    return (int)hipErrorInvalidValue;
+  const int rows = od_dim.rows, cols = od_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  const bool vec4 = cols % 4 == 0 && iv_dim.stride % 4 == 0 && ov_dim.stride % 4 == 0 &&
+                    od_dim.stride % 4 == 0 && id_dim.stride % 4 == 0 &&
+                    (uintptr_t)in_value % 16 == 0 && (uintptr_t)out_value % 16 == 0 &&
+                    (uintptr_t)out_deriv % 16 == 0 && (uintptr_t)in_deriv % 16 == 0;
+  const int cpb = vec4 ? 1024 : 256;
+  const unsigned cb = (unsigned)((cols + cpb - 1) / cpb);
+  unsigned rb = (unsigned)rows;
+  const unsigned cap = 8192u / cb + 1u;
+  if (rb > cap) rb = cap;
+  if (rb > 65535u) rb = 65535u;
+  hipStream_t s = kcnn::as_stream(st);
+  if (vec4)
+    hipLaunchKernelGGL(dropout_backprop4_kernel, dim3(cb, rb), dim3(256), 0, s, in_value,
+                       (int64_t)iv_dim.stride, out_value, (int64_t)ov_dim.stride, out_deriv,
+                       (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols);
+  else
+    hipLaunchKernelGGL(dropout_backprop_kernel, dim3(cb, rb), dim3(256), 0, s, in_value,
+                       (int64_t)iv_dim.stride, out_value, (int64_t)ov_dim.stride, out_deriv,
+                       (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols);
+  return kcnn::launch_status();
+}
+
+}  // extern "C"
