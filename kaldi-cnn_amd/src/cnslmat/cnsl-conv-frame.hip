@@ -372,7 +372,7 @@ template <int KS, int FT, int PC, int AR, bool RP = false>
 __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
     ConvGeom g, const float *__restrict__ X, int xs,
     const float *__restrict__ K, int ks, const float *__restrict__ bias,
-    float *__restrict__ out, int os, int vec_ok, int dbg,
+    float *__restrict__ out, int os, int vec_ok, int clk,
     float *__restrict__ pool, int ps, unsigned char *__restrict__ mask, int ms,
     PoolWin pw3, RpStats rps) {
   constexpr bool X6 = AR == 1, F16 = AR == 2, SPL = AR != 0;
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
   // are read at one offset + e, without the per-tap table reads
   bool run8 = false;
   if constexpr (SPL) {
-    run8 = !(dbg & 64);
+    run8 = true;
     for (int k = 0; k + 1 < g.Kdim && run8; k++) {
       if ((k + 1) % 8 == 0) continue;
       uint32_t c0, r0, x0, y0, c1, r1, x1, y1;
@@ -488,10 +488,10 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
       run8 = o1 == o0 + 1;
     }
   }
-#ifdef KCNN_PHASE_TIMING  // per-phase s_memtime totals of block 0 (dbg & 16)
+#ifdef KCNN_PHASE_TIMING  // per-phase s_memtime totals of block 0 (clk != 0)
   long long tm[6] = {0, 0, 0, 0, 0, 0};
   long long tprev = clock64();
-#define KCNN_TMARK(i) if (dbg & 16) { const long long tn = clock64(); tm[i] += tn - tprev; tprev = tn; }
+#define KCNN_TMARK(i) if (clk) { const long long tn = clock64(); tm[i] += tn - tprev; tprev = tn; }
 #else
 #define KCNN_TMARK(i)
 #endif
@@ -584,9 +584,6 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
           for (int e = 0; e < 8; e++) {
             v[s][e] = k0 + e < g.Kdim ? v[s][e] : 0.0f;
             m = fmaxf(m, fabsf(v[s][e]));
-#ifdef KCNN_EXPERIMENTS  // A/B: dbg & 2048 drops the position columns' min
-            if (!(dbg & 2048))
-#endif
             mn = min(mn, (__float_as_uint(v[s][e]) << 1) - 2u);
           }
         }
@@ -594,21 +591,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
         // v_permlane32_swap here, one accumulator register of 16 lanes of a
         // wave's last item came out wrong in about one call in four of a
         // 601-frame forward, G = 96, Kdim 12; experiments/diag_det2.py.)
-#ifdef KCNN_FWD_PERMLANE  // experiment: the swap variant of the hazard study
-        {
-          auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m),
-                                                     false, false);
-#ifdef KCNN_FWD_PERMLANE_NOP  // two wait states between the swap and its readers
-          uint32_t s0 = sw[0], s1 = sw[1];
-          asm volatile("s_nop 1" : "+v"(s0), "+v"(s1));
-          sw[0] = s0;
-          sw[1] = s1;
-#endif
-          m = fmaxf(m, __uint_as_float(h_f ? sw[1] : sw[0]));
-        }
-#else
         m = fmaxf(m, __shfl_xor(m, 32));
-#endif
         mn = min(mn, (uint32_t)__shfl_xor((int)mn, 32));
         const uint32_t mb = __float_as_uint(m);
         // a spread position column (f16-split.h): the tile's items are checked
@@ -773,9 +756,6 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
                                      __HIP_MEMORY_SCOPE_WORKGROUP);
               rowrun = max(rowrun, a);
               const uint32_t u = a - 1u;  // wraps for 0: never the min
-#ifdef KCNN_EXPERIMENTS  // A/B: dbg & 4096 drops the row min
-              if (!(dbg & 4096))
-#endif
               rowmn = min(rowmn, u);
             }
             // (pinned per item: left free, the scheduler spreads the items'
@@ -799,14 +779,8 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
             const int U = (gb * 32 + (r0 & 3) + 8 * (r0 >> 2)) / PC;
             const unsigned vv =
                 g.G % 32 == 0 || U + h_f * (4 / PC) < g.G / PC ? vo : 0x3ffffff0u;
-#ifdef KCNN_EXPERIMENTS  // store A/B: dbg & 256 drops the pooled values, & 512 the masks
-            if (!(dbg & 256))
-#endif
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mx[j]), prs, vv * 4u,
                                                   (unsigned)(U * Pq) * 4u, 0);
-#ifdef KCNN_EXPERIMENTS
-            if (!(dbg & 512))
-#endif
             __builtin_amdgcn_raw_buffer_store_b8((unsigned char)msk[j], mrs, vv,
                                                  (unsigned)(U * Pq), 0);
           }
@@ -867,9 +841,6 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
             }
           }
         };
-#ifdef KCNN_EXPERIMENTS  // A/B: dbg & 8192 never takes the checked sequence
-        if (dbg & 8192) tsp = 0;
-#endif
         if (F16 && (wspread || tsp != 0)) sequence(std::true_type{});  // uniform, rare
         else sequence(std::false_type{});
         if constexpr (F16) fp32_items();  // the items a spread check rejected (rare)
@@ -1070,7 +1041,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_regs_kernel(
     }
   }
 #ifdef KCNN_PHASE_TIMING
-  if ((dbg & 16) && blockIdx.x == 0 && lane == 0)
+  if (clk && blockIdx.x == 0 && lane == 0)
     printf("fwd wave %d: xload %lld gather %lld mfma %lld bar1 %lld store %lld bar2 %lld\n",
            wave, tm[0], tm[1], tm[2], tm[3], tm[4], tm[5]);
 #endif
@@ -1344,7 +1315,7 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void conv_bwd_dma_kernel(
     ConvGeom g, const float *__restrict__ X, int xs,
     const float *__restrict__ dY, int dys, const float *__restrict__ K, int ks,
     float *__restrict__ dX, int dxs, float *__restrict__ ws_part, int ZZ,
-    unsigned long long wg0, unsigned long long wg1, int zsep, int dx_acc, int dbg,
+    unsigned long long wg0, unsigned long long wg1, int zsep, int dx_acc, int clk,
     const unsigned char *__restrict__ pmask, int pms) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int P = g.P;
@@ -1521,10 +1492,10 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void conv_bwd_dma_kernel(
   // before that frame's last slab barrier (Z is rewritten after it)
   const int npiece = NCH > 1 ? NCH - 1 : 1;
   int cur = 0, nprev = -1;
-#ifdef KCNN_PHASE_TIMING  // per-phase s_memtime totals of block 0 (dbg & 16)
+#ifdef KCNN_PHASE_TIMING  // per-phase s_memtime totals of block 0 (clk != 0)
   long long tm[7] = {0, 0, 0, 0, 0, 0, 0};
   long long tprev = clock64();
-#define KCNN_TMARK(i) if (dbg & 16) { const long long tn = clock64(); tm[i] += tn - tprev; tprev = tn; }
+#define KCNN_TMARK(i) if (clk) { const long long tn = clock64(); tm[i] += tn - tprev; tprev = tn; }
 #else
 #define KCNN_TMARK(i)
 #endif
@@ -1695,7 +1666,7 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void conv_bwd_dma_kernel(
   }
   KCNN_TMARK(5)
 #ifdef KCNN_PHASE_TIMING
-  if ((dbg & 16) && blockIdx.x == 0 && lane == 0)
+  if (clk && blockIdx.x == 0 && lane == 0)
     printf("bwd3 wave %d: barrier %lld dma %lld dgrad %lld wgrad %lld tail %lld end %lld other %lld\n",
            wave, tm[0], tm[1], tm[2], tm[3], tm[4], tm[5], tm[6]);
 #endif
@@ -1988,11 +1959,7 @@ unsigned frame_grid(const ConvGeom &g, int blocks_per_cu) {
 // The fused conv + pool forward's Y stores (fusion mode 2, Y kept for later)
 // as streaming stores (vec_ok bit 1): c2 213 -> 206 us.  Not for the unfused
 // conv, whose Y the pool reads right after (155 -> 181 us there).
-// KCNN_CONV_Y_NT=0 plain stores
-static int y_nt() {
-  static const int v = KCNN_KNOB("KCNN_CONV_Y_NT", 1) ? 2 : 0;
-  return v;
-}
+static constexpr int kYNt = 2;
 
 int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
                         const float *K, int ks, const float *bias, float *out,
@@ -2010,24 +1977,21 @@ int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
     return 0;
   }
   const int Kpad = (g.Kdim + 1) & ~1;
-  static const int variant = KCNN_KNOB("KCNN_FWD_VARIANT", 2);
-  if (variant == 2 && g.Kdim <= 32 && g.G <= 128 && g.P <= 4 * 32 * 3 &&
+  if (g.Kdim <= 32 && g.G <= 128 && g.P <= 4 * 32 * 3 &&
       g.C * g.HW <= 256 * 8) {
     const size_t lds = (size_t)((32 * g.P + 3) & ~3) * 4 + 160 * 4 + 32 * 8 +
                        (size_t)g.C * g.HW * 4 + 8 * 4;
     if (lds <= (size_t)kFrameLdsMax) {
       const int vec_ok = ((uintptr_t)out % 16 == 0) && (os % 4 == 0);
       const int ksn = (g.Kdim + 1) / 2;
-      static const int bpc_env = KCNN_KNOB("KCNN_FWD_BPC", 0);
       const int ar = fwd_arith(g, family(kFamFwdX6));
-      const unsigned grid = frame_grid(
-          g, bpc_env > 0 ? bpc_env : ar ? 2 : fwd_regs_blocks_per_cu(lds));
+      const unsigned grid = frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(lds));
 #define KCNN_FWD_REGS_T(KS_, AR_)                                                       \
   hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, 0, AR_>), dim3(grid), dim3(256), lds, \
-                     st, g, X, xs, K, ks, bias, out, os, vec_ok, dbg, nullptr, 0, nullptr, \
+                     st, g, X, xs, K, ks, bias, out, os, vec_ok, clk, nullptr, 0, nullptr, \
                      0, PoolWin{}, RpStats{})
 #define KCNN_FWD_REGS(KS_) KCNN_FWD_REGS_T(KS_, 0)
-      static const int dbg = KCNN_KNOB("KCNN_FWD_DEBUG", 0);
+      const int clk = phase_timing();
       if (ar == 2 && g.Kdim <= 16) KCNN_FWD_REGS_T(1, 2);
       else if (ar == 2) KCNN_FWD_REGS_T(2, 2);
       else if (ar == 1 && g.Kdim < 16) KCNN_FWD_REGS_T(1, 1);
@@ -2041,7 +2005,7 @@ int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
       return (int)hipGetLastError();
     }
   }
-  if (variant >= 1) {
+  {
     // slab-streamed: T [32][P] staged in LDS, written as whole 16-B lines
     const int Gp = (g.G + 31) & ~31;
     const size_t lds = (size_t)align16(Kpad * 8) + (size_t)((32 * g.P + 3) & ~3) * 4 +
@@ -2118,13 +2082,11 @@ int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
   const size_t lds = (size_t)((32 * g.P + 3) & ~3) * 4 + 160 * 4 + 32 * 8 +
                      (size_t)g.C * g.HW * 4 + 8 * 4;
   if (lds > (size_t)kFrameLdsMax) return -1;
-  const int vec_ok = ((uintptr_t)out % 16 == 0) && (os % 4 == 0) ? 1 | y_nt() : 0;
+  const int vec_ok = ((uintptr_t)out % 16 == 0) && (os % 4 == 0) ? 1 | kYNt : 0;
   const int ksn = (g.Kdim + 1) / 2;
-  static const int grid_env = KCNN_KNOB("KCNN_FWD_GRID", 0);
   const int ar = fwd_arith(g, family(kFamFwdX6));
-  const unsigned grid = grid_env > 0 ? (unsigned)std::min<int64_t>(grid_env, g.R)
-                                     : frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(lds));
-  static const int dbg = KCNN_KNOB("KCNN_FWD_DEBUG", 0);
+  const unsigned grid = frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(lds));
+  const int clk = phase_timing();
   // the register-pooled-only form: pooled output only, pc 4, G = 128 and
   // exactly 12 position tiles, so each of the 4 waves has all 3 (the form
   // runs every item unfiltered: with 9-11 tiles a wave's third tile would
@@ -2150,10 +2112,10 @@ int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
     if (rp && PC_ == 4 && AR_ == 2)                                                          \
       hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, PC_, AR_, PC_ == 4 && AR_ == 2>),     \
                          dim3(grid), dim3(256), lds_rp, st, g, X, xs, K, ks, bias, out, os,  \
-                         vec_ok, dbg, pool, ps, mask, ms, pw3, rps);                         \
+                         vec_ok, clk, pool, ps, mask, ms, pw3, rps);                         \
     else                                                                                     \
       hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, PC_, AR_>), dim3(grid), dim3(256), lds, \
-                         st, g, X, xs, K, ks, bias, out, os, vec_ok, dbg, pool, ps, mask, ms, pw3, \
+                         st, g, X, xs, K, ks, bias, out, os, vec_ok, clk, pool, ps, mask, ms, pw3, \
                          RpStats{});                                                         \
   } while (0)
 #define KCNN_FWD_POOL(KS_, PC_) KCNN_FWD_POOL_T(KS_, PC_, 0)
@@ -2168,8 +2130,7 @@ int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
     else if (ksn <= 12) KCNN_FWD_POOL(12, PC_);   \
     else KCNN_FWD_POOL(16, PC_);                  \
   } while (0)
-  static const int win_ct = KCNN_KNOB("KCNN_FWD_WIN_CT", 1);  // 0: the runtime window
-  if (win3 && win_ct && ph == 3 && pw == 1 && pc == 4) KCNN_FWD_POOL_KS(-3);
+  if (win3 && ph == 3 && pw == 1 && pc == 4) KCNN_FWD_POOL_KS(-3);
   else if (win3) KCNN_FWD_POOL_KS(-1);
   else if (pc == 2) KCNN_FWD_POOL_KS(2);
   else if (pc == 4) KCNN_FWD_POOL_KS(4);
@@ -2310,14 +2271,11 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
                            void *ws, size_t ws_bytes, int dx_acc, hipStream_t st,
                            const unsigned char *pmask, int pms, int pc, int ph,
                            const ConvUpdateEpi *ue) {
-  static const int enabled = KCNN_KNOB("KCNN_FUSED_BWD", 1);
-  static const int variant = KCNN_KNOB("KCNN_BWD_VARIANT", 3);  // 1: register-staged
-  static const int bdbg = KCNN_KNOB("KCNN_BWD_DEBUG", 0);
-  if (!enabled || (dX == nullptr && gW == nullptr)) return -1;
+  if (dX == nullptr && gW == nullptr) return -1;
   if (g.Kdim > 31 || g.G % 32 != 0 || g.G > 128 || g.G == 0) return -1;
   // the bf16x6 kernel (cnsl-conv-x6.hip) where the shape allows; KCNN_BWD_X6=0
   // keeps the fp32-MFMA kernels below
-  if (family(kFamBwdX6) && variant == 3 && kcnn_conv_bwd_x6_eligible(g, dX != nullptr, pc, ph)) {
+  if (family(kFamBwdX6) && kcnn_conv_bwd_x6_eligible(g, dX != nullptr, pc, ph)) {
     const int S = (int)frame_grid(g, 1);
     const int E = (g.Kdim + 1) * g.G;
     float *part = static_cast<float *>(ws);
@@ -2344,8 +2302,7 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
       rc = kcnn_conv_bwd_x6(gc, X ? X + (int64_t)r0 * xs : X, xs, dY + (int64_t)r0 * dys, dys,
                             K, ks, dX ? dX + (int64_t)r0 * dxs : dX, dxs, gW ? part : nullptr,
                             nch > 1 ? (int)frame_grid(gc, 1) : S, dx_acc, st,
-                            pmask ? pmask + (int64_t)r0 * pms : pmask, pms, pc, ph,
-                            bdbg | (c > 0 ? 1 << 30 : 0));
+                            pmask ? pmask + (int64_t)r0 * pms : pmask, pms, pc, ph, c > 0);
     }
     if (rc || gW == nullptr) return rc;
     hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, part, S,
@@ -2357,7 +2314,7 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
     return -1;
   if (pc == 0 && ((uintptr_t)dY % 16 != 0 || dys % 4 != 0)) return -1;  // 16-B slab loads
   // pc = 2 would stage 16 rows per slab: past the register budget
-  if (pc != 0 && (!(pc == 4 || pc == 8) || variant != 3)) return -1;
+  if (pc != 0 && !(pc == 4 || pc == 8)) return -1;
   const int S = (int)frame_grid(g, 1);
   const int E = (g.Kdim + 1) * g.G;
   const int ZZ = g.Kdim | 1;
@@ -2387,15 +2344,13 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
   size_t lds3 = bwd_dma_lds(g);
   // a separate Z buffer when it fits (deferred col2im, see the kernel)
   const size_t zbytes = (size_t)g.P * ZZ * 4;
-  const int zsep = dX != nullptr && lds3 + zbytes <= (size_t)kBwdLdsMax &&
-                   !(bdbg & 32);
+  const int zsep = dX != nullptr && lds3 + zbytes <= (size_t)kBwdLdsMax;
   if (zsep) lds3 += zbytes;
-  if (variant == 3 && g.C * g.HW <= BWD_THREADS * BWD_MAXX &&
-      lds3 <= (size_t)kBwdLdsMax) {
+  if (g.C * g.HW <= BWD_THREADS * BWD_MAXX && lds3 <= (size_t)kBwdLdsMax) {
 #define KCNN_BWD3P(NCH, DXB, WGB, PCM)                                                 \
   hipLaunchKernelGGL((conv_bwd_dma_kernel<NCH, DXB, WGB, PCM>), dim3(S), dim3(BWD_THREADS), \
                      lds3, st, g, X, xs, dY, dys, K, ks, dX, dxs, part, ZZ, wg[0], wg[1], zsep, \
-                     dx_acc, bdbg, pmask, pms)
+                     dx_acc, phase_timing(), pmask, pms)
 #define KCNN_BWD3(NCH, DXB, WGB)                  \
   do {                                            \
     if (pc == 4) KCNN_BWD3P(NCH, DXB, WGB, 4);    \
@@ -2418,7 +2373,8 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
 #undef KCNN_BWD3
 #undef KCNN_BWD3P
   } else {
-    // register-staged variant: needs the gradient outputs, writes dX
+    // register-staged kernel (the DMA kernel's limits fail): needs the
+    // gradient outputs, writes dX
     if (gW == nullptr || dx_acc || pc) return -1;
     const int SP = bwd_sp(g);
     const size_t lds = bwd_lds(g, SP);
@@ -2471,8 +2427,6 @@ int kcnn_conv_bwd_frame(const ConvGeom &g, const float *X, int xs,
     return rc;
   }
   if (g.G % 32 != 0 || (int64_t)g.G * g.P * 4 % 16 != 0) return -1;
-  static const int variant = KCNN_KNOB("KCNN_BWD_VARIANT", 3);
-  if (variant != 3 && dX != nullptr) return -1;  // chunking needs dX accumulation
   for (int g0 = 0; g0 < g.G; g0 += 128) {
     ConvGeom gc = g;
     gc.G = g.G - g0 < 128 ? g.G - g0 : 128;

@@ -28,7 +28,6 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(256) void conv_w_presplit_kernel(const float *__res
 }
 constexpr int kAuxBytes = 384 * 8;  // F16: scale exponents and weights of a tile's groups
 
-template <int BG, bool PADDED, bool STG, bool TAB, int POOL, bool F16>
+template <int BG, bool PADDED, bool TAB, int POOL, bool F16>
 __global__ __launch_bounds__(NT, 1) void conv_igemm_x6_kernel(
     ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ Kw, int ks,
     const float *__restrict__ bias, float *__restrict__ out, int os, int relu, PoolOut po,
@@ -446,16 +445,11 @@ __global__ __launch_bounds__(NT, 1) void conv_igemm_x6_kernel(
 #pragma unroll
       for (int j = 0; j < 2; j++) acc[i][j] = x6::mfma6(a[i], bb[j], acc[i][j]);
   };
-  // STG: waves 4-7 split the next step's operands between their two MFMA
-  // halves, waves 0-3 after both, so the two waves of a SIMD (w, w + 4)
-  // alternate their vector and matrix phases instead of running them at once
-  const bool late = !STG || wave < 4;
   for (int t = 0; t < T; t++) {
     const char *buf = lds + (t & 1) * BUF;
     half_step(buf, 0);
-    if (!late && t + 1 < T) store(lds + ((t + 1) & 1) * BUF);
     half_step(buf, 1);
-    if (late && t + 1 < T) store(lds + ((t + 1) & 1) * BUF);
+    if (t + 1 < T) store(lds + ((t + 1) & 1) * BUF);
     if (t + 2 < T) load(t + 2);
     __syncthreads();
   }
@@ -770,7 +764,7 @@ __global__ __launch_bounds__(256) void conv_igemm_efix_kernel(
 // k-tile-0 blocks also sum dY for the bias gradient (fixed order).  Partials
 // go to ws[split][g*Kdim + k] (then the G bias entries), reduced in a fixed
 // order by kcnn_reduce_splits_wgrad: deterministic.
-template <bool PADDED, bool STG>
+template <bool PADDED>
 __global__ __launch_bounds__(NT, 1) void conv_wgrad_x6_kernel(
     ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ dY, int dys,
     float *__restrict__ ws, int fps, int ktiles, int nblocks) {
@@ -904,13 +898,11 @@ __global__ __launch_bounds__(NT, 1) void conv_wgrad_x6_kernel(
 #pragma unroll
       for (int j = 0; j < 2; j++) acc[i][j] = x6::mfma6(a[i], bb[j], acc[i][j]);
   };
-  const bool late = !STG || wave < 4;  // as in conv_igemm_x6_kernel
   for (int t = 0; t < nsteps; t++) {
     const char *buf = lds + (t & 1) * BUF;
     half_step(buf, 0);
-    if (!late && t + 1 < nsteps) store(lds + ((t + 1) & 1) * BUF);
     half_step(buf, 1);
-    if (late && t + 1 < nsteps) store(lds + ((t + 1) & 1) * BUF);
+    if (t + 1 < nsteps) store(lds + ((t + 1) & 1) * BUF);
     if (t + 2 < nsteps) load(t + 2);
     __syncthreads();
   }
@@ -1379,36 +1371,26 @@ __global__ __launch_bounds__(256) void conv_wgrad_efix_kernel(
   }
 }
 
-// KCNN_CONV_X6_STAGGER=1: the wave-pair stagger (STG).  It gained 4 % on
-// c5 while the split subtractions were packed into v_pk_add_f32; built
-// without SLP vectorization (Makefile) the kernels measure the same or
-// 0.6 % slower with it, so it is off by default.
-int stagger() {
-  static const int v = KCNN_KNOB("KCNN_CONV_X6_STAGGER", 0);
-  return v;
-}
-
 constexpr int kLdsMax = 160 * 1024;
 constexpr int img_bytes(bool f16) { return 2 * (f16 ? 2 : 3) * 384 * ROWB; }  // double-buffered planes
 
 // LDS of the tap table for Kdim (0: it does not fit beside the images)
 int tab_bytes(const ConvGeom &g, bool padded) {
-  static const int use = KCNN_KNOB("KCNN_IGX6_TAB", 1);
   const int KT = (g.Kdim + BK - 1) / BK * BK;
   const int b = KT * 4 + (padded ? KT : 0);
-  return use && img_bytes(false) + b <= kLdsMax ? b : 0;
+  return img_bytes(false) + b <= kLdsMax ? b : 0;
 }
 
-template <int BG, bool PADDED, bool STG, bool TAB, int POOL, bool F16>
+template <int BG, bool PADDED, bool TAB, int POOL, bool F16>
 void launch_t(const ConvGeom &g, unsigned blocks, const float *X, int xs, const float *K,
               int ks, const float *bias, float *out, int os, int relu, hipStream_t st,
               PoolOut po, F16Aux fx) {
   const int lds = img_bytes(F16) + (TAB ? tab_bytes(g, PADDED) : 0) + (F16 ? kAuxBytes : 0);
   static bool attr = hipFuncSetAttribute(
-      reinterpret_cast<const void *>(&conv_igemm_x6_kernel<BG, PADDED, STG, TAB, POOL, F16>),
+      reinterpret_cast<const void *>(&conv_igemm_x6_kernel<BG, PADDED, TAB, POOL, F16>),
       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) == hipSuccess;
   (void)attr;
-  hipLaunchKernelGGL((conv_igemm_x6_kernel<BG, PADDED, STG, TAB, POOL, F16>), dim3(blocks),
+  hipLaunchKernelGGL((conv_igemm_x6_kernel<BG, PADDED, TAB, POOL, F16>), dim3(blocks),
                      dim3(NT), lds, st, g, X, xs, K, ks, bias, out, os, relu, po, fx);
 }
 // f16x3 implicit-GEMM calls since the last reset (kcnn_conv_fix_counts)
@@ -1419,12 +1401,11 @@ void launch_pair(const ConvGeom &g, unsigned blocks, const float *X, int xs, con
                  int ks, const float *bias, float *out, int os, int relu, hipStream_t st,
                  PoolOut po, F16Aux fx) {
   if (!fx.list) {
-    launch_t<BG, PADDED, false, TAB, POOL, false>(g, blocks, X, xs, K, ks, bias, out, os, relu,
-                                                  st, po, fx);
+    launch_t<BG, PADDED, TAB, POOL, false>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, po,
+                                           fx);
     return;
   }
-  launch_t<BG, PADDED, false, TAB, POOL, true>(g, blocks, X, xs, K, ks, bias, out, os, relu,
-                                               st, po, fx);
+  launch_t<BG, PADDED, TAB, POOL, true>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, po, fx);
   g_igemm_f16_calls.fetch_add(1, std::memory_order_relaxed);
   hipLaunchKernelGGL((conv_igemm_fixup_kernel<BG, POOL>), dim3(std::min(blocks, 256u)),
                      dim3(256), 0, st, g, X, xs, K, ks, bias, out, os, relu, po,
@@ -1433,7 +1414,7 @@ void launch_pair(const ConvGeom &g, unsigned blocks, const float *X, int xs, con
                      ks, bias, out, os, relu, po, (const unsigned *)fx.list,
                      (const unsigned *)fx.elist);
 }
-// pooled epilogue (POOL > 0): no stagger (the host declines it)
+// pooled epilogue (POOL > 0)
 template <int BG, bool PADDED, int POOL>
 void launch_pool(const ConvGeom &g, unsigned blocks, const float *X, int xs, const float *K,
                  int ks, const float *bias, float *out, int os, PoolOut po, F16Aux fx,
@@ -1447,11 +1428,6 @@ template <int BG, bool PADDED>
 void launch(const ConvGeom &g, unsigned blocks, const float *X, int xs, const float *K, int ks,
             const float *bias, float *out, int os, int relu, F16Aux fx, hipStream_t st) {
   const bool tb = tab_bytes(g, PADDED) != 0;
-  if (stagger() && !fx.list) {
-    if (tb) launch_t<BG, PADDED, true, true, 0, false>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, PoolOut{}, fx);
-    else launch_t<BG, PADDED, true, false, 0, false>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, PoolOut{}, fx);
-    return;
-  }
   if (tb) launch_pair<BG, PADDED, true, 0>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, PoolOut{}, fx);
   else launch_pair<BG, PADDED, false, 0>(g, blocks, X, xs, K, ks, bias, out, os, relu, st, PoolOut{}, fx);
 }
@@ -1500,21 +1476,9 @@ struct F16Setup {
 // step with f16x3)
 // (family value 3: f16x3 for every shape, the tests' setting)
 bool use_f16(const ConvGeom &g) {
-  static const int lg = KCNN_KNOB("KCNN_IGF16_LOG2FLOP", 34);
   const int f = family(kFamIgemmX6);
   return g.R > 0 && (f == 3 || (f == 2 && 2.0 * (double)g.M * g.G * g.Kdim >=
-                                              (double)(1ull << lg)));
-}
-// experiment build: KCNN_IGF16_DEBUG=1 prints each call's recomputed tiles
-void report_flags(const F16Aux &fx, unsigned nb, const ConvGeom &g, hipStream_t st) {
-  static const int dbg = KCNN_KNOB("KCNN_IGF16_DEBUG", 0);
-  if (!dbg || !fx.list) return;
-  unsigned n[2] = {0, 0};
-  if (hipMemcpyAsync(n, fx.list, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return;
-  fprintf(stderr, "igemm f16x3: G %d Kdim %d M %lld: %u of %u tiles, %u elements recomputed\n",
-          g.G, g.Kdim, (long long)g.M, n[0], nb, n[1]);
+                                              (double)(1ull << 34)));
 }
 
 }  // namespace
@@ -1575,9 +1539,6 @@ int kcnn_conv_igemm_x6(const ConvGeom &g, const float *X, int xs, const float *K
     if (padded) launch<256, true>(g, nb, X, xs, K, ks, bias, out, os, relu, fs.fx, st);
     else launch<256, false>(g, nb, X, xs, K, ks, bias, out, os, relu, fs.fx, st);
   }
-  report_flags(fs.fx, nb, g, st);
-  if (!f16 && KCNN_KNOB("KCNN_IGF16_DEBUG", 0))
-    fprintf(stderr, "igemm bf16x6: G %d Kdim %d M %lld relu %d\n", g.G, g.Kdim, (long long)g.M, relu);
   return (int)hipGetLastError();
 }
 
@@ -1592,7 +1553,7 @@ int kcnn_conv_igemm_x6_pool(const ConvGeom &g, const float *X, int xs, const flo
                             hipStream_t st) {
   const bool win = (ph == 2 && pw == 1 && g.oh % 2 == 0) ||
                    (ph == 1 && pw == 2 && g.oh == 1 && g.ow % 2 == 0);
-  if (!win || !(pc == 1 || pc == 2 || pc == 4) || g.G % pc != 0 || stagger()) return -1;
+  if (!win || !(pc == 1 || pc == 2 || pc == 4) || g.G % pc != 0) return -1;
   const unsigned nb = igemm_x6_blocks(g, xs, ks);
   if (nb == 0) return -1;
   const bool f16 = use_f16(g);
@@ -1614,7 +1575,6 @@ int kcnn_conv_igemm_x6_pool(const ConvGeom &g, const float *X, int xs, const flo
     else KCNN_IGP(256, false);
   }
 #undef KCNN_IGP
-  report_flags(fs.fx, nb, g, st);
   return (int)hipGetLastError();
 }
 
@@ -1713,20 +1673,17 @@ int kcnn_conv_wgrad_x6(const ConvGeom &g, const float *X, int xs, const float *d
     return (int)hipGetLastError();
   }
   constexpr int lds = 2 * 3 * 384 * ROWB;
-#define KCNN_WX6(P_, S_)                                                                  \
+#define KCNN_WX6(P_)                                                                      \
   do {                                                                                    \
     static bool attr = hipFuncSetAttribute(                                               \
-        reinterpret_cast<const void *>(&conv_wgrad_x6_kernel<P_, S_>),                    \
+        reinterpret_cast<const void *>(&conv_wgrad_x6_kernel<P_>),                        \
         hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;                    \
     (void)attr;                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_x6_kernel<P_, S_>), grid, dim3(NT), lds, st, g, X, xs, \
+    hipLaunchKernelGGL((conv_wgrad_x6_kernel<P_>), grid, dim3(NT), lds, st, g, X, xs,     \
                        dY, dys, ws, fps, ktiles, nblocks);                                \
   } while (0)
-  if (padded) {
-    if (stagger()) KCNN_WX6(true, true); else KCNN_WX6(true, false);
-  } else {
-    if (stagger()) KCNN_WX6(false, true); else KCNN_WX6(false, false);
-  }
+  if (padded) KCNN_WX6(true);
+  else KCNN_WX6(false);
 #undef KCNN_WX6
   return (int)hipGetLastError();
 }

@@ -150,14 +150,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(
 //   * Operands per MFMA: one LDS read (A: W tile, B: im2col tile).
 constexpr int IG2_KTAB = 2304;  // im2col-row table entries (c5 C3: Kdim 2304)
 
-// flags bit: RectifiedLinearComponent's Propagate in the epilogue (the other
-// bits are timing switches of the phase-timing build)
-constexpr int kIg2Relu = 1 << 16;
+constexpr int IG2_BK = 16;      // K step
 
-template <int WGG, bool PADDED, int IG2_BK, bool TAB>
+// relu: RectifiedLinearComponent's Propagate in the epilogue
+template <int WGG, bool PADDED, bool TAB>
 __global__ __launch_bounds__(256) void conv_igemm2_kernel(
     ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ Kmat,
-    int ks, const float *__restrict__ bias, float *__restrict__ out, int os, int dbg) {
+    int ks, const float *__restrict__ bias, float *__restrict__ out, int os, int relu) {
   constexpr int WGM = 4 / WGG;
   constexpr int BG = 64 * WGG, BM = 64 * WGM;
   constexpr int ANF = IG2_BK * BG / 256;  // A floats per thread per K step (4 or 8)
@@ -209,12 +208,12 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(
   }
   const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
       (void *)X, (short)0,
-      (dbg & 4) ? 0 : (int)((int64_t)g.R * xs * 4 < 0x7fffffff ? (int64_t)g.R * xs * 4 : 0x7fffffff),
-      0x00020000);  // dbg & 4: zero records (timing: same instructions, no traffic)
+      (int)((int64_t)g.R * xs * 4 < 0x7fffffff ? (int64_t)g.R * xs * 4 : 0x7fffffff),
+      0x00020000);
 
   // W rows through a descriptor too: rows past Kdim read 0 (range check)
   const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)Kmat, (short)0, (dbg & 8) ? 0 : g.Kdim * ks * 4, 0x00020000);
+      (void *)Kmat, (short)0, g.Kdim * ks * 4, 0x00020000);
   if (!PADDED) tapmask = mvalid ? 0xffffffffu : 0u;
   // TAB: rows past Kdim have tap 31, which no lane's mask admits (kh*kw <= 31)
   const unsigned nmask = PADDED ? ~(tapmask & 0x7fffffffu) : 0u;
@@ -241,7 +240,6 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(
   // branch-free: every load issues back to back; nothing reads a loaded
   // value before store(), so the loads land while the MFMAs run
   auto load = [&](int kt) {
-    if (dbg & 1) return;  // timing experiments: no operand loads
     const int kb = kt * IG2_BK;
 #pragma unroll
     for (int i = 0; i < ANF / 4; i++) {
@@ -288,7 +286,6 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(
     }
   };
   auto store = [&](int b) {
-    if (dbg & 2) return;  // timing experiments: no LDS stores
 #pragma unroll
     for (int i = 0; i < ANF / 4; i++)
       *reinterpret_cast<float4 *>(&As[b][ar + A_RSTEP * i][ag]) = areg[i];
@@ -343,7 +340,7 @@ __global__ __launch_bounds__(256) void conv_igemm2_kernel(
         if (gg >= g.G) continue;
         float v = acc[a][b][r];
         if (bias) v = v + bias[gg];
-        if (dbg & kIg2Relu) v = v < 0.0f ? 0.0f : v;  // ApplyFloor(0)
+        if (relu) v = v < 0.0f ? 0.0f : v;  // ApplyFloor(0)
         orow[(int64_t)gg * g.P] = v;
       }
     }
@@ -759,14 +756,11 @@ __global__ __launch_bounds__(64) void conv_col2im_plane_kernel(
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     const int n = u / g.C, c = u - n * g.C;
     const float *src = Z + (int64_t)n * zs + (int64_t)c * U;
-    if (vec & 2) {  // streaming loads: Z was just written and is read once
+    if (vec) {  // streaming loads: Z was just written and is read once
       typedef float f4 __attribute__((ext_vector_type(4)));
       for (int i = lane; i < U / 4; i += 64)
         reinterpret_cast<f4 *>(zp)[i] =
             __builtin_nontemporal_load(reinterpret_cast<const f4 *>(src) + i);
-    } else if (vec) {
-      for (int i = lane; i < U / 4; i += 64)
-        reinterpret_cast<float4 *>(zp)[i] = reinterpret_cast<const float4 *>(src)[i];
     } else {
       for (int i = lane; i < U; i += 64) zp[i] = src[i];
     }
@@ -855,8 +849,7 @@ struct Wgrad2Plan {
 // S keeps each accumulator chain <= ~8192 terms (fp32 chain error) and is
 // picked so that the blocks fill whole rounds of 512 (2 per CU).
 bool plan_wgrad2(const ConvGeom &g, int xs, int dys, Wgrad2Plan &pl) {
-  static const int enabled = KCNN_KNOB("KCNN_WGRAD2", 1);
-  if (!enabled || g.R <= 0 || g.G < 32 || g.P > 96 || g.Kdim < 32)
+  if (g.R <= 0 || g.G < 32 || g.P > 96 || g.Kdim < 32)
     return false;
   pl.fpc = g.P <= 16 ? 32 / g.P : 1;
   pl.nch = g.P <= 32 ? 1 : (g.P + 31) / 32;
@@ -915,8 +908,7 @@ int launch_wgrad2(const ConvGeom &g, const Wgrad2Plan &pl, const float *X, int x
 // positions than the output (gather waste HW/P; nnet.config layer 1: 840 vs
 // 18, a 47x waste for the flipped-kernel gather).
 bool use_dgrad_scatter(const ConvGeom &g) {
-  static const int enabled = KCNN_KNOB("KCNN_DGRAD_SCATTER", 1);
-  return enabled && g.Kdim >= 32 && 4 * (int64_t)g.HW >= 5 * (int64_t)g.P && g.G >= 16;
+  return g.Kdim >= 32 && 4 * (int64_t)g.HW >= 5 * (int64_t)g.P && g.G >= 16;
 }
 
 size_t zbytes_pad(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -972,10 +964,9 @@ int dgrad_scatter(const ConvGeom &g, const float *dY, MatrixDim dyd,
   if (zlds >= 1024 && zlds <= 32768) {
     const int units = g.R * g.C;
     const bool vec = (g.kh * g.kw * g.P) % 4 == 0 && zd.stride % 4 == 0;
-    static const int nt = KCNN_KNOB("KCNN_COL2IM_NT", 1);
     hipLaunchKernelGGL(conv_col2im_plane_kernel,
                        dim3((unsigned)(units < 256 * 24 ? units : 256 * 24)), dim3(64), zlds,
-                       st, g, z, zd.stride, dX, dxd.stride, vec ? (nt ? 3 : 1) : 0);
+                       st, g, z, zd.stride, dX, dxd.stride, vec ? 1 : 0);
     return kcnn::launch_status();
   }
   const int64_t ne = (int64_t)g.R * g.C * g.HW;
@@ -1083,9 +1074,7 @@ int hipF_conv2d_maxpool3d(const float *in, MatrixDim in_dim, int in_height,
   // long kernels: the implicit GEMM with the pool in its epilogue, for the
   // shapes whose unfused convolution is that same kernel (conv2d_impl: not
   // in the frame kernels' range, not the small-filter direct kernel)
-  // (KCNN_IGEMM_POOL=0: unfused)
-  static const int igpool = KCNN_KNOB("KCNN_IGEMM_POOL", 1);
-  if (!igpool || (g.Kdim <= 64 && g.P >= 16) || use_direct(g, 1)) return -1;
+  if ((g.Kdim <= 64 && g.P >= 16) || use_direct(g, 1)) return -1;
   return kcnn_conv_igemm_x6_pool(g, in, in_dim.stride, kernel, kernel_dim.stride, bias, out,
                                  out_dim.stride, pool, pool_dim.stride, mask, mask_stride, ph,
                                  pw, pc, st) == 0
@@ -1142,37 +1131,26 @@ static int conv2d_impl(const float *in, MatrixDim in_dim, int in_height, int in_
     return 0;
   // implicit GEMM v2 (fp32 MFMA): concat layout, X addressable with 32-bit
   // offsets, tap masks for padded maps need kh*kw <= 32
-  static const int ig2 = KCNN_KNOB("KCNN_IGEMM2", 1);
   const bool padded = g.pad_h > 0 || g.pad_w > 0;
   const int wgg = g.G > 64 ? 2 : 1;
-  if (ig2 && concat && (int64_t)g.R * in_dim.stride * 4 < ((int64_t)1 << 31) &&
+  if (concat && (int64_t)g.R * in_dim.stride * 4 < ((int64_t)1 << 31) &&
       (int64_t)g.Kdim * kernel_dim.stride * 4 < ((int64_t)1 << 31) &&
       g.G % 4 == 0 && kernel_dim.stride % 4 == 0 &&
       (uintptr_t)kernel % 16 == 0 && (!padded || g.kh * g.kw <= 32)) {
     const int bg = 64 * wgg, bm = 64 * (4 / wgg);
     dim3 grid2((unsigned)((g.M + bm - 1) / bm), (unsigned)((g.G + bg - 1) / bg));
-    // timing experiments (operand loads / LDS stores / traffic switched off):
-    // only in the phase-timing build (make timing), never in libkcnn.so
-    static const int ig2timing = KCNN_KNOB("KCNN_IGEMM2_DEBUG", 0);
-    const int ig2dbg = ig2timing | (relu ? kIg2Relu : 0);
-    static const int ig2bk = KCNN_KNOB("KCNN_IGEMM2_BK", 16);
-    static const int ig2tab = KCNN_KNOB("KCNN_IGEMM2_TAB", 1);
-    const bool tab = ig2tab && (g.Kdim + 15) / 16 * 16 <= IG2_KTAB &&
+    const bool tab = (g.Kdim + 15) / 16 * 16 <= IG2_KTAB &&
                      (int64_t)g.HW * g.C < (1 << 28) && (!padded || g.kh * g.kw <= 31);
 #define KCNN_IG2(W_, P_)                                                                  \
   do {                                                                                    \
     if (tab)                                                                              \
-      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, 16, true>), grid2, dim3(256), 0, st, g, \
+      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, true>), grid2, dim3(256), 0, st, g,  \
                          in, in_dim.stride, kernel, kernel_dim.stride, bias, out,          \
-                         out_dim.stride, ig2dbg);                                          \
-    else if (ig2bk == 32)                                                                 \
-      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, 32, false>), grid2, dim3(256), 0, st, g, \
-                         in, in_dim.stride, kernel, kernel_dim.stride, bias, out,          \
-                         out_dim.stride, ig2dbg);                                          \
+                         out_dim.stride, relu);                                            \
     else                                                                                  \
-      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, 16, false>), grid2, dim3(256), 0, st, g, \
+      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, false>), grid2, dim3(256), 0, st, g, \
                          in, in_dim.stride, kernel, kernel_dim.stride, bias, out,          \
-                         out_dim.stride, ig2dbg);                                          \
+                         out_dim.stride, relu);                                            \
   } while (0)
     if (wgg == 2) {
       if (padded) KCNN_IG2(2, true); else KCNN_IG2(2, false);

@@ -70,8 +70,11 @@ constexpr int MAXS = 6;             // wgrad k16 steps per wave (24 over waves 4
 constexpr int MAXT = 3;             // dgrad position tiles per wave (12 over waves 0-3)
 constexpr int MAXU = 2;             // split units per thread (8 * 96 <= 2 * 512)
 constexpr int MAXX = 4;             // X values per thread (C*H*W <= 2048)
-constexpr int PZ = PP + 4;          // Z row (k-major) of conv_bwd_x6p_kernel: 16-B aligned,
+constexpr int PZ = PP + 4;          // Z row (k-major) of conv_bwd_x6q_kernel: 16-B aligned,
                                     // rows 4 banks apart
+// the kernels' flags argument
+constexpr int kX6Clock = 16;        // KCNN_PHASE_TIMING builds: the per-phase clock marks are on
+constexpr int kX6Acc = 1 << 30;     // add to the partial an earlier frame range left there
 
 struct X6Steps {
   uint8_t s[NW][MAXS];  // wgrad k16 steps of each wave, 0xff = none
@@ -114,20 +117,20 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6_kernel(
     ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ dY, int dys,
     const float *__restrict__ K, int ks, float *__restrict__ dX, int dxs,
     float *__restrict__ ws_part, int ZZ, X6Steps steps, int dx_acc,
-    const unsigned char *__restrict__ pmask, int pms, int dbg) {
+    const unsigned char *__restrict__ pmask, int pms, int flags) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef KCNN_PHASE_TIMING  // per-phase clock totals of block 0's waves (dbg & 16)
+#ifdef KCNN_PHASE_TIMING  // per-phase clock totals of block 0's waves (flags & kX6Clock)
   long long tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tprev = clock64();
 #define KCNN_TMARK(i)                                   \
-  if (dbg & 16) {                                       \
+  if (flags & kX6Clock) {                               \
     const long long tn = clock64();                     \
     tm[i] += tn - tprev;                                \
     tprev = tn;                                         \
   }
 #else
 #define KCNN_TMARK(i)
-  (void)dbg;
+  (void)flags;
 #endif
   const int P = g.P;
   const int Hp = g.H + 2 * g.pad_h, Wp = g.W + 2 * g.pad_w;
@@ -517,7 +520,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6_kernel(
       col2im(nprev);
     }
 #ifdef KCNN_PHASE_TIMING
-    if ((dbg & 16) && blockIdx.x == 0 && lane == 0)
+    if ((flags & kX6Clock) && blockIdx.x == 0 && lane == 0)
       printf("bwdx6 wave %d: B1 %lld ch0 %lld split %lld B2 %lld im2col %lld dma %lld mfma %lld "
              "tail %lld\n", wave, tm[0], tm[1], tm[2], tm[3], tm[4], tm[5], tm[6], tm[7]);
 #endif
@@ -543,8 +546,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6_kernel(
         float sum = 0.0f;
 #pragma unroll
         for (int w = 0; w < 4; w++) sum += red[w * 1024 + e];
-        // (dbg bit 30: add to the partial an earlier frame range left there)
-        dst[i * g.G + ch * 32 + j] = (dbg & (1 << 30)) ? dst[i * g.G + ch * 32 + j] + sum : sum;
+        dst[i * g.G + ch * 32 + j] = (flags & kX6Acc) ? dst[i * g.G + ch * 32 + j] + sum : sum;
       }
     }
   };
@@ -558,525 +560,22 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6_kernel(
 }
 
 // ---------------------------------------------------------------------------
-#ifdef KCNN_EXPERIMENTS  // the round-2/3 pipelined kernel, x6q's predecessor:
-                         // only the experiment build (KCNN_BWD_X6P=1) has it
-// conv_bwd_x6p_kernel: conv_bwd_x6_kernel's math bit for bit -- the same
-// image contents, operand fragments, and order of the MFMAs into every
-// accumulator -- software-pipelined, for the pooled backward with both
-// outputs (DX and WG, a folded PH x 1 x PCM Maxpool, NCH >= 2 slabs per
-// frame: c2, c5 C1).
+// conv_bwd_x6q_kernel: conv_bwd_x6_kernel's math bit for bit (the same image
+// contents, operand fragments and MFMA order into every accumulator),
+// software-pipelined, for the pooled backward with both outputs (DX and WG,
+// a folded PH x 1 x PCM Maxpool, NCH >= 2 slabs per frame: c2, c5 C1).
 //
 // conv_bwd_x6_kernel alternates an all-VALU phase (every wave splits the
 // next slab into the image) with an all-MFMA phase, two barriers apart, so
 // each SIMD's matrix pipe idles while its waves split (c2, block 0: split
 // 134 k, MFMA phase 167 k of 495 k cycles per wave, MFMA pipe 28 % busy).
-// Here the split of slab t+1 runs beside the MFMAs of slab t.  A thread
-// keeps its split units' gated bf16 planes in registers until the image is
-// free, and its raw dP / mask values come from HBM into registers one slab
-// ahead (no staging buffer, no LDS-DMA).  Per SIMD, the dgrad wave w and the
-// wgrad wave w + 4:
-//
-//   MFMA phase t   dgrad wave: split its 2 units of slab t+1, prefetch their
-//                  raw values of slab t+2, then its dgrad MFMAs of slab t
-//                  (position tiles w, w + 4, w + 8);  wgrad wave: its wgrad
-//                  MFMAs of slab t, then the frame work (col2im of the
-//                  previous frame on the first slab, the next frame's im2col
-//                  gather on the last), then its 1 unit of slab t+1 -- so
-//                  each wave's VALU runs beside its partner's MFMAs.  The
-//                  dgrad waves store the frame's Z on its last slab.
-//   barrier Ba     the image of slab t is read no more
-//   write phase    the held planes of slab t+1 -> the image; the map of the
-//                  frame after next -> LDS (last slab)
-//   barrier Bb     the image of slab t+1 is published
-//
-// Z is kept k-major here ([Kdim][PZ], a lane's accumulator rows are 16-B
-// runs); the col2im adds the same values in the same order.
-template <int NCH, int PCM, int PH>
-__global__ __launch_bounds__(NT, 1) void conv_bwd_x6p_kernel(
-    ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ dP, int dps,
-    const float *__restrict__ K, int ks, float *__restrict__ dX, int dxs,
-    float *__restrict__ ws_part, int ZZ, X6Steps steps, int dx_acc,
-    const unsigned char *__restrict__ pmask, int pms, int dbg) {
-  static_assert(NCH >= 2 && PCM > 0, "pooled backward with >= 2 slabs per frame");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef KCNN_PHASE_TIMING  // per-phase clock totals of block 0's waves (dbg & 16)
-  long long tm[6] = {0, 0, 0, 0, 0, 0};
-  long long tprev = clock64();
-#define KCNN_TMARK(i)               \
-  if (dbg & 16) {                   \
-    const long long tn = clock64(); \
-    tm[i] += tn - tprev;            \
-    tprev = tn;                     \
-  }
-#else
-#define KCNN_TMARK(i)
-  (void)dbg;
-#endif
-  using MaskT = typename std::conditional<(PH > 1), unsigned short, unsigned char>::type;
-  constexpr int MB = (int)sizeof(MaskT);
-  constexpr int NJ = 32 / PCM;                         // pooled rows per slab
-  constexpr int SPL = NT;                                 // splitting threads
-  constexpr int MAXUP = (NJ * (PP / 4) + SPL - 1) / SPL;  // split units per thread
-  const int P = g.P;
-  const int Q = P / PH;  // pooled positions per dP row
-  const int Hp = g.H + 2 * g.pad_h, Wp = g.W + 2 * g.pad_w;
-  const int CHWp = g.C * Hp * Wp;
-  char *Yp = smem;                                            // [3][32][384] bf16
-  char *Wimg = Yp + 3 * YPL;                                  // [3][32][128] bf16
-  // Z k-major, [Kdim][PZ]: a lane's accumulator rows are runs of 4
-  // consecutive positions of one k, stored as 16-B writes
-  float *Zt = reinterpret_cast<float *>(Wimg + 3 * WPL);
-  float *Xs = Zt + g.Kdim * PZ;                               // padded map + {1}
-  int *qtab = reinterpret_cast<int *>(Xs + round4(CHWp + 1));  // [384]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l = lane & 31, hf = lane >> 5;
-  const int CHW = g.C * g.HW;
-  const bool unpadded = g.pad_h == 0 && g.pad_w == 0;
-  const int ntile = (P + 31) >> 5;
-  const int PW = (P + 15) & ~15;
-  const int NPQ = PW >> 2;
-  const int NU = NJ * NPQ;
-  const int G = (int)gridDim.x;
-  const int rowf = (g.G / PCM) * Q;  // pooled values per frame row
-
-  // W planes (dgrad B operand), as conv_bwd_x6_kernel
-  for (int e = tid; e < 32 * 64; e += NT) {
-    const int k = e >> 6, gg = (e & 63) * 2;
-    const float v0 = (k < g.Kdim && gg < g.G) ? K[(int64_t)k * ks + gg] : 0.0f;
-    const float v1 = (k < g.Kdim && gg + 1 < g.G) ? K[(int64_t)k * ks + gg + 1] : 0.0f;
-    uint32_t h, m, lo;
-    split2(v0, v1, h, m, lo);
-    const int o = woff(k, gg);
-    *reinterpret_cast<uint32_t *>(Wimg + o) = h;
-    *reinterpret_cast<uint32_t *>(Wimg + WPL + o) = m;
-    *reinterpret_cast<uint32_t *>(Wimg + 2 * WPL + o) = lo;
-  }
-  int abase = CHWp * 4, qmul = 0;
-  if (l < g.Kdim) {
-    uint32_t c, r, qx, qy;
-    g.div_khkw.divmod((uint32_t)l, c, r);
-    g.div_kh.divmod(r, qx, qy);
-    abase = ((int)c * Hp * Wp + (int)qx * Hp + (int)qy) * 4;
-    qmul = 1;
-  }
-  for (int e = tid; e < CHWp; e += NT) Xs[e] = 0.0f;
-  if (tid == 0) Xs[CHWp] = 1.0f;
-  for (int p = tid; p < PP; p += NT) {
-    uint32_t px, py;
-    g.div_oh.divmod((uint32_t)p, px, py);
-    qtab[p] = p < P ? ((int)px * Hp + (int)py) * 4 : 0x3fffffff;
-  }
-  const uint32_t amax = (uint32_t)CHWp * 4;
-  const char *Xb = reinterpret_cast<const char *>(Xs);
-
-  // ---- split units: (pooled row j, position quad p0), the same in every
-  // slab; the dgrad waves' threads own units tid + 256 i
-  int uj[MAXUP], up0[MAXUP], ubase[MAXUP], ux[MAXUP][2];
-#pragma unroll
-  for (int i = 0; i < MAXUP; ++i) {
-    const int u = min(tid + SPL * i, NU - 1);
-    uj[i] = u / NPQ;
-    up0[i] = (u - uj[i] * NPQ) * 4;
-    const int r0 = PCM * uj[i];
-    ubase[i] = r0 * ROWB + ((up0[i] >> 7) << 8) + ((up0[i] & 7) << 1);
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) ux[i][hh] = ((up0[i] >> 3) & 15) ^ (((r0 >> 2) + hh) & 3);
-  }
-  // raw values of a unit: PH == 1 the quad's 4 dP values, PH > 1 the 2
-  // windows' values; the mask bytes of the same positions as two dwords
-  // (aligned down) and the byte shift.  U: units per thread of the role
-  // (MAXUP for the dgrad waves; the wgrad waves split nothing)
-  constexpr int NX = PH > 1 ? 2 : 4;
-  auto load_raw = [&](auto Uc, float (&rx)[decltype(Uc)::value][NX],
-                      uint32_t (&rm)[decltype(Uc)::value][2], int (&rsh)[decltype(Uc)::value],
-                      int nn, int cc) {
-    constexpr int U = decltype(Uc)::value;
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(dP + (int64_t)nn * dps), (short)0, rowf * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(pmask + (int64_t)nn * pms), (short)0, rowf * MB, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      if (tid + SPL * i >= NU) break;
-      const int s = (cc * NJ + uj[i]) * Q + (PH > 1 ? up0[i] / PH : up0[i]);
-      if constexpr (NX == 4) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rd, (unsigned)s * 4u, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) rx[i][q] = __uint_as_float(v[q]);
-      } else {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rd, (unsigned)s * 4u, 0, 0);
-        rx[i][0] = __uint_as_float(v[0]);
-        rx[i][1] = __uint_as_float(v[1]);
-      }
-      const unsigned mo = (unsigned)s * MB;
-      const auto w = __builtin_amdgcn_raw_buffer_load_b64(rk, mo & ~3u, 0, 0);
-      rm[i][0] = w[0];
-      rm[i][1] = w[1];
-      rsh[i] = (int)(mo & 3u);
-    }
-  };
-  // gated planes of a unit: [map c][plane][2 dwords]
-  auto split_raw = [&](auto Uc, const float (&rx)[decltype(Uc)::value][NX],
-                       const uint32_t (&rm)[decltype(Uc)::value][2],
-                       const int (&rsh)[decltype(Uc)::value],
-                       uint32_t (&sres)[decltype(Uc)::value][PCM][6]) {
-    constexpr int U = decltype(Uc)::value;
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      if (tid + SPL * i >= NU) break;
-      const int p0 = up0[i];
-      const uint32_t mw = __builtin_amdgcn_alignbyte(rm[i][1], rm[i][0], (uint32_t)rsh[i]);
-      float x[4];
-      unsigned mk[4];
-      short rq[4];
-      if constexpr (PH > 1) {
-        const int pq0 = p0 / PH, r0 = p0 - pq0 * PH;
-        const unsigned m0 = mw & 0xffffu, m1 = mw >> 16;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const bool sel = r0 + q >= PH;
-          rq[q] = (short)(r0 + q - (sel ? PH : 0));
-          x[q] = sel ? rx[i][1] : rx[i][0];
-          mk[q] = p0 + q < P ? (sel ? m1 : m0) : 0u;
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          rq[q] = 0;
-          x[q] = rx[i][q];
-          mk[q] = p0 + q < P ? (mw >> (8 * q)) & 0xffu : 0u;
-        }
-      }
-      uint32_t h01, m01, l01, h23, m23, l23;
-      split2(x[0], x[1], h01, m01, l01);
-      split2(x[2], x[3], h23, m23, l23);
-      const s16x2 w01 = __builtin_bit_cast(s16x2, mk[0] | (mk[1] << 16));
-      const s16x2 w23 = __builtin_bit_cast(s16x2, mk[2] | (mk[3] << 16));
-      const s16x2 b01 = {(short)(15 - rq[0]), (short)(15 - rq[1])};
-      const s16x2 b23 = {(short)(15 - rq[2]), (short)(15 - rq[3])};
-#pragma unroll
-      for (int c = 0; c < PCM; ++c) {
-        const s16x2 cc = {(short)(c * PH), (short)(c * PH)}, k15 = {15, 15};
-        const s16x2 sh01 = b01 - cc, sh23 = b23 - cc;
-        const uint32_t s01 = __builtin_bit_cast(uint32_t, (s16x2)((w01 << sh01) >> k15));
-        const uint32_t s23 = __builtin_bit_cast(uint32_t, (s16x2)((w23 << sh23) >> k15));
-        sres[i][c][0] = h01 & s01;
-        sres[i][c][1] = h23 & s23;
-        sres[i][c][2] = m01 & s01;
-        sres[i][c][3] = m23 & s23;
-        sres[i][c][4] = l01 & s01;
-        sres[i][c][5] = l23 & s23;
-      }
-    }
-  };
-  auto write_sres = [&](auto Uc, const uint32_t (&sres)[decltype(Uc)::value][PCM][6]) {
-    constexpr int U = decltype(Uc)::value;
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      if (tid + SPL * i >= NU) break;
-#pragma unroll
-      for (int c = 0; c < PCM; ++c) {
-        const int o = ubase[i] + c * ROWB + ((ux[i][c >> 2] ^ ((c & 3) << 2)) << 4);
-        *reinterpret_cast<uint2 *>(Yp + o) = make_uint2(sres[i][c][0], sres[i][c][1]);
-        *reinterpret_cast<uint2 *>(Yp + YPL + o) = make_uint2(sres[i][c][2], sres[i][c][3]);
-        *reinterpret_cast<uint2 *>(Yp + 2 * YPL + o) = make_uint2(sres[i][c][4], sres[i][c][5]);
-      }
-    }
-  };
-
-  // ---- X map (wgrad A operand) ----
-  float xv[MAXX];
-  auto load_x = [&](int n) {
-#pragma unroll
-    for (int i = 0; i < MAXX; i++)
-      if (tid + NT * i < CHW) xv[i] = X[(int64_t)n * xs + tid + NT * i];
-  };
-  auto commit_x = [&]() {
-#pragma unroll
-    for (int i = 0; i < MAXX; i++) {
-      const int e = tid + NT * i;
-      if (e < CHW) {
-        int slot = e;
-        if (!unpadded) {
-          uint32_t c, q, wi, hi;
-          g.div_HW.divmod((uint32_t)e, c, q);
-          g.div_H.divmod(q, wi, hi);
-          slot = (int)c * Hp * Wp + ((int)wi + g.pad_w) * Hp + (int)hi + g.pad_h;
-        }
-        Xs[slot] = xv[i];
-      }
-    }
-  };
-  // ---- col2im (dX) from Zs: conv_bwd_x6_kernel's, the same sums in the same order
-  const int khkw = g.kh * g.kw;
-  // element (p, k) at k * PZ + p: tap (kx, ky) of output (c, tx, ty) at
-  // c khkw PZ + tx oh + ty + kx (kh PZ - oh) + ky (PZ - 1)
-  const int zax = g.kh * PZ - g.oh, zby = PZ - 1;
-  auto col2im = [&](int nn) {
-#pragma unroll 1
-    for (int i = 0; i < MAXX; i++) {
-      const int e = tid + NT * i;
-      if (e >= CHW) continue;
-      uint32_t c, q, wi, hi;
-      g.div_HW.divmod((uint32_t)e, c, q);
-      g.div_H.divmod(q, wi, hi);
-      const int ty = (int)hi + g.pad_h, tx = (int)wi + g.pad_w;
-      const int zb = (int)c * khkw * PZ + tx * g.oh + ty;
-      const int ylo = max(0, ty - g.oh + 1), ny = min(g.kh - 1, ty) - ylo;
-      const int xlo = max(0, tx - g.ow + 1), xhi = min(g.kw - 1, tx);
-      float sum = 0.0f;
-      for (int kx = xlo; kx <= xhi; kx++) {
-        const int zk = zb + kx * zax;
-        for (int k0 = 0; k0 < g.kh; k0 += 8) {
-          float v[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) v[u] = Zt[zk + (k0 + u) * zby];
-#pragma unroll
-          for (int u = 0; u < 8; u++)
-            sum += (unsigned)(k0 + u - ylo) <= (unsigned)ny ? v[u] : 0.0f;
-        }
-      }
-      float *d = dX + (int64_t)nn * dxs + e;
-      *d = dx_acc ? *d + sum : sum;
-    }
-  };
-
-  const bool dgrad_wave = wave < 4;
-  int my_steps = 0;
-  int stp[MAXS];
-#pragma unroll
-  for (int s = 0; s < MAXS; ++s) {
-    stp[s] = steps.s[wave][s];
-    if (!dgrad_wave && stp[s] != 0xff) my_steps = s + 1;
-  }
-  // the frame's im2col values of this wave's steps, split once per frame
-  auto gather = [&](auto &a) {
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {
-      if (s >= my_steps) break;
-      const int pbase = 16 * stp[s] + 8 * hf;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const uint32_t off = min((uint32_t)(abase + qmul * qtab[pbase + e]), amax);
-        v[e] = *reinterpret_cast<const float *>(Xb + off);
-      }
-      split8(v, a[s][0], a[s][1], a[s][2]);
-      __builtin_amdgcn_sched_barrier(0);  // one step's temporaries at a time
-    }
-  };
-
-  const int n0 = blockIdx.x;
-  auto frames = [&](auto role) {
-    constexpr bool RD = decltype(role)::value == 1;  // dgrad waves
-    constexpr int U = RD ? MAXUP : 1;
-    using UC = std::integral_constant<int, U>;
-    float rx[U][NX];
-    uint32_t rm[U][2];
-    int rsh[U];
-    uint32_t sres[U][PCM][6];
-    // (defined on every path: steps past my_steps are never used, but an
-    // undefined register set costs the allocator spills)
-    bf16x8 ain[RD ? 1 : MAXS][3];
-#pragma unroll
-    for (int s = 0; s < (RD ? 1 : MAXS); ++s)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) ain[s][pl] = bf16x8{};
-    // ---- prologue: the maps of the first two frames, the first frame's
-    // im2col values, its first slab in the image, its second slab's raw values
-    load_x(n0);
-    load_raw(UC{}, rx, rm, rsh, n0, 0);
-    __syncthreads();  // Xs zeroed, qtab and the W image written
-    commit_x();
-    if (n0 + G < g.R) load_x(n0 + G);
-    __syncthreads();
-    if constexpr (!RD) gather(ain);
-    split_raw(UC{}, rx, rm, rsh, sres);
-    load_raw(UC{}, rx, rm, rsh, n0, 1);
-    __syncthreads();  // the gather's reads of Xs are done
-    if (n0 + G < g.R) commit_x();
-    write_sres(UC{}, sres);
-    __syncthreads();  // Bb: slab (n0, 0) in the image, frame n0 + G's map in Xs
-
-    floatx16 wacc[RD ? 1 : NCH];
-#pragma unroll
-    for (int c = 0; c < (RD ? 1 : NCH); c++) wacc[c] = zero16();
-    int nprev = -1;
-
-    for (int n = n0; n < g.R; n += G) {
-      // dgrad position tiles: the dgrad waves w, w + 4; the wgrad waves take
-      // one each (w + 4 = tiles 8-11), beside their weight-gradient steps
-      constexpr int TT = RD ? MAXT : 1;
-      floatx16 zacc[TT];
-#pragma unroll
-      for (int t = 0; t < TT; ++t) zacc[t] = zero16();
-      auto tile_of = [&](int t) { return wave + 4 * t; };
-      // Z[p][k] += dY^T W on this wave's position tiles: MFMA group gi =
-      // (tile t = gi / 2, k16 slice s = gi % 2), the next group's transposed
-      // reads issued before the current group's MFMAs (two fragment sets live,
-      // not every group's: the wgrad role's registers are tight)
-      auto dgrad = [&](int ch) {
-        bf16x8 wf[2][3];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
-            wf[s][pl] = *reinterpret_cast<const bf16x8 *>(
-                Wimg + pl * WPL + woff(l, ch * 32 + 16 * s + 8 * hf));
-        const int G4 = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-        auto load_af = [&](int gi, bf16x8 (&af)[3]) {
-          const int col = tile_of(gi >> 1) * 32 + 16 * (G4 & 1) + 4 * pp;
-          const int row = 16 * (gi & 1) + 8 * (G4 >> 1) + q;
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (lds_s16x4 *)(Yp + pl * YPL + yoff(row, col)));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (lds_s16x4 *)(Yp + pl * YPL + yoff(row + 4, col)));
-            af[pl] = __builtin_bit_cast(
-                bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-          }
-        };
-        constexpr int NG = 2 * TT;
-        bf16x8 afb[2][3];
-        if (tile_of(0) < ntile) load_af(0, afb[0]);
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-          if (tile_of(gi >> 1) >= ntile) break;  // uniform
-          if (gi + 1 < NG && tile_of((gi + 1) >> 1) < ntile) load_af(gi + 1, afb[(gi + 1) & 1]);
-          zacc[gi >> 1] = mfma6(afb[gi & 1], wf[gi & 1], zacc[gi >> 1]);
-        }
-      };
-      // Z of this frame -> LDS: its last reader, the col2im of the previous
-      // frame in this frame's first slab, is two barriers back
-      auto store_z = [&]() {
-#pragma unroll
-        for (int t = 0; t < TT; ++t) {
-          const int pt = tile_of(t);
-          if (pt >= ntile) break;
-          // rows (r & 3) + 8 (r >> 2) + 4 hf: four runs of 4 positions
-          // (positions past P land in the row's tail, never read)
-          if (l < g.Kdim) {
-            float *zr = Zt + l * PZ + pt * 32 + 4 * hf;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-              *reinterpret_cast<float4 *>(zr + 8 * i) =
-                  make_float4(zacc[t][4 * i], zacc[t][4 * i + 1], zacc[t][4 * i + 2],
-                              zacc[t][4 * i + 3]);
-          }
-        }
-      };
-#pragma unroll
-      for (int ch = 0; ch < NCH; ch++) {
-        // slab t = (n, ch); t+1 and t+2 in frame order
-        const int n1 = ch + 1 < NCH ? n : n + G;
-        const int n2 = ch + 2 < NCH ? n : n + G, c2 = ch + 2 < NCH ? ch + 2 : ch + 2 - NCH;
-        const bool next = n1 < g.R;
-        KCNN_TMARK(5)
-        if (ch == 0 && n + 2 * G < g.R) load_x(n + 2 * G);
-        if constexpr (RD) {
-          // the split of slab t+1 beside the wgrad waves' MFMAs, then ours
-          if (next) {
-            split_raw(UC{}, rx, rm, rsh, sres);
-            if (n2 < g.R) load_raw(UC{}, rx, rm, rsh, n2, c2);
-          }
-          KCNN_TMARK(0)
-          dgrad(ch);
-          KCNN_TMARK(1)
-          if (ch == 0 && nprev >= 0) col2im(nprev);
-        } else {
-          // gW[k][g] += im2col(X) dY^T over this wave's k16 steps of p (the
-          // next step's row reads issued before the current step's MFMAs)
-          // yoff(l, 16 stp + 8 hf) = l ROWB + (stp >> 3) 256 + (((stp & 7) << 5) ^
-          // ((hf ^ swz4(l)) << 4)): the lane part passes through an opaque
-          // move each slab, so the compiler does not hoist (and spill) six
-          // per-step addresses out of the frame loop
-          int lx, lrow;
-          asm volatile("v_mov_b32 %0, %1" : "=v"(lx) : "v"((hf ^ swz4(l)) << 4));
-          asm volatile("v_mov_b32 %0, %1" : "=v"(lrow) : "v"(l * ROWB));
-          auto load_bf = [&](int s, bf16x8 (&bf)[3]) {
-            const int off = lrow + ((stp[s] >> 3) << 8) + (((stp[s] & 7) << 5) ^ lx);
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-              bf[pl] = *reinterpret_cast<const bf16x8 *>(Yp + pl * YPL + off);
-          };
-          bf16x8 bfb[2][3];
-          if (my_steps > 0) load_bf(0, bfb[0]);
-#pragma unroll
-          for (int s = 0; s < MAXS; ++s) {
-            if (s >= my_steps) break;
-            if (s + 1 < MAXS && s + 1 < my_steps) load_bf(s + 1, bfb[(s + 1) & 1]);
-            wacc[ch] = mfma6(ain[s], bfb[s & 1], wacc[ch]);
-          }
-          KCNN_TMARK(1)
-          if (ch == 0 && nprev >= 0) col2im(nprev);
-          // the next frame's im2col values (its map went to Xs two barriers
-          // ago; this slab's MFMAs were the last readers of ain)
-          if (ch == NCH - 1 && n + G < g.R) gather(ain);
-        }
-        if (RD && ch == NCH - 1) store_z();
-        KCNN_TMARK(2)
-        __syncthreads();  // Ba: the image of slab t is read no more
-        KCNN_TMARK(3)
-        if (next) {
-          // the wgrad waves split their unit here, beside the dgrad waves'
-          // LDS writes (its planes are not held through the MFMA phase)
-          if constexpr (!RD) {
-            split_raw(UC{}, rx, rm, rsh, sres);
-            if (n2 < g.R) load_raw(UC{}, rx, rm, rsh, n2, c2);
-          }
-          write_sres(UC{}, sres);
-        }
-        // the map of the frame after next (Xs was last read by this slab's gather)
-        if (ch == NCH - 1 && n + 2 * G < g.R) commit_x();
-        __syncthreads();  // Bb: slab t+1 published
-        KCNN_TMARK(4)
-      }
-      nprev = n;
-    }
-    __syncthreads();  // the last frame's Z
-    if (nprev >= 0) col2im(nprev);
-#ifdef KCNN_PHASE_TIMING
-    if ((dbg & 16) && blockIdx.x == 0 && lane == 0)
-      printf("bwdx6p wave %d: split %lld mfma %lld frame %lld Ba %lld write+Bb %lld top %lld\n",
-             wave, tm[0], tm[1], tm[2], tm[3], tm[4], tm[5]);
-#endif
-    // the wgrad waves' partials summed in a fixed order, as conv_bwd_x6_kernel
-    const int E = (g.Kdim + 1) * g.G;
-    float *dst = ws_part + (int64_t)blockIdx.x * E;
-    float *red = reinterpret_cast<float *>(Yp);
-#pragma unroll
-    for (int ch = 0; ch < NCH; ch++) {
-      __syncthreads();
-      if constexpr (!RD) {
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-          red[(wave - 4) * 1024 + mfma32_row(r, lane) * 32 + l] = wacc[ch][r];
-      }
-      __syncthreads();
-      for (int e = tid; e < 1024; e += NT) {
-        const int i = e >> 5, j = e & 31;
-        if (i > g.Kdim) continue;
-        float sum = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) sum += red[w * 1024 + e];
-        // (dbg bit 30: add to the partial an earlier frame range left there)
-        dst[i * g.G + ch * 32 + j] = (dbg & (1 << 30)) ? dst[i * g.G + ch * 32 + j] + sum : sum;
-      }
-    }
-  };
-  if (dgrad_wave) frames(std::integral_constant<int, 1>{});
-  else frames(std::integral_constant<int, 2>{});
-#undef KCNN_TMARK
-}
-#endif  // KCNN_EXPERIMENTS
-
-// ---------------------------------------------------------------------------
-// conv_bwd_x6q_kernel: conv_bwd_x6p_kernel's math bit for bit (the same image
-// contents, fragments and MFMA order into every accumulator), with the slab
-// image consumed in two position halves so that its LDS writes run beside
-// the MFMAs instead of between them.
+// Here the split of slab t+1 runs beside the MFMAs of slab t: a thread keeps
+// its split units' gated bf16 planes in registers until the image is free,
+// and its raw dP / mask values come from HBM into registers one slab ahead
+// (no staging buffer, no LDS-DMA).  The slab image is consumed in two
+// position halves, so that its LDS writes run beside the MFMAs instead of
+// between them.  Z is kept k-major ([Kdim][PZ], a lane's accumulator rows
+// are 16-B runs); the col2im adds the same values in the same order.
 //
 // Half A = positions 0-255 (dgrad tiles 0-7: tiles w and w + 4 of dgrad wave
 // w; wgrad steps 0-15: steps 0-3 of every wgrad wave), half B = 256-383
@@ -1095,7 +594,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6p_kernel(
 // dgrad-wave thread u.  Frame work sits where an accumulator's last reader
 // is behind a barrier: the wgrad waves gather the next frame's A-step
 // im2col values in P_A of the last slab, behind that phase's MFMAs on them
-// (KCNN_X6Q_GA of them; the rest in its P_B), and its B-step values in P_A
+// (GA of them; the rest in its P_B), and its B-step values in P_A
 // of the first; the next frame's map goes to Xs in P_B of the first slab; the
 // dgrad waves col2im the previous frame over P_A of every slab (from a
 // per-element tap table, ahead of the last slab's store of Z; on the wgrad
@@ -1113,26 +612,21 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
     ConvGeom g, const float *__restrict__ X, int xs, const float *__restrict__ dP, int dps,
     const float *__restrict__ K, int ks, float *__restrict__ dX, int dxs,
     float *__restrict__ ws_part, int ZZ, X6Steps steps, int dx_acc,
-    const unsigned char *__restrict__ pmask, int pms, int dbg) {
+    const unsigned char *__restrict__ pmask, int pms, int flags) {
   static_assert(NCH >= 2 && PCM > 0, "pooled backward with >= 2 slabs per frame");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef KCNN_PHASE_TIMING  // per-phase clock totals of block 0's waves (dbg & 16)
+#ifdef KCNN_PHASE_TIMING  // per-phase clock totals of block 0's waves (flags & kX6Clock)
   long long tm[5 * NCH] = {};
   long long tprev = clock64();
 #define KCNN_TMARK(i)               \
-  if (dbg & 16) {                   \
+  if (flags & kX6Clock) {           \
     const long long tn = clock64(); \
     tm[i] += tn - tprev;            \
     tprev = tn;                     \
   }
-// timing experiments that skip work (wrong results): 32 no image stores, 64
-// no MFMAs, 128 no splits, 256 no frame work (gather, col2im, map, Z), 512
-// no gather, 1024 no col2im
-#define KCNN_SKIP(b) (dbg & (b))
 #else
 #define KCNN_TMARK(i)
-#define KCNN_SKIP(b) false
-  (void)dbg;
+  (void)flags;
 #endif
   (void)ZZ;
   using MaskT = typename std::conditional<(PH > 1), unsigned short, unsigned char>::type;
@@ -1262,7 +756,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
   };
   auto split_raw = [&](const Unit &U, const float (&rx)[NX], const uint32_t (&rm)[2],
                        int rsh, uint32_t (&sres)[PCM][6]) {
-    if (!U.on || KCNN_SKIP(128)) return;
+    if (!U.on) return;
     const int p0 = U.p0;
     const uint32_t mw = __builtin_amdgcn_alignbyte(rm[1], rm[0], (uint32_t)rsh);
     float x[4];
@@ -1308,7 +802,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
     }
   };
   auto write_sres = [&](const Unit &U, const uint32_t (&sres)[PCM][6]) {
-    if (!U.on || KCNN_SKIP(32)) return;
+    if (!U.on) return;
 #pragma unroll
     for (int c = 0; c < PCM; ++c) {
       const int ux = (c >> 2) ? U.x1 : U.x0;
@@ -1476,10 +970,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
   // A steps of the next frame gathered in P_A of the last slab, the rest in
   // its P_B (c2 pooled backward, 3 runs each: 0 178.5 us, 1 179.1, 2 176.7,
   // 4 174.6; moving the dgrad waves' col2im shares to P_B measured 184.5)
-#ifndef KCNN_X6Q_GA
-#define KCNN_X6Q_GA 4
-#endif
-  constexpr int GA = KCNN_X6Q_GA;
+  constexpr int GA = 4;
   static_assert(GA >= 0 && GA <= SA, "A-step gather split");
   using CGA = std::integral_constant<int, GA>;
 
@@ -1558,8 +1049,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
           if (tile_of(gi >> 1) >= ntile) break;  // uniform
           if (gi + 1 < 2 * T1) load_af(gi + 1, afb[(gi + 1 - 2 * T0) & 1]);  // unconditional
           __builtin_amdgcn_sched_barrier(0);
-          if (!KCNN_SKIP(64))
-            zacc[gi >> 1] = mfma6(afb[(gi - 2 * T0) & 1], wf[gi & 1], zacc[gi >> 1]);
+          zacc[gi >> 1] = mfma6(afb[(gi - 2 * T0) & 1], wf[gi & 1], zacc[gi >> 1]);
         }
       };
       // gW[k][g] += im2col(X) dY^T over this wave's k16 steps [S0, S1) (the
@@ -1588,7 +1078,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
           // counts at the MFMAs conservative and serialise the reads
           if (s + 1 < S1) load_bf(s + 1, bfb[(s + 1 - S0) & 1]);
           __builtin_amdgcn_sched_barrier(0);  // the next step's reads stay ahead of these MFMAs
-          if (!KCNN_SKIP(64)) wacc[ch] = mfma6(ain[s], bfb[(s - S0) & 1], wacc[ch]);
+          wacc[ch] = mfma6(ain[s], bfb[(s - S0) & 1], wacc[ch]);
         }
       };
       auto store_z = [&]() {
@@ -1618,7 +1108,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
           // the previous frame's dX (its Z went to LDS before the last Bb;
           // this frame's store of Z is in P_B of its last slab), here where
           // the fewest registers are live, beside the wgrad waves' MFMAs
-          if (nprev >= 0 && !KCNN_SKIP(256 | 1024)) {  // spread over the frame's P_A phases
+          if (nprev >= 0) {  // spread over the frame's P_A phases
             constexpr int PER = (MAXC + NCH - 1) / NCH;
             col2im(nprev, ch * PER, min((ch + 1) * PER, MAXC));
           }
@@ -1635,12 +1125,12 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
           }
           // frame n's B-step values (their last reader: P_B of frame n - G's
           // last slab; Xs holds frame n's map until P_B of this slab)
-          if (ch == 0 && !KCNN_SKIP(256 | 512)) gather(ain, CA{}, CS{});
+          if (ch == 0) gather(ain, CA{}, CS{});
           // the next frame's first GA A-step values, behind this phase's MFMAs
           // on them (Xs has held the next frame's map since P_B of the first
           // slab): the wgrad waves' P_A is the shorter of the two roles'
           if constexpr (GA > 0)
-            if (ch == NCH - 1 && n + G < g.R && !KCNN_SKIP(256 | 512)) gather(ain, C0{}, CGA{});
+            if (ch == NCH - 1 && n + G < g.R) gather(ain, C0{}, CGA{});
         }
         KCNN_TMARK(5 * ch + 0)
         __syncthreads();  // Ba: half A of slab t read, its B half published
@@ -1653,13 +1143,13 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
             load_raw(ub, rxB, rmB, rshB, min(n2, g.R - 1), c2);
           }
           dgrad(ch, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
-          if (ch == NCH - 1 && !KCNN_SKIP(256)) store_z();
+          if (ch == NCH - 1) store_z();
         } else {
           wgrad(ch, CA{}, CS{});
           // the next frame's other A-step values (their last reader was P_A
           // of this slab; its map went to Xs in P_B of the first slab)
           if constexpr (GA < SA)
-            if (ch == NCH - 1 && n + G < g.R && !KCNN_SKIP(256 | 512)) gather(ain, CGA{}, CA{});
+            if (ch == NCH - 1 && n + G < g.R) gather(ain, CGA{}, CA{});
         }
         if (ch == 0) {
           if (n + G < g.R) commit_x();
@@ -1673,7 +1163,7 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
     }
     if (RD && nprev >= 0) col2im(nprev, 0, MAXC);  // the last frame's Z (stored before the last Bb)
 #ifdef KCNN_PHASE_TIMING
-    if ((dbg & 16) && blockIdx.x == 0 && lane == 0)
+    if ((flags & kX6Clock) && blockIdx.x == 0 && lane == 0)
       for (int c = 0; c < NCH; ++c)
         printf("bwdx6q wave %d ch %d: PA %lld Ba %lld PB %lld Bb %lld top %lld\n", wave, c,
                tm[5 * c], tm[5 * c + 1], tm[5 * c + 2], tm[5 * c + 3], tm[5 * c + 4]);
@@ -1696,29 +1186,21 @@ __global__ __launch_bounds__(NT, 1) void conv_bwd_x6q_kernel(
         float sum = 0.0f;
 #pragma unroll
         for (int w = 0; w < 4; w++) sum += red[w * 1024 + e];
-        // (dbg bit 30: add to the partial an earlier frame range left there)
-        dst[i * g.G + ch * 32 + j] = (dbg & (1 << 30)) ? dst[i * g.G + ch * 32 + j] + sum : sum;
+        dst[i * g.G + ch * 32 + j] = (flags & kX6Acc) ? dst[i * g.G + ch * 32 + j] + sum : sum;
       }
     }
   };
   if (dgrad_wave) frames(std::integral_constant<int, 1>{});
   else frames(std::integral_constant<int, 2>{});
 #undef KCNN_TMARK
-#undef KCNN_SKIP
 }
 
-size_t x6q_lds(const ConvGeom &g);
-size_t x6p_lds(const ConvGeom &g) {
-  const int CHWp = g.C * (g.H + 2 * g.pad_h) * (g.W + 2 * g.pad_w);
-  return (size_t)3 * YPL + 3 * WPL + (size_t)g.Kdim * PZ * 4 +
-         (size_t)round4(CHWp + 1) * 4 + (size_t)PP * 4;
-}
-
-// conv_bwd_x6q_kernel: x6p's plan and the col2im tap table
-// (and the map's split parts, 8 B per element instead of x6p's 4)
+// conv_bwd_x6q_kernel: the dY and W images, Z, the map's split parts (8 B
+// per element), qtab and the col2im tap table
 size_t x6q_lds(const ConvGeom &g) {
   const int CHWp = g.C * (g.H + 2 * g.pad_h) * (g.W + 2 * g.pad_w);
-  return x6p_lds(g) + (size_t)round4(g.C * g.HW) * 4 + (size_t)round4(CHWp + 1) * 4;
+  return (size_t)3 * YPL + 3 * WPL + (size_t)g.Kdim * PZ * 4 +
+         (size_t)round4(CHWp + 1) * 8 + (size_t)PP * 4 + (size_t)round4(g.C * g.HW) * 4;
 }
 
 size_t x6_lds(const ConvGeom &g, bool dx, int pc, int ph) {
@@ -1748,10 +1230,11 @@ bool kcnn_conv_bwd_x6_eligible(const ConvGeom &g, bool dx, int pc, int ph) {
 // One filter chunk (G <= 128): the workgroup partials ws_part[S][(Kdim+1) G]
 // (gW rows, then the bias row) for kcnn_conv_bwd_frame's reduction, S =
 // gridDim = min(R, 256); dX written (or added, dx_acc) when dX != NULL.
+// part_acc: add to ws_part what an earlier frame range left there.
 int kcnn_conv_bwd_x6(const ConvGeom &g, const float *X, int xs, const float *dY, int dys,
                      const float *K, int ks, float *dX, int dxs, float *ws_part, int S,
                      int dx_acc, hipStream_t st, const unsigned char *pmask, int pms,
-                     int pc, int ph, int dbg) {
+                     int pc, int ph, bool part_acc) {
   const bool dx = dX != nullptr, wg = ws_part != nullptr;
   if (!dx && !wg) return 0;
   if (!kcnn_conv_bwd_x6_eligible(g, dx, pc, ph)) return -1;
@@ -1769,47 +1252,37 @@ int kcnn_conv_bwd_x6(const ConvGeom &g, const float *X, int xs, const float *dY,
     for (int s = 0; s < nstep; ++s) tab.s[4 + s % 4][s / 4] = (uint8_t)s;
   }
   const int ZZ = g.Kdim | 1;
+  const int flags = (part_acc ? kX6Acc : 0) | (phase_timing() ? kX6Clock : 0);
   // the software-pipelined kernel for the pooled backward with both outputs
-  // (bitwise the same results); KCNN_BWD_X6P=0 (experiment build) keeps
-  // conv_bwd_x6_kernel for it too
-  static const int pipelined = KCNN_KNOB("KCNN_BWD_X6P", 2);
-  const size_t plds = pipelined == 1 ? x6p_lds(g) : x6q_lds(g);
-  if (pipelined && dx && wg && pc > 0 && g.G >= 64 && plds <= (size_t)160 * 1024) {
-    const size_t lds = plds;
-#define KCNN_X6PK(KER, NCH, PCM, PH)                                                       \
+  // (bitwise the same results)
+  if (dx && wg && pc > 0 && g.G >= 64 && x6q_lds(g) <= (size_t)160 * 1024) {
+    const size_t lds = x6q_lds(g);
+#define KCNN_X6Q(NCH, PCM, PH)                                                             \
   do {                                                                                     \
-    static bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&KER<NCH, PCM, PH>), \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                           160 * 1024) == hipSuccess;                       \
+    static bool attr =                                                                     \
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bwd_x6q_kernel<NCH, PCM, PH>), \
+                            hipFuncAttributeMaxDynamicSharedMemorySize,                    \
+                            160 * 1024) == hipSuccess;                                     \
     (void)attr;                                                                            \
-    hipLaunchKernelGGL((KER<NCH, PCM, PH>), dim3(S), dim3(NT), lds, st, g, X, xs, dY, dys, K, \
-                       ks, dX, dxs, ws_part, ZZ, tab, dx_acc, pmask, pms, dbg);            \
+    hipLaunchKernelGGL((conv_bwd_x6q_kernel<NCH, PCM, PH>), dim3(S), dim3(NT), lds, st, g, X, \
+                       xs, dY, dys, K, ks, dX, dxs, ws_part, ZZ, tab, dx_acc, pmask, pms,   \
+                       flags);                                                             \
   } while (0)
-#ifdef KCNN_EXPERIMENTS
-#define KCNN_X6PP(NCH, PCM, PH)                                \
-  do {                                                         \
-    if (pipelined == 1) KCNN_X6PK(conv_bwd_x6p_kernel, NCH, PCM, PH); \
-    else KCNN_X6PK(conv_bwd_x6q_kernel, NCH, PCM, PH);         \
-  } while (0)
-#else
-#define KCNN_X6PP(NCH, PCM, PH) KCNN_X6PK(conv_bwd_x6q_kernel, NCH, PCM, PH)
-#endif
-#define KCNN_X6PM(NCH)                                      \
-  do {                                                      \
-    if (pc == 4 && ph == 3) KCNN_X6PP(NCH, 4, 3);           \
-    else if (pc == 4 && ph == 2) KCNN_X6PP(NCH, 4, 2);      \
-    else if (pc == 4) KCNN_X6PP(NCH, 4, 1);                 \
-    else if (pc == 8 && ph == 2) KCNN_X6PP(NCH, 8, 2);      \
-    else KCNN_X6PP(NCH, 8, 1);                              \
+#define KCNN_X6QM(NCH)                                 \
+  do {                                                 \
+    if (pc == 4 && ph == 3) KCNN_X6Q(NCH, 4, 3);       \
+    else if (pc == 4 && ph == 2) KCNN_X6Q(NCH, 4, 2);  \
+    else if (pc == 4) KCNN_X6Q(NCH, 4, 1);             \
+    else if (pc == 8 && ph == 2) KCNN_X6Q(NCH, 8, 2);  \
+    else KCNN_X6Q(NCH, 8, 1);                          \
   } while (0)
     switch (g.G / 32) {
-      case 2: KCNN_X6PM(2); break;
-      case 3: KCNN_X6PM(3); break;
-      default: KCNN_X6PM(4); break;
+      case 2: KCNN_X6QM(2); break;
+      case 3: KCNN_X6QM(3); break;
+      default: KCNN_X6QM(4); break;
     }
-#undef KCNN_X6PM
-#undef KCNN_X6PP
-#undef KCNN_X6PK
+#undef KCNN_X6QM
+#undef KCNN_X6Q
     return (int)hipGetLastError();
   }
   const size_t lds = x6_lds(g, dx, pc, ph);
@@ -1821,7 +1294,7 @@ int kcnn_conv_bwd_x6(const ConvGeom &g, const float *X, int xs, const float *dY,
     (void)attr;                                                                            \
     hipLaunchKernelGGL((conv_bwd_x6_kernel<NCH, DXB, WGB, PCM, PH>), dim3(S), dim3(NT), lds, \
                        st, g, X, xs, dY, dys, K, ks, dX, dxs, ws_part, ZZ, tab, dx_acc,     \
-                       pmask, pms, dbg);                                                   \
+                       pmask, pms, flags);                                                 \
   } while (0)
 #define KCNN_X6M(NCH, DXB, WGB)                                  \
   do {                                                           \

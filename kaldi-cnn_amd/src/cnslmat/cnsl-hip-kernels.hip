@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void maxpool_direct_prop_kernel(
 
 // Direct channel-group backprop (write_all semantics, like the group kernel
 // below): output e routes dP[e] to every input of its window equal to P[e].
-template <int PC, bool NT = false>
+template <int PC>
 __global__ __launch_bounds__(256) void maxpool_direct_backprop_kernel(
     const float *__restrict__ x, int64_t xs, const float *__restrict__ y,
     int64_t ys, const float *__restrict__ dy, int64_t dys,
@@ -442,11 +442,9 @@ __global__ __launch_bounds__(256) void maxpool_direct_backprop_kernel(
     const float *m = x + (int64_t)row * xs + w;
 #pragma unroll
     for (int c = 0; c < PC; c++)
-      v[t][c] = NT ? __builtin_nontemporal_load(m + c * plane) : m[c * plane];
-    pv[t] = NT ? __builtin_nontemporal_load(y + (int64_t)row * ys + j)
-               : y[(int64_t)row * ys + j];
-    dv[t] = NT ? __builtin_nontemporal_load(dy + (int64_t)row * dys + j)
-               : dy[(int64_t)row * dys + j];  // own stride (B14)
+      v[t][c] = m[c * plane];
+    pv[t] = y[(int64_t)row * ys + j];
+    dv[t] = dy[(int64_t)row * dys + j];  // own stride (B14)
     in_off[t] = (int64_t)row * dxs + w;
   }
 #pragma unroll
@@ -454,9 +452,7 @@ __global__ __launch_bounds__(256) void maxpool_direct_backprop_kernel(
     if (!ok[t]) continue;
 #pragma unroll
     for (int c = 0; c < PC; c++) {
-      const float r = v[t][c] == pv[t] ? dv[t] : 0.0f;
-      if (NT) __builtin_nontemporal_store(r, dx + in_off[t] + c * plane);
-      else dx[in_off[t] + c * plane] = r;
+      dx[in_off[t] + c * plane] = v[t][c] == pv[t] ? dv[t] : 0.0f;
     }
   }
 }
@@ -588,8 +584,6 @@ PoolPlane make_pool_plane(int64_t rows, int in_cols, int H, int W, int ph, int p
   return q;
 }
 
-bool env_pool_direct();
-
 // Plane kernels apply to non-overlap windows with ph*pw > 1 whose group of
 // pc maps fits the LDS budget; 16-B copies when the runs are aligned.
 bool pool_plane_ok(int in_cols, int H, int W, int ph, int pw, int pc, int mode,
@@ -598,7 +592,7 @@ bool pool_plane_ok(int in_cols, int H, int W, int ph, int pw, int pc, int mode,
   // nnet.config's 1x2x1 pool has 12-float runs and goes element-wise)
   return mode == 0 && (ph > 1 || pw > 1) && H % ph == 0 && W % pw == 0 && pc * H * W >= 256 &&
          in_cols % (pc * H * W) == 0 && (size_t)(pc * H * W + 2 * (H / ph) * (W / pw)) * 4 <= 32768 &&
-         rows * (in_cols / (pc * H * W)) < ((int64_t)1 << 31) && env_pool_direct();
+         rows * (in_cols / (pc * H * W)) < ((int64_t)1 << 31);
 }
 
 unsigned plane_grid(int units) { return (unsigned)(units < 256 * 24 ? units : 256 * 24); }
@@ -772,60 +766,9 @@ __global__ __launch_bounds__(256) void maxpool_overlap2d_backprop_kernel(
   }
 }
 
-// Backprop of a 3-D window pool from the fused forward's 16-bit mask: a
-// thread takes 4 consecutive inputs (16-B store), each one's window j and bit
-// b = (c % pc)*pw*ph + (w % pw)*ph + (h % ph); dX = bit ? dP[j] : 0.
-__global__ __launch_bounds__(256) void maxpool_mask3d_backprop_kernel(
-    const unsigned short *__restrict__ mask, int64_t ms, const float *__restrict__ dy,
-    int64_t dys, float *__restrict__ dx, int64_t dxs, uint32_t total4, FastDiv div_cols4,
-    FastDiv div_plane, FastDiv div_h, FastDiv div_ph, FastDiv div_pw, FastDiv div_pc,
-    int H, int W, int outplane, int outh) {
-  const uint32_t base = blockIdx.x * (256u * kPoolWinVec) + threadIdx.x;
-  float res[kPoolWinVec][4];
-  int64_t off[kPoolWinVec];
-#pragma unroll
-  for (int t = 0; t < kPoolWinVec; t++) {
-    const uint32_t e0 = base + 256u * t;
-    const uint32_t e = e0 < total4 ? e0 : total4 - 1;
-    uint32_t row, q4, c, rem, w, h;
-    div_cols4.divmod(e, row, q4);
-    const uint32_t col = 4 * q4;
-    div_plane.divmod(col, c, rem);
-    div_h.divmod(rem, w, h);
-    const unsigned short *mr = mask + (int64_t)row * ms;
-    const float *dr = dy + (int64_t)row * dys;
-    // window coordinates once, then stepped with the element (h fastest)
-    uint32_t jc, bc, jw, bw, jh, bh;
-    div_pc.divmod(c, jc, bc);
-    div_pw.divmod(w, jw, bw);
-    div_ph.divmod(h, jh, bh);
-    const uint32_t ph = div_ph.d, pw = div_pw.d, pc = div_pc.d;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t j = jc * (uint32_t)outplane + jw * (uint32_t)outh + jh;
-      const uint32_t bit = (bc * pw + bw) * ph + bh;
-      res[t][k] = (mr[j] >> bit) & 1u ? dr[j] : 0.0f;
-      if (++bh == ph) { bh = 0; ++jh; }
-      if (++h == (uint32_t)H) {
-        h = 0; bh = 0; jh = 0;
-        if (++bw == pw) { bw = 0; ++jw; }
-        if (++w == (uint32_t)W) {
-          w = 0; bw = 0; jw = 0;
-          if (++bc == pc) { bc = 0; ++jc; }
-        }
-      }
-    }
-    off[t] = (int64_t)row * dxs + col;
-  }
-#pragma unroll
-  for (int t = 0; t < kPoolWinVec; t++) {
-    if (base + 256u * t >= total4) continue;
-    *reinterpret_cast<float4 *>(dx + off[t]) =
-        make_float4(res[t][0], res[t][1], res[t][2], res[t][3]);
-  }
-}
-
-// Scatter form of the same: a thread owns one pooled value (window) and
+// Backprop of a 3-D window pool from the fused forward's 16-bit mask: bit
+// b = (c % pc)*pw*ph + (w % pw)*ph + (h % ph) of window j's mask routes dP[j]
+// to that input, dX = bit ? dP[j] : 0.  A thread owns one pooled value (window) and
 // writes its ph*pw*pc inputs (pc runs of pw runs of ph consecutive floats;
 // the runs of neighbouring lanes tile each map column).  The window index is
 // computed once per window instead of once per input.
@@ -938,12 +881,6 @@ __global__ __launch_bounds__(256) void maxpool_group_backprop_kernel(
     }
     __syncthreads();
   }
-}
-
-// KCNN_POOL_DIRECT=0 selects the LDS-staged group forward (A/B measurements).
-bool env_pool_direct() {
-  static const int v = KCNN_KNOB("KCNN_POOL_DIRECT", 1);
-  return v != 0;
 }
 
 // The group kernels apply when the pool is channel-only and every group of
@@ -1109,35 +1046,19 @@ int hipF_maxpool_backprop_mask3d(const unsigned short *mask, int mask_stride,
     return (int)hipErrorInvalidValue;
   const int outh = in_height / ph;
   const int outplane = outh * (in_width / pw);
-  static const int scatter = KCNN_KNOB("KCNN_MASK3D_SCATTER", 1);
-  if (scatter) {
-    const int64_t nout = (int64_t)out_deriv_dim.rows * out_deriv_dim.cols;
-    if (nout == 0) return 0;
-    if (nout >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-    auto kern = maxpool_mask3d_scatter_kernel<0, 0, 0>;
-    if (ph == 3 && pw == 1 && pc == 4) kern = maxpool_mask3d_scatter_kernel<3, 1, 4>;
-    else if (ph == 2 && pw == 1 && pc == 4) kern = maxpool_mask3d_scatter_kernel<2, 1, 4>;
-    else if (ph == 2 && pw == 2 && pc == 2) kern = maxpool_mask3d_scatter_kernel<2, 2, 2>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0,
-                       kcnn::as_stream(stream), mask, (int64_t)mask_stride, out_deriv,
-                       (int64_t)out_deriv_dim.stride, in_deriv, (int64_t)in_deriv_dim.stride,
-                       (uint32_t)nout, FastDiv((uint32_t)out_deriv_dim.cols),
-                       FastDiv((uint32_t)outplane), FastDiv((uint32_t)outh), in_height, plane,
-                       ph, pw, pc);
-    return kcnn::launch_status();
-  }
-  const int64_t n4 = (int64_t)in_deriv_dim.rows * in_deriv_dim.cols / 4;
-  if (n4 == 0) return 0;
-  if (n4 >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  const uint32_t total4 = (uint32_t)n4;
-  const unsigned blocks = (total4 + 256 * kPoolWinVec - 1) / (256 * kPoolWinVec);
-  hipLaunchKernelGGL(maxpool_mask3d_backprop_kernel, dim3(blocks), dim3(256), 0,
+  const int64_t nout = (int64_t)out_deriv_dim.rows * out_deriv_dim.cols;
+  if (nout == 0) return 0;
+  if (nout >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+  auto kern = maxpool_mask3d_scatter_kernel<0, 0, 0>;
+  if (ph == 3 && pw == 1 && pc == 4) kern = maxpool_mask3d_scatter_kernel<3, 1, 4>;
+  else if (ph == 2 && pw == 1 && pc == 4) kern = maxpool_mask3d_scatter_kernel<2, 1, 4>;
+  else if (ph == 2 && pw == 2 && pc == 2) kern = maxpool_mask3d_scatter_kernel<2, 2, 2>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0,
                      kcnn::as_stream(stream), mask, (int64_t)mask_stride, out_deriv,
                      (int64_t)out_deriv_dim.stride, in_deriv, (int64_t)in_deriv_dim.stride,
-                     total4, FastDiv((uint32_t)(in_deriv_dim.cols / 4)),
-                     FastDiv((uint32_t)plane), FastDiv((uint32_t)in_height),
-                     FastDiv((uint32_t)ph), FastDiv((uint32_t)pw), FastDiv((uint32_t)pc),
-                     in_height, in_width, outplane, outh);
+                     (uint32_t)nout, FastDiv((uint32_t)out_deriv_dim.cols),
+                     FastDiv((uint32_t)outplane), FastDiv((uint32_t)outh), in_height, plane,
+                     ph, pw, pc);
   return kcnn::launch_status();
 }
 
@@ -1193,14 +1114,10 @@ int hipF_copy_rows_at(const float *src, MatrixDim src_dim, float *dest,
   return launch_elem2d(src_dim.rows, src_dim.cols, f, kcnn::as_stream(stream));
 }
 
-// Streaming (nontemporal) loads and stores in the direct pool kernels.
-// KCNN_POOL_NT: bit 1 forward (default on: Y read once, P written once; c2
-// in the unfused step 225 -> 177-197 us, 52.8 % -> 60-67 % of HBM), bit 0
-// backprop (default off: 355 -> 461 us measured).
-static int pool_nt() {
-  static const int v = KCNN_KNOB("KCNN_POOL_NT", 2);
-  return v;
-}
+// Streaming (nontemporal) loads and stores in the direct pool kernels: the
+// forward of 4-channel windows has them (Y read once, P written once; c2 in
+// the unfused step 225 -> 177-197 us, 52.8 % -> 60-67 % of HBM), the backprop
+// does not (355 -> 461 us measured with them).
 
 int hipF_maxpool_prop(const float *src, MatrixDim src_dim, float *pool,
                       MatrixDim pool_dim, int in_height, int in_width,
@@ -1211,14 +1128,11 @@ int hipF_maxpool_prop(const float *src, MatrixDim src_dim, float *pool,
   const int64_t nout = (int64_t)pool_dim.rows * pool_dim.cols;
   if (mode == 0 && pool_height_dim == 1 && pool_width_dim == 1 &&
       pool_channel_dim >= 2 && pool_channel_dim <= 4 && pool_dim.cols % plane == 0 &&
-      src_dim.cols == pool_dim.cols * pool_channel_dim && nout < ((int64_t)1 << 31) &&
-      env_pool_direct()) {
+      src_dim.cols == pool_dim.cols * pool_channel_dim && nout < ((int64_t)1 << 31)) {
     if (nout == 0) return 0;
     const unsigned blocks =
         (unsigned)((nout + 256 * kPoolDirectOut - 1) / (256 * kPoolDirectOut));
-    static const int nt = pool_nt();
-    auto kern = pool_channel_dim == 4   ? (nt >= 2 ? maxpool_direct_prop_kernel<4, true>
-                                              : maxpool_direct_prop_kernel<4>)
+    auto kern = pool_channel_dim == 4   ? maxpool_direct_prop_kernel<4, true>
                 : pool_channel_dim == 3 ? maxpool_direct_prop_kernel<3>
                                         : maxpool_direct_prop_kernel<2>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, kcnn::as_stream(stream),
@@ -1254,7 +1168,7 @@ int hipF_maxpool_prop(const float *src, MatrixDim src_dim, float *pool,
                        (int64_t)pool_dim.stride, pg);
     return kcnn::launch_status();
   }
-  if (mode != 0 && pool_channel_dim >= 2 && pool_channel_dim <= 4 && env_pool_direct()) {
+  if (mode != 0 && pool_channel_dim >= 2 && pool_channel_dim <= 4) {
     if (pool_dim.rows == 0 || plane == 0) return 0;
     const int C = src_dim.cols / plane;
     hipStream_t st = kcnn::as_stream(stream);
@@ -1304,13 +1218,11 @@ int hipF_maxpool_backprop(const float *in_val, MatrixDim in_val_dim,
   if (write_all && mode == 0 && pool_height_dim == 1 && pool_width_dim == 1 &&
       pool_channel_dim >= 2 && pool_channel_dim <= 4 && out_val_dim.cols % plane0 == 0 &&
       in_val_dim.cols == out_val_dim.cols * pool_channel_dim &&
-      nout < ((int64_t)1 << 31) && env_pool_direct()) {
+      nout < ((int64_t)1 << 31)) {
     if (nout == 0) return 0;
     const unsigned blocks =
         (unsigned)((nout + 256 * kPoolDirectOut - 1) / (256 * kPoolDirectOut));
-    static const int nt = pool_nt();
-    auto kern = pool_channel_dim == 4   ? (nt == 1 || nt == 3 ? maxpool_direct_backprop_kernel<4, true>
-                                                              : maxpool_direct_backprop_kernel<4>)
+    auto kern = pool_channel_dim == 4   ? maxpool_direct_backprop_kernel<4>
                 : pool_channel_dim == 3 ? maxpool_direct_backprop_kernel<3>
                                         : maxpool_direct_backprop_kernel<2>;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, in_val, (int64_t)in_val_dim.stride, out_val,
@@ -1326,7 +1238,7 @@ int hipF_maxpool_backprop(const float *in_val, MatrixDim in_val_dim,
       (uintptr_t)dest % 16 == 0 && in_height % pool_height_dim == 0 &&
       in_width % pool_width_dim == 0 &&
       in_val_dim.cols == out_val_dim.cols * pool_height_dim * pool_width_dim * pool_channel_dim &&
-      (int64_t)in_val_dim.rows * in_val_dim.cols < ((int64_t)1 << 33) && env_pool_direct()) {
+      (int64_t)in_val_dim.rows * in_val_dim.cols < ((int64_t)1 << 33)) {
     const uint32_t total4 = (uint32_t)((int64_t)in_val_dim.rows * in_val_dim.cols / 4);
     if (total4 == 0) return 0;
     const int outh = in_height / pool_height_dim;
@@ -1374,7 +1286,7 @@ int hipF_maxpool_backprop(const float *in_val, MatrixDim in_val_dim,
   PoolGeom g = make_pool_geom(in_height, in_width, 1, 1, pool_channel_dim,
                               mode, out_val_dim.cols);
   const int plane = in_height * in_width;
-  if (pool_channel_dim >= 2 && pool_channel_dim <= 4 && plane > 0 && env_pool_direct()) {
+  if (pool_channel_dim >= 2 && pool_channel_dim <= 4 && plane > 0) {
     const int C = in_val_dim.cols / plane;
     if (in_val_dim.rows == 0) return 0;
     if (mode == 1 && out_val_dim.cols == (C - pool_channel_dim + 1) * plane &&

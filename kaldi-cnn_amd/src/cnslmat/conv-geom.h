@@ -77,12 +77,13 @@ int kcnn_conv_bwd_frame(const kcnn::ConvGeom &g, const float *X, int xs,
                         const unsigned char *pmask = nullptr, int pms = 0,
                         int pc = 0, int ph = 1);
 // The same fused backward on the bf16 MFMAs with exact three-way operand
-// splits (cnsl-conv-x6.hip); ws_part == NULL runs the data gradient only.
+// splits (cnsl-conv-x6.hip); ws_part == NULL runs the data gradient only,
+// part_acc adds to ws_part what an earlier frame range left there.
 bool kcnn_conv_bwd_x6_eligible(const kcnn::ConvGeom &g, bool dx, int pc, int ph = 1);
 int kcnn_conv_bwd_x6(const kcnn::ConvGeom &g, const float *X, int xs, const float *dY,
                      int dys, const float *K, int ks, float *dX, int dxs, float *ws_part,
                      int S, int dx_acc, hipStream_t st, const unsigned char *pmask,
-                     int pms, int pc, int ph, int dbg = 0);
+                     int pms, int pc, int ph, bool part_acc = false);
 // Conv2D(concat) + bias (+ ReLU when relu) as an implicit GEMM on the f16
 // (f16x3, igemm_x6 family 2 / 3) or bf16 (bf16x6) MFMAs
 // (cnsl-conv-igemm-x6.hip); -1 when the shape is outside its limits.

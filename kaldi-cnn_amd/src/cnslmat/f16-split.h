@@ -100,26 +100,12 @@ __device__ __forceinline__ float opaque_m1() {
   asm volatile("" : "+s"(v));
   return v;
 }
-#ifdef KCNN_F16_ASM  // experiment build: r04's inline asm form, for the hazard study
-__device__ __forceinline__ float sub_h0(float a, uint32_t h, float) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(a), "v"(h));
-  return r;
-}
-__device__ __forceinline__ float sub_h1(float a, uint32_t h, float) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r)
-      : "v"(a), "v"(h));
-  return r;
-}
-#else
 __device__ __forceinline__ float sub_h0(float a, uint32_t h, float m1) {
   return __builtin_fmaf((float)__builtin_bit_cast(f16x2, h)[0], m1, a);
 }
 __device__ __forceinline__ float sub_h1(float a, uint32_t h, float m1) {
   return __builtin_fmaf((float)__builtin_bit_cast(f16x2, h)[1], m1, a);
 }
-#endif
 // (x0 * 2^e0, x1 * 2^e1) -> packed f16 pairs hi, lo: 6 VALU
 __device__ __forceinline__ void split2h(float x0, float x1, int e0, int e1, uint32_t &h,
                                         uint32_t &l, float m1) {

@@ -103,7 +103,6 @@ struct GemmF16Args {
   int M, N, K, lda, ldb, ldc;
   int bvec;                      // bmax, bcnt 16-B aligned and N % 4 == 0 (the reduce's loads)
   MomentumEpi mom;               // mom.W: C is a weight gradient applied in the store (emit)
-  int dbg;                       // KCNN_EXPERIMENTS builds: A/B switches
   int kps, ksplit, tiles_m, tiles_n;
   int nwhole;                    // ksplit > 1: the first nwhole tiles (a multiple of 256) whole
   int fix_local;                 // ksplit > 1: no fix-up launch; the reduce recomputes every rejection
@@ -118,22 +117,20 @@ struct GemmF16Args {
 // panels of op(B) in that XCD's L2, instead of one row panel and 32 column
 // panels (c2's data gradient: an XCD wave then reads 8 MB of operand panels
 // instead of 17)
-#ifndef KCNN_GEMM_GM
-#define KCNN_GEMM_GM 4
-#endif
+constexpr int GM = 4;
 __device__ __forceinline__ void tile_rc(const GemmF16Args &p, int t, int &tm, int &tn) {
-  const int gsz = KCNN_GEMM_GM * p.tiles_n;
+  const int gsz = GM * p.tiles_n;
   const int g = t / gsz, r = t - g * gsz;
-  const int m0 = g * KCNN_GEMM_GM;
-  const int gm = min(p.tiles_m - m0, KCNN_GEMM_GM);
+  const int m0 = g * GM;
+  const int gm = min(p.tiles_m - m0, GM);
   tm = m0 + r % gm;
   tn = r / gm;
 }
 // ... and back: the order's index of tile (tm, tn)
 __device__ __forceinline__ int tile_index(const GemmF16Args &p, int tm, int tn) {
-  const int g = tm / KCNN_GEMM_GM, m0 = g * KCNN_GEMM_GM;
-  const int gm = min(p.tiles_m - m0, KCNN_GEMM_GM);
-  return g * KCNN_GEMM_GM * p.tiles_n + tn * gm + (tm - m0);
+  const int g = tm / GM, m0 = g * GM;
+  const int gm = min(p.tiles_m - m0, GM);
+  return g * GM * p.tiles_n + tn * gm + (tm - m0);
 }
 // This workgroup's (split, tile row, tile column); true for a whole tile.
 // Blocks [0, nwhole) take tiles [0, nwhole) over all of K, the others the
@@ -163,7 +160,7 @@ __device__ __forceinline__ int swz(int r, int c) {
 }
 // offset of (k, col) in a [k][R] image of 16-bit values, 16-B chunks XOR-
 // swizzled by (k & 3) << 2 so the four k-rows of one transposed read hit
-// four disjoint 16-bank groups (cu-gemm-x6.hip's fast kernel)
+// four disjoint 16-bank groups (as cu-gemm-x6.hip's tswz)
 template <int R>
 __device__ __forceinline__ int tswz(int k, int col) {
   return k * (R * 2) + ((((col >> 3) ^ ((k & 3) << 2))) << 4) + ((col & 7) << 1);
@@ -328,12 +325,7 @@ struct Loader {
         asm volatile("");  // a branch: not per-element selects in every K step
         if (kq * KPT + j >= kv) x0 = x1 = 0.0f;
       }
-#ifdef KCNN_GEMM_XNOSPLIT
-      ph[hf] = __float_as_uint(x0);
-      pl[hf] = __float_as_uint(x1);
-#else
       split2h(x0, x1, e[2 * hf], e[2 * hf + 1], ph[hf], pl[hf], m1);
-#endif
       if (hf == 1) {
         const int o = tswz<R>(kq * KPT + j, 4 * rq);
         *reinterpret_cast<uint2 *>(lds + o) = make_uint2(ph[0], ph[1]);
@@ -359,12 +351,7 @@ struct Loader {
         if (kb + 2 * q >= kv) x0 = 0.0f;
         if (kb + 2 * q + 1 >= kv) x1 = 0.0f;
       }
-#ifdef KCNN_GEMM_XNOSPLIT  // experiment build: timing without the split
-      ph[q & 3] = __float_as_uint(x0);
-      pl[q & 3] = __float_as_uint(x1);
-#else
       split2h(x0, x1, e[u], e[u], ph[q & 3], pl[q & 3], m1);
-#endif
       if ((q & 3) == 3) {
         const int off = swz(r, c0 + (q >> 2));
         *reinterpret_cast<uint4 *>(lds + off) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
@@ -402,16 +389,6 @@ struct Loader {
 // whole block).
 __device__ __forceinline__ int tile_scales(const GemmF16Args &p, int *sexp, float *sw, int row0,
                                            int col0, int tid) {
-#ifdef KCNN_EXPERIMENTS  // KCNN_GEMM_DEBUG & 4: no statistics loads (scale 0; timing only)
-  if (p.dbg & 64) {
-    for (int i = tid; i < BM + BN; i += NT) {
-      sexp[i] = 0;
-      sw[i] = 0.0f;
-    }
-    __syncthreads();
-    return 0;
-  }
-#endif
   int skip = 0, spr = 0;
   for (int i = tid; i < BM + BN; i += NT) {
     int s = 0;
@@ -576,11 +553,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
   // second store_value after the staged store read back the new C).
   // (the momentum update's W and prev have 16-B aligned rows: host check)
   const bool staged = row0 + BM <= p.M && col0 + BN <= p.N && !skip &&
-                      (partial || p.mom.W || ((ldo & 3) | ((uintptr_t)slab & 15)) == 0)
-#ifdef KCNN_EXPERIMENTS  // KCNN_GEMM_DEBUG & 8: the per-register stores only
-                      && !(p.dbg & 128)
-#endif
-      ;
+                      (partial || p.mom.W || ((ldo & 3) | ((uintptr_t)slab & 15)) == 0);
   if (staged) {
     __syncthreads();  // every wave past its last read of the plane buffers
     constexpr int SR = 68;  // staging row pitch (floats): 16-B rows, rows 4 apart on other banks
@@ -691,14 +664,6 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
           }
         }
         const float v = __builtin_amdgcn_ldexpf(acc[i][j][g], -(er + ec));
-#ifdef KCNN_EXPERIMENTS  // KCNN_GEMM_DEBUG & 1: no stores, & 2: nontemporal stores
-        if (p.dbg & 16) continue;
-        if (p.dbg & 32) {
-          float *o = partial ? slab + (int64_t)row * ldo + col : p.C + (int64_t)row * p.ldc + col;
-          __builtin_nontemporal_store(partial ? v : store_value(p, v, o, col), o);
-          continue;
-        }
-#endif
         if (partial) slab[(int64_t)row * ldo + col] = v;
         else emit(p, row, col, v);
       }
@@ -922,20 +887,14 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
   auto mfma_n = [&](int n, const f16x8 (&fa)[2][2], const f16x8 (&fb)[2][2]) {
     const int i = n / 6, j = (n / 3) & 1, pr = n % 3;
     constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-#ifdef KCNN_GEMM_XNOMFMA  // experiment build: timing without the products
-    asm volatile("" ::"v"(fa[i][PA[pr]]), "v"(fb[j][PB[pr]]));
-#else
     acc[i][j] = mfma(fa[i][PA[pr]], fb[j][PB[pr]], acc[i][j]);
-#endif
   };
 
   // waves 4-7 (each SIMD's second wave) at priority 1 for the whole kernel
   // (MI355X_MICROARCH.md, two waves per SIMD, item 4: the younger half loses
   // every VALU arbitration otherwise)
-#ifndef KCNN_GEMM_PRIO
-#define KCNN_GEMM_PRIO 1
-#endif
-  if (KCNN_GEMM_PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
+  constexpr int PRIO = 1;
+  if (PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
   // the first two K tiles' loads go out before the tile's scales are read
   // (the split needs both; the scales' loads and barriers then pass under
   // the tiles' latency: c2's data gradient 400 -> 381 us at K 1024 without
@@ -991,10 +950,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
 #pragma unroll
       for (int n = 0; n < 12; ++n) {
         mfma_n(n, fa1, fb1);
-#ifndef KCNN_GEMM_XNOLOAD  // experiment build: timing without the main loop's loads
         if (n == 1) lan.load(rsA, p.lda, vra, kk(t + 3, A_KC), tid);
         if (n == 3) lbn.load(rsB, p.ldb, vrb, kk(t + 3, B_KC), tid);
-#endif
         if (more && n >= 2 && n < 10) read_frag(nbuf, 0, n - 2, fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1478,13 +1435,9 @@ __device__ __forceinline__ uint32_t reduce_quad(const GemmF16Args &p, int64_t e,
   }
   if (ar >= NONFINITE) return 0;
   const float sv[4] = {v.x, v.y, v.z, v.w};
-#ifdef KCNN_EXPERIMENTS  // A/B: KCNN_RED_DEBUG & 1 drops the spread check
-  const bool any = !(p.dbg & 1) && (cr | cc[0] | cc[1] | cc[2] | cc[3]) != 0 && ar != 0;
-#else
   // the counts are 0 unless a group is spread, so one test skips the check
   // (an all-zero row: its products are exactly 0, no check)
   const bool any = (cr | cc[0] | cc[1] | cc[2] | cc[3]) != 0 && ar != 0;
-#endif
   float *o = p.C + (int64_t)r * p.ldc + c;
   const bool fin = max(max(bm[0], bm[1]), max(bm[2], bm[3])) < NONFINITE;
   if (p.mom.W && !any && fin) {  // the fused momentum update, 16-B (host: aligned)
@@ -1714,33 +1667,30 @@ int choose_ksplit(int64_t tiles, int M, int N, int K, int *nwhole = nullptr) {
   return best;
 }
 
-// KCNN_F16X3_FAST (experiment build): 1 (default) the one-barrier fast
-// kernel where no operand is LR, 0 the two-phase kernel (bitwise the same C)
+// the one-barrier fast kernel where no operand is LR (an LR operand's 16
+// loaded values per thread and K step spill there), else the two-phase
+// kernel (bitwise the same C)
 template <int AM, int BMODE, bool RAG>
 void launch_t(const GemmF16Args &a, unsigned blocks, hipStream_t st) {
-  static const int fast = KCNN_KNOB("KCNN_F16X3_FAST", 1);
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_f16x3_kernel<AM, BMODE, RAG>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  // (an LR operand's 16 loaded values per thread and K step spill there)
   if constexpr (AM != LR && BMODE != LR) {
-    static bool fattr = [] {
+    static bool attr = [] {
       return hipFuncSetAttribute(
                  reinterpret_cast<const void *>(&gemm_f16x3_fast_kernel<AM, BMODE, RAG>),
                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
     }();
-    (void)fattr;
-    if (fast) {
-      hipLaunchKernelGGL((gemm_f16x3_fast_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT),
-                         LDS_BYTES, st, a);
-      return;
-    }
+    (void)attr;
+    hipLaunchKernelGGL((gemm_f16x3_fast_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT),
+                       LDS_BYTES, st, a);
+  } else {
+    static bool attr = [] {
+      return hipFuncSetAttribute(
+                 reinterpret_cast<const void *>(&gemm_f16x3_kernel<AM, BMODE, RAG>),
+                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
+    }();
+    (void)attr;
+    hipLaunchKernelGGL((gemm_f16x3_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT), LDS_BYTES,
+                       st, a);
   }
-  hipLaunchKernelGGL((gemm_f16x3_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT), LDS_BYTES, st,
-                     a);
 }
 template <bool RAG>
 void launch_r(int am, int bm, const GemmF16Args &a, unsigned blocks, hipStream_t st) {
@@ -1928,9 +1878,6 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   a.bmin = bmax + N;
   a.bcnt = bmax + 2 * (size_t)N;
   a.bvec = N % 4 == 0 && (uintptr_t)a.bmax % 16 == 0 && (uintptr_t)a.bcnt % 16 == 0;
-  static const int red_dbg = KCNN_KNOB("KCNN_RED_DEBUG", 0);
-  static const int gemm_dbg = KCNN_KNOB("KCNN_GEMM_DEBUG", 0);
-  a.dbg = red_dbg | gemm_dbg << 4;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.alpha = alpha; a.beta = beta;
   a.tiles_m = (M + BM - 1) / BM;
@@ -1938,13 +1885,6 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
   int nwhole = 0;
   int s = choose_ksplit(tiles, M, N, K, &nwhole);
-#ifdef KCNN_EXPERIMENTS  // A/B: KCNN_F16X3_KSPLIT forces the split count (0: chosen), no whole tiles;
-                         // KCNN_F16X3_NOWHOLE keeps the chosen count without whole tiles
-  static const int ks_force = KCNN_KNOB("KCNN_F16X3_KSPLIT", 0);
-  static const int no_whole = KCNN_KNOB("KCNN_F16X3_NOWHOLE", 0);
-  if (ks_force > 0) s = std::min(ks_force, 4);
-  if (ks_force > 0 || no_whole) nwhole = 0;
-#endif
   const size_t need = s > 1 ? slab_bytes(s, M, N) + flag_bytes(M, N) : 0;
   if (need > ws_bytes || !ws) s = 1;
   if (s > 1) {
@@ -1974,8 +1914,7 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   // row's padded quad)
   auto mode = [](bool kc, const float *ptr, int ld) {
     if (kc) return (int)LK;
-    static const int tr = KCNN_KNOB("KCNN_F16X3_TR", 1);
-    return tr && ld % 4 == 0 && (uintptr_t)ptr % 16 == 0 ? (int)LT : (int)LR;
+    return ld % 4 == 0 && (uintptr_t)ptr % 16 == 0 ? (int)LT : (int)LR;
   };
   bool fix_launch = true;
   if (s > 1) {

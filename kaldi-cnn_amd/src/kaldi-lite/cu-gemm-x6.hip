@@ -167,7 +167,7 @@ __device__ __forceinline__ f32x16 mfma(const bf16x8 &a, const bf16x8 &b, const f
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-template <bool A_KC, bool B_KC, bool STG>
+template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(NT, 1) void gemm_x6_kernel(GemmX6Args p) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
@@ -242,10 +242,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_x6_kernel(GemmX6Args p) {
     la.template store<A_PLANE>(nA, tid);
     lb.template store<B_PLANE>(nA + 3 * A_PLANE, tid);
   };
-  // STG: waves 4-7 split the next step's operands between their two MFMA
-  // halves, waves 0-3 after both, so the two waves of a SIMD (w, w + 4)
-  // alternate their vector and matrix phases
-  const bool late = !STG || wave < 4;
+  // waves 4-7 split the next step's operands between their two MFMA halves,
+  // waves 0-3 after both, so the two waves of a SIMD (w, w + 4) alternate
+  // their vector and matrix phases (c2 FC GEMMs 1.655 -> 1.636 ms)
+  const bool late = wave < 4;
   for (int t = 0; t < T; ++t) {
     const char *buf = lds + (t & 1) * BUF;
     half_step(buf, 0);
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_x6_kernel(GemmX6Args p) {
 // path issues the same loads and the compiler's vmcnt wait before a split
 // counts exactly the later tile's loads instead of waiting for all of them.
 // Needs whole BK steps (K % BK == 0) and the workgroup's offsets below 2^31
-// (the host checks, as for the fast kernel).
+// (the host checks).
 template <int R, bool KC>
 struct TileLoaderD {
   static constexpr int KPT = KC ? 8 : R * BK / NT;
@@ -358,8 +358,9 @@ struct TileLoaderD {
   }
 };
 
-template <bool A_KC, bool B_KC, int DEPTH>
+template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(NT, 1) void gemm_x6d_kernel(GemmX6Args p) {
+  constexpr int DEPTH = 2;  // prefetch depth, in K steps
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -532,23 +533,14 @@ __global__ void gemm_x6_reduce_scalar_kernel(const float *__restrict__ part, int
 }
 
 // ---------------------------------------------------------------------------
-// Fast path (K and every split a multiple of BK, 16-B aligned operands,
-// M and N multiples of 4 on a row-contiguous side): one basic block per K
-// step, so the split of tile t+1 and the HBM loads of tile t+2 are placed
-// between the bf16 MFMAs of tile t by the scheduler (sched_group_barrier)
-// instead of running as separate VALU phases that the MFMA pipe waits out.
-//  - Loads are raw buffer loads; a row past M gets an offset past the
-//    buffer's range and reads 0, so there is no branch in the step.
-//  - A K-contiguous operand keeps the [row][k] image (64-B rows) read by
-//    ds_read_b128.  A row-contiguous one ([k][row] in memory: op(A) = A^T
-//    or B not transposed) is loaded as float4 along the rows, split, and
-//    written as a [k][row] image; the MFMA fragment comes from it by
-//    ds_read_b64_tr_b16 (lane 4q + p of each 16-lane group addresses k-row q,
-//    columns 4p..4p+3; lane i gets column i of the 4 rows).  16-B chunks are
-//    XOR-swizzled by (k & 3) << 2, so the four k-rows of one transposed read
-//    hit four disjoint 16-bank groups.
+// LDS images of the plane GEMM below.  A K-contiguous operand keeps the
+// [row][k] image (64-B rows, swz) read by ds_read_b128.  A row-contiguous one
+// ([k][row] in memory: op(A) = A^T or B not transposed) has a [k][row] image;
+// the MFMA fragment comes from it by ds_read_b64_tr_b16 (lane 4q + p of each
+// 16-lane group addresses k-row q, columns 4p..4p+3; lane i gets column i of
+// the 4 rows).  16-B chunks are XOR-swizzled by (k & 3) << 2, so the four
+// k-rows of one transposed read hit four disjoint 16-bank groups.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // offset of (k, col) in a [k][R] transposed image, 16-B chunks swizzled
@@ -556,114 +548,6 @@ template <int R>
 __device__ __forceinline__ int tswz(int k, int col) {
   return k * (R * 2) + ((((col >> 3) ^ ((k & 3) << 2))) << 4) + ((col & 7) << 1);
 }
-
-template <int R, bool KC>
-struct FastLoader {
-  // KC: unit = (row, 8 consecutive k); !KC: unit = (4 consecutive rows, KQ k)
-  static constexpr int KQ = KC ? 8 : R * BK / (NT * 4);
-  static constexpr int UPT = KC ? R * 4 / NT : 1;
-  static_assert(KC ? (R * 4) % NT == 0 : (R / 4) * (BK / KQ) == NT, "tile shape");
-  u32x4 v[UPT][KC ? 2 : KQ];
-  int off[UPT];   // byte offset of the unit at k = 0 of the split (or OOB)
-  int kstride;    // bytes per k step of one unit (KC: 4; !KC: ld * 4)
-
-  __device__ __forceinline__ void init(int ld, int row0, int rows, int tid) {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int unit = tid + u * NT;
-      if constexpr (KC) {
-        const int r = unit >> 2, c = unit & 3;
-        off[u] = row0 + r < rows ? r * ld * 4 + c * 32 : (int)0x80000000;
-      } else {
-        const int rq = unit % (R / 4), kq = unit / (R / 4);
-        off[u] = row0 + 4 * rq < rows ? kq * KQ * ld * 4 + rq * 16 : (int)0x80000000;
-      }
-    }
-    kstride = KC ? 4 : ld * 4;
-  }
-  // tile at k offset kk (relative to the split's first k)
-  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rs, int kk) {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      if constexpr (KC) {
-        v[u][0] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[u], kk * 4, 0);
-        v[u][1] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[u] + 16, kk * 4, 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < KQ; ++j)
-          v[u][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[u] + j * kstride,
-                                                          kk * kstride, 0);
-      }
-    }
-  }
-  // the split in NPIECE pieces of one split2 each (interleaved with MFMAs);
-  // a unit's three plane writes go with its last piece
-  static constexpr int NPIECE = KC ? UPT * 4 : KQ * 2;
-  // ph / pm / pl: the caller's temporaries for one unit's pieces
-  template <int PL>
-  __device__ __forceinline__ void piece(char *lds, int tid, int pc, uint32_t (&ph)[4],
-                                        uint32_t (&pm)[4], uint32_t (&pl)[4]) const {
-    if constexpr (KC) {
-      const int u = pc >> 2, i = pc & 3;
-      const u32x4 &s = v[u][i >> 1];
-      split2(__uint_as_float(s[2 * (i & 1)]), __uint_as_float(s[2 * (i & 1) + 1]),
-             ph[i], pm[i], pl[i]);
-      if (i == 3) {
-        const int unit = tid + u * NT;
-        const int o = swz(unit >> 2, unit & 3);
-        *reinterpret_cast<uint4 *>(lds + o) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-        *reinterpret_cast<uint4 *>(lds + PL + o) = make_uint4(pm[0], pm[1], pm[2], pm[3]);
-        *reinterpret_cast<uint4 *>(lds + 2 * PL + o) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-      }
-    } else {
-      const int j = pc >> 1, hf = pc & 1;
-      const u32x4 &s = v[0][j];
-      split2(__uint_as_float(s[2 * hf]), __uint_as_float(s[2 * hf + 1]), ph[hf], pm[hf],
-             pl[hf]);
-      if (hf == 1) {
-        const int rq = tid % (R / 4), kq = tid / (R / 4);
-        const int o = tswz<R>(kq * KQ + j, 4 * rq);
-        *reinterpret_cast<uint2 *>(lds + o) = make_uint2(ph[0], ph[1]);
-        *reinterpret_cast<uint2 *>(lds + PL + o) = make_uint2(pm[0], pm[1]);
-        *reinterpret_cast<uint2 *>(lds + 2 * PL + o) = make_uint2(pl[0], pl[1]);
-      }
-    }
-  }
-  template <int PL>
-  __device__ __forceinline__ void store(char *lds, int tid) const {
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      const int unit = tid + u * NT;
-      if constexpr (KC) {
-        const int r = unit >> 2, c = unit & 3;
-        uint32_t h[4], m[4], l[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const u32x4 &s = v[u][i >> 1];
-          split2(__uint_as_float(s[2 * (i & 1)]), __uint_as_float(s[2 * (i & 1) + 1]),
-                 h[i], m[i], l[i]);
-        }
-        const int o = swz(r, c);
-        *reinterpret_cast<uint4 *>(lds + o) = make_uint4(h[0], h[1], h[2], h[3]);
-        *reinterpret_cast<uint4 *>(lds + PL + o) = make_uint4(m[0], m[1], m[2], m[3]);
-        *reinterpret_cast<uint4 *>(lds + 2 * PL + o) = make_uint4(l[0], l[1], l[2], l[3]);
-      } else {
-        const int rq = unit % (R / 4), kq = unit / (R / 4);
-#pragma unroll
-        for (int j = 0; j < KQ; ++j) {
-          const u32x4 &s = v[u][j];
-          uint32_t h0, m0, l0, h1, m1, l1;
-          split2(__uint_as_float(s[0]), __uint_as_float(s[1]), h0, m0, l0);
-          split2(__uint_as_float(s[2]), __uint_as_float(s[3]), h1, m1, l1);
-          const int o = tswz<R>(kq * KQ + j, 4 * rq);
-          *reinterpret_cast<uint2 *>(lds + o) = make_uint2(h0, h1);
-          *reinterpret_cast<uint2 *>(lds + PL + o) = make_uint2(m0, m1);
-          *reinterpret_cast<uint2 *>(lds + 2 * PL + o) = make_uint2(l0, l1);
-        }
-      }
-    }
-  }
-};
 
 // MFMA fragment (32 rows from rb, k16 half s) of one plane
 template <int R, bool KC>
@@ -684,242 +568,15 @@ __device__ __forceinline__ bf16x8 frag(const char *plane, int rb, int s, int lan
   }
 }
 
-struct GemmFastArgs {
-  const float *A, *B;
-  float *C;
-  int M, N, K, lda, ldb, ldc;
-  int kps, ksplit, tiles_m, tiles_n;
-  float alpha, beta;
-  int partial;
-};
-
-template <bool A_KC, bool B_KC, int DBG>
-__global__ __launch_bounds__(NT, 1) void gemm_x6_fast_kernel(GemmFastArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  const int nb = gridDim.x, b = blockIdx.x;
-  const int xcd = b & 7, q = nb >> 3, rr = nb & 7;
-  const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (b >> 3);
-  const int split = lid % p.ksplit;
-  const int rest = lid / p.ksplit;
-  const int tn = rest % p.tiles_n, tm = rest / p.tiles_n;
-  const int row0 = tm * BM, col0 = tn * BN;
-  const int kbeg = split * p.kps;
-  const int T = min(p.kps, p.K - kbeg) / BK;
-
-  // per-workgroup descriptors: the base is the tile's first element at the
-  // split's first k, so every in-range offset is < 2^31 (host-checked)
-  const float *abase = A_KC ? p.A + (int64_t)row0 * p.lda + kbeg
-                            : p.A + (int64_t)kbeg * p.lda + row0;
-  const float *bbase = B_KC ? p.B + (int64_t)col0 * p.ldb + kbeg
-                            : p.B + (int64_t)kbeg * p.ldb + col0;
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc((void *)abase, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc((void *)bbase, (short)0, 0x7fffffff, 0x00020000);
-
-  // two register sets: step t splits tile t+1 out of set (t+1) & 1 and
-  // then reloads that set with tile t+3, so a tile's HBM loads have two
-  // whole K steps to land before the split waits on them
-  FastLoader<BM, A_KC> la0, la1;
-  FastLoader<BN, B_KC> lb0, lb1;
-  la0.init(p.lda, row0, p.M, tid);
-  lb0.init(p.ldb, col0, p.N, tid);
-  la1.init(p.lda, row0, p.M, tid);
-  lb1.init(p.ldb, col0, p.N, tid);
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.0f;
-
-  if (T > 0) {
-    la0.load(ra, 0);
-    lb0.load(rb, 0);
-    la0.template store<A_PLANE>(lds, tid);
-    lb0.template store<B_PLANE>(lds + 3 * A_PLANE, tid);
-    la1.load(ra, min(1, T - 1) * BK);
-    lb1.load(rb, min(1, T - 1) * BK);
-    la0.load(ra, min(2, T - 1) * BK);
-    lb0.load(rb, min(2, T - 1) * BK);
-    __syncthreads();
-  }
-
-  // K step t = phase A | barrier | phase B:
-  //   A: the 24 s = 0 MFMAs (fragments F0, read in the previous phase B),
-  //      the split of tile t+1 into the other buffer (12 pieces, one per
-  //      MFMA pair) and the s = 1 fragment reads F1;
-  //   barrier: tile t+1 is written and buffer t & 1 fully read by all waves;
-  //   B: the 24 s = 1 MFMAs, the s = 0 fragment reads of step t+1 (from the
-  //      other buffer) and the HBM loads of tile t+3.
-  // The reads after the barrier thus run beside MFMAs instead of in front
-  // of them.  Each MFMA and the work placed after it are fenced
-  // (sched_barrier) so the order above is the issue order.
-  const int ar = wm * 64, br = wn * 64;
-  bf16x8 fa0[2][3], fb0[2][3], fa1[2][3], fb1[2][3];
-  constexpr int NRA = A_KC ? 1 : 2, NRB = B_KC ? 1 : 2;  // reads per fragment
-  constexpr int NREAD = 6 * NRA + 6 * NRB;
-  // r-th fragment read of half s (A fragments first, then B)
-  auto read_frag = [&](const char *buf, int s, int r, bf16x8 (&fa)[2][3],
-                       bf16x8 (&fb)[2][3]) {
-    if (r < 6) {
-      const int i = r / 3, pl = r % 3;
-      if (DBG & 16) {
-        fa[i][pl] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)lane, (unsigned)s, 3u * i, 7u * pl});
-        return;
-      }
-      fa[i][pl] = frag<BM, A_KC>(buf + pl * A_PLANE, ar + 32 * i, s, lane);
-    } else {
-      const int i = (r - 6) / 3, pl = (r - 6) % 3;
-      if (DBG & 16) {
-        fb[i][pl] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)lane, (unsigned)s, 5u * i, 9u * pl});
-        return;
-      }
-      fb[i][pl] = frag<BN, B_KC>(buf + 3 * A_PLANE + pl * B_PLANE, br + 32 * i, s, lane);
-    }
-  };
-  // n-th MFMA of a half: accumulator (i, j) = (n / 12, (n / 6) % 2), the
-  // six products small to large
-  auto mfma_n = [&](int n, const bf16x8 (&fa)[2][3], const bf16x8 (&fb)[2][3]) {
-    const int i = n / 12, j = (n / 6) & 1, pr = n % 6;
-    if (DBG & 4) return;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-    acc[i][j] = mfma(fa[i][PA[pr]], fb[j][PB[pr]], acc[i][j]);
-  };
-  if (T > 0) {
-#pragma unroll
-    for (int r = 0; r < 12; ++r) read_frag(lds, 0, r, fa0, fb0);
-  }
-  auto step = [&](int t, FastLoader<BM, A_KC> &la, FastLoader<BN, B_KC> &lb) {
-    const char *buf = lds + (t & 1) * BUF;
-    char *nbuf = lds + ((t + 1) & 1) * BUF;
-    const int kload = min(t + 3, T - 1) * BK;  // the last tile again past T
-    uint32_t ph[4], pm[4], pl[4];
-    // phase A
-#pragma unroll
-    for (int n = 0; n < 24; ++n) {
-      mfma_n(n, fa0, fb0);
-      if (!(DBG & 1) && (n & 1) == 0) {
-        const int pc = n >> 1;
-        if (pc < FastLoader<BM, A_KC>::NPIECE)
-          la.template piece<A_PLANE>(nbuf, tid, pc, ph, pm, pl);
-        else
-          lb.template piece<B_PLANE>(nbuf + 3 * A_PLANE, tid,
-                                     pc - FastLoader<BM, A_KC>::NPIECE, ph, pm, pl);
-      }
-      // F1 reads: one per MFMA from the 6th on (all issued by the 18th)
-      if (n >= 6 && n - 6 < NREAD / 2) {
-        read_frag(buf, 1, 2 * (n - 6), fa1, fb1);
-        read_frag(buf, 1, 2 * (n - 6) + 1, fa1, fb1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (!(DBG & 8)) __syncthreads();
-    // phase B
-#pragma unroll
-    for (int n = 0; n < 24; ++n) {
-      mfma_n(n, fa1, fb1);
-      if (n >= 2 && n - 2 < NREAD / 2) {
-        read_frag(nbuf, 0, 2 * (n - 2), fa0, fb0);
-        read_frag(nbuf, 0, 2 * (n - 2) + 1, fa0, fb0);
-      }
-      if (!(DBG & 2) && n >= 1 && (n - 1) % 2 == 0) {
-        // HBM loads of tile t+3, spread over the half
-        const int q = (n - 1) / 2;
-        if (q == 0) { la.load(ra, kload); }
-        if (q == 1) { lb.load(rb, kload); }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  int t = 0;
-  for (; t + 1 < T; t += 2) {
-    step(t, la1, lb1);      // tile t+1 is in set 1 (t even)
-    step(t + 1, la0, lb0);  // tile t+2 in set 0
-  }
-  if (t < T) step(t, la1, lb1);
-
-  float *out = p.partial ? p.C + (int64_t)split * p.M * p.N : p.C;
-  const int ldo = p.partial ? p.N : p.ldc;
-  const int half = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = col0 + wn * 64 + j * 32 + (lane & 31);
-      if (col >= p.N) continue;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int row = row0 + wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * half;
-        if (row >= p.M) continue;
-        float *o = out + (int64_t)row * ldo + col;
-        if (p.partial) *o = acc[i][j][g];
-        else *o = p.beta == 0.0f ? p.alpha * acc[i][j][g]
-                                 : p.alpha * acc[i][j][g] + p.beta * *o;
-      }
-    }
-}
-
-template <bool A_KC, bool B_KC, int DBG>
-void launch_fast_d(const GemmFastArgs &a, unsigned blocks, hipStream_t st) {
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_x6_fast_kernel<A_KC, B_KC, DBG>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_x6_fast_kernel<A_KC, B_KC, DBG>), dim3(blocks), dim3(NT),
-                     LDS_BYTES, st, a);
-}
-
-// the DBG template argument (timing experiments that skip work, so the
-// results are wrong: 1 no split stores, 2 no HBM loads, 4 no MFMAs, 8 no
-// barrier, 16 no fragment reads) is selectable by KCNN_X6_DBG only in the
-// phase-timing build (make timing), never in libkcnn.so
-template <bool A_KC, bool B_KC>
-void launch_fast(const GemmFastArgs &a, unsigned blocks, hipStream_t st) {
-#ifdef KCNN_PHASE_TIMING
-  static const int dbg = KCNN_KNOB("KCNN_X6_DBG", 0);
-  switch (dbg) {
-    case 1: launch_fast_d<A_KC, B_KC, 1>(a, blocks, st); return;
-    case 2: launch_fast_d<A_KC, B_KC, 2>(a, blocks, st); return;
-    case 4: launch_fast_d<A_KC, B_KC, 4>(a, blocks, st); return;
-    case 16: launch_fast_d<A_KC, B_KC, 16>(a, blocks, st); return;
-    default: break;
-  }
-#endif
-  launch_fast_d<A_KC, B_KC, 0>(a, blocks, st);
-}
-
-// KCNN_X6_FAST=1 selects the one-block-per-step kernel above.  It is not the
-// default: at the c2 FC shapes it measured within box-to-box noise of the
-// two-phase kernel (0.49-0.55 vs 0.51-0.61 ms), its mixed-layout variants
-// spill (256 VGPRs with the two-set register ring), and one of eight runs
-// of tests/test_gpu_gemm.py failed on it (fc_dgrad, max err/S 3e-4) without
-// reproducing in 20 repeats -- an unexplained fault is not shipped.
-bool fast_enabled() {
-  static const bool on = KCNN_KNOB("KCNN_X6_FAST", 0) != 0;
-  return on;
-}
-// KCNN_X6_DEEP=0 (experiment build): gemm_x6_kernel's one-step prefetch
-bool deep_enabled() {
-  static const bool on = KCNN_KNOB("KCNN_X6_DEEP", 1) != 0;
-  return on;
-}
-
 // ---------------------------------------------------------------------------
 // Plane GEMM: both operands already split into their three bf16 planes in
 // HBM (kl_split_planes), so the K step is pure data movement and MFMAs.
 // Tiles reach LDS by LDS-DMA (buffer_load ... lds: 1 KiB per wave
 // instruction, no VGPRs, no VALU): the lane of each 16-B LDS slot reads the
 // global chunk that the swizzled image wants there (a permutation of 16-B
-// chunks, so the images are exactly those of the fast kernel and `frag`
-// reads them).  Same phase A | barrier | phase B step as the fast kernel;
+// chunks, so `frag` reads the images described above).  A K step is phase A
+// (the MFMAs of k16 half 0, the fragment reads of half 1) | barrier | phase B
+// (the MFMAs of half 1, the next tile's fragment reads of half 0);
 // the DMA of tile t+2 is issued in phase B of step t into the buffer whose
 // last reads finished before that step's barrier, and the next barrier
 // (s_waitcnt vmcnt(0) + s_barrier) publishes it.
@@ -1141,42 +798,26 @@ __global__ void split_planes_kernel(const float *__restrict__ src, int rows, int
   }
 }
 
-template <bool A_KC, bool B_KC, bool STG>
-void launch_x6_t(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_x6_kernel<A_KC, B_KC, STG>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_x6_kernel<A_KC, B_KC, STG>), dim3(blocks), dim3(NT), LDS_BYTES,
-                     st, a);
-}
-// KCNN_X6_STAGGER=0: no wave-pair stagger (c2 FC GEMMs 1.655 -> 1.636 ms with it)
 template <bool A_KC, bool B_KC>
 void launch_x6(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
-  static const int stg = KCNN_KNOB("KCNN_X6_STAGGER", 1);
-  if (stg) launch_x6_t<A_KC, B_KC, true>(a, blocks, st);
-  else launch_x6_t<A_KC, B_KC, false>(a, blocks, st);
-}
-
-template <bool A_KC, bool B_KC, int DEPTH>
-void launch_x6d_t(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
   static bool attr = [] {
     return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_x6d_kernel<A_KC, B_KC, DEPTH>),
+               reinterpret_cast<const void *>(&gemm_x6_kernel<A_KC, B_KC>),
                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
   }();
   (void)attr;
-  hipLaunchKernelGGL((gemm_x6d_kernel<A_KC, B_KC, DEPTH>), dim3(blocks), dim3(NT), LDS_BYTES,
-                     st, a);
+  hipLaunchKernelGGL((gemm_x6_kernel<A_KC, B_KC>), dim3(blocks), dim3(NT), LDS_BYTES, st, a);
 }
-// prefetch depth 2; KCNN_X6_DEEP=2 (experiment build) selects depth 3
+
 template <bool A_KC, bool B_KC>
 void launch_x6d(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
-  static const int depth = KCNN_KNOB("KCNN_X6_DEEP", 1);
-  if (depth == 2) launch_x6d_t<A_KC, B_KC, 3>(a, blocks, st);
-  else launch_x6d_t<A_KC, B_KC, 2>(a, blocks, st);
+  static bool attr = [] {
+    return hipFuncSetAttribute(
+               reinterpret_cast<const void *>(&gemm_x6d_kernel<A_KC, B_KC>),
+               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
+  }();
+  (void)attr;
+  hipLaunchKernelGGL((gemm_x6d_kernel<A_KC, B_KC>), dim3(blocks), dim3(NT), LDS_BYTES, st, a);
 }
 
 // K splits for a tile count: the fraction of the last wave of workgroups
@@ -1231,32 +872,12 @@ extern "C" int kl_gemm_x6(int transA, int transB, int M, int N, int K, float alp
   a.ldc = ldc;
   const int64_t nb = tiles * s;
   if (nb >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  // fast path: whole BK steps in every split, 16-B loads on both operands
-  // (a row-contiguous operand also needs its row count a multiple of 4) and
-  // every buffer offset of a workgroup below 2^31
-  auto fits = [&](bool kc, const float *ptr, int ld, int rows, int R) {
-    if (ld % 4 || (uintptr_t)ptr % 16) return false;
-    if (kc) return (int64_t)R * ld * 4 + (int64_t)K * 4 < ((int64_t)1 << 31);
-    return rows % 4 == 0 && (int64_t)(a.kps + 1) * ld * 4 < ((int64_t)1 << 31);
-  };
   // two-deep prefetch kernel: whole BK steps, the workgroup's offsets below 2^31
   auto deep_fits = [&](bool kc, int ld, int R) {
     if (kc) return (int64_t)R * ld * 4 + (int64_t)K * 4 < ((int64_t)1 << 31);
     return (int64_t)(a.kps + 1) * ld * 4 + (int64_t)R * 4 < ((int64_t)1 << 31);
   };
-  if (fast_enabled() && K % BK == 0 && fits(a_kc, A, lda, M, BM) &&
-      fits(b_kc, B, ldb, N, BN)) {
-    GemmFastArgs f;
-    f.A = A; f.B = B; f.C = a.C; f.M = M; f.N = N; f.K = K;
-    f.lda = lda; f.ldb = ldb; f.ldc = ldc; f.kps = a.kps; f.ksplit = s;
-    f.tiles_m = a.tiles_m; f.tiles_n = a.tiles_n; f.alpha = alpha; f.beta = beta;
-    f.partial = a.partial;
-    if (a_kc && b_kc) launch_fast<true, true>(f, (unsigned)nb, st);
-    else if (a_kc) launch_fast<true, false>(f, (unsigned)nb, st);
-    else if (b_kc) launch_fast<false, true>(f, (unsigned)nb, st);
-    else launch_fast<false, false>(f, (unsigned)nb, st);
-  } else if (deep_enabled() && K % BK == 0 && deep_fits(a_kc, lda, BM) &&
-             deep_fits(b_kc, ldb, BN)) {
+  if (K % BK == 0 && deep_fits(a_kc, lda, BM) && deep_fits(b_kc, ldb, BN)) {
     if (a_kc && b_kc) launch_x6d<true, true>(a, (unsigned)nb, st);
     else if (a_kc) launch_x6d<true, false>(a, (unsigned)nb, st);
     else if (b_kc) launch_x6d<false, true>(a, (unsigned)nb, st);

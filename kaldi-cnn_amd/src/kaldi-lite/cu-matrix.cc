@@ -479,14 +479,10 @@ void CuMatrixBase<Real>::AddMatMat(Real alpha, const CuMatrixBase<Real> &A,
   // gives too few output tiles to fill 256 CUs: split K over a strided
   // batch, then sum the partials in a fixed order.
   int nsplit = 1;
-  {
-    const int64_t tiles = (int64_t)((m + 255) / 256) * ((n + 255) / 256);
-    if (tiles < 128 && k >= 4096) {
-      for (int s : {4, 2})
-        if (k % s == 0 && k / s >= 1024 && tiles * s <= 512) { nsplit = s; break; }
-    }
-    static const int e = KCNN_KNOB("KCNN_GEMM_SPLITK", 0);
-    if (e >= 1 && k % e == 0) nsplit = e;
+  const int64_t tiles = (int64_t)((m + 255) / 256) * ((n + 255) / 256);
+  if (tiles < 128 && k >= 4096) {
+    for (int s : {4, 2})
+      if (k % s == 0 && k / s >= 1024 && tiles * s <= 512) { nsplit = s; break; }
   }
   if (nsplit > 1) {
     CuDevice &dev = CuDevice::Instantiate();

@@ -55,9 +55,14 @@ int family_by_name(const char *name) {
   return -1;
 }
 
-int experiment_env(const char *name, int dflt) {
-  const char *s = getenv(name);
-  return s && *s ? atoi(s) : dflt;
+#ifdef KCNN_PHASE_TIMING
+int phase_timing() {
+  static const int on = [] {
+    const char *s = getenv("KCNN_PHASE_TIMING");
+    return s && atoi(s) != 0 ? 1 : 0;
+  }();
+  return on;
 }
+#endif
 
 }  // namespace kcnn

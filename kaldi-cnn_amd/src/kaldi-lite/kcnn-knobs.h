@@ -19,11 +19,14 @@
 // (KCNN_FUSE, KCNN_LITERAL and KCNN_PROFILE are kcnn_set_fusion,
 // kcnn_set_literal_path and kcnn_set_profiling.)
 //
-// Experiment knobs (KCNN_KNOB) are the A/B switches used while tuning a
-// kernel.  Only the `make timing` build (-DKCNN_EXPERIMENTS) reads them from
-// the environment; the product library compiles each one to its default.
-#ifndef KCNN_KALDI_LITE_KCNN_KNOBS_H_
-#define KCNN_KALDI_LITE_KCNN_KNOBS_H_
+// One observation-only facility remains beside them: the per-phase clock
+// marks of the convolution kernels (KCNN_TMARK and the printf of block 0's
+// totals).  They are compiled only into the `make timing` library
+// (-DKCNN_PHASE_TIMING), which switches them on when KCNN_PHASE_TIMING=1 is in
+// the environment; they change no result.  phase_timing() is constant 0 in
+// the product library.
+#ifndef KCNN_KALDI_LITE_KNOBS_H_
+#define KCNN_KALDI_LITE_KNOBS_H_
 
 namespace kcnn {
 
@@ -32,14 +35,13 @@ enum Family { kFamFwdX6 = 0, kFamBwdX6, kFamIgemmX6, kFamWgradX6, kFamGemm, kNum
 int family(Family f);                 // current value of a selector
 int set_family(Family f, int value);  // 0 on success, -1 for an invalid value
 int family_by_name(const char *name);  // Family index, -1 when unknown
-int experiment_env(const char *name, int dflt);
+
+#ifdef KCNN_PHASE_TIMING
+int phase_timing();  // 1 when the clock marks are switched on
+#else
+constexpr int phase_timing() { return 0; }
+#endif
 
 }  // namespace kcnn
 
-#ifdef KCNN_EXPERIMENTS
-#define KCNN_KNOB(name, dflt) (::kcnn::experiment_env(name, dflt))
-#else
-#define KCNN_KNOB(name, dflt) (dflt)
-#endif
-
-#endif  // KCNN_KALDI_LITE_KCNN_KNOBS_H_
+#endif  // KCNN_KALDI_LITE_KNOBS_H_

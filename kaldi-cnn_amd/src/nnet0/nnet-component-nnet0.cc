@@ -942,12 +942,10 @@ bool MaxpoolComponent::FusableWindow3D(int32 *ph, int32 *pw, int32 *pc) const {
 }
 
 bool MaxpoolComponent::FoldsIntoConvBackprop() const {
-  // KCNN_FOLD_3D=0: 3-D windows back to BackpropFromMask + the conv's Backprop
-  static const bool fold3d = KCNN_KNOB("KCNN_FOLD_3D", 1) != 0;
   const int32 c = FusableChannelPool();
   if (c == 4 || c == 8) return true;
   int32 ph, pw, pc;
-  return fold3d && c == 0 && FusableWindow3D(&ph, &pw, &pc) && pw == 1 && (ph == 2 || ph == 3) &&
+  return c == 0 && FusableWindow3D(&ph, &pw, &pc) && pw == 1 && (ph == 2 || ph == 3) &&
          (pc == 4 || pc == 8) && ph * pc <= 16;
 }
 

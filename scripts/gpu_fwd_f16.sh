@@ -1,7 +1,6 @@
 # The f16x3 frame forward: determinism of repeated forwards, its range / Inf
 # tests and the conv, fusion, GEMM and family suites, a kernel trace of the
-# c2 step, the c2 bench with the f16x3 and the bf16x6 forward, and the
-# forward's phase / store A/B in the timing build.
+# c2 step, and the c2 bench with the f16x3 and the bf16x6 forward.
 #   scripts/gpu_fwd_f16.sh <outdir>
 set -o pipefail
 O=${1:-gpurun_out/fwdf16}
@@ -17,5 +16,4 @@ for v in 2 1 2 1; do
   KCNN_FWD_X6=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --json-out $O/bench_$v.json > $O/bench_$v.log 2>&1 || exit 6
   python -c "import json;d=json.load(open('$O/bench_$v.json'));print('fwd_x6=$v', d['value'], d['ms_per_step'])"
 done
-if [ -n "$AB" ]; then DBGS="0 256 512" PHASE=16 bash scripts/gpu_fwd_ab.sh $O/ab || exit 8; fi
 echo done
