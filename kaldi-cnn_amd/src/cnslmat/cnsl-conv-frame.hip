@@ -1954,6 +1954,39 @@ unsigned frame_grid(const ConvGeom &g, int blocks_per_cu) {
   return (unsigned)(b > 0 ? b : 1);
 }
 
+// conv_fwd_regs_kernel's shape limits and dynamic LDS bytes (0: the shape is
+// outside them or the plan does not fit).
+size_t fwd_regs_lds(const ConvGeom &g) {
+  if (g.Kdim > 32 || g.G > 128 || g.P < 16 || g.P > 4 * 32 * 3 || g.C * g.HW > 256 * 8)
+    return 0;
+  const size_t lds = (size_t)((32 * g.P + 3) & ~3) * 4 + 160 * 4 + 32 * 8 +
+                     (size_t)g.C * g.HW * 4 + 8 * 4;
+  return lds <= (size_t)kFrameLdsMax ? lds : 0;
+}
+
+// The fp32 fused backward kernels' position limits (conv_bwd_dma_kernel and
+// conv_bwd_frame_kernel: BWD_MAXT tiles per wave, BWD_MAXV slab registers).
+bool bwd_fp32_positions_ok(const ConvGeom &g) {
+  return g.P >= 16 && g.P <= 32 * BWD_WAVES * BWD_MAXT && 8 * g.P <= BWD_THREADS * BWD_MAXV;
+}
+
+// Runs fn(chunk geometry, first filter) over g's filters in chunks of 128
+// (each a column range of W, b and Y).  Only the first chunk may decline
+// (-1: nothing is written yet); a later one that does is a launch failure.
+// G <= 128 is one chunk, g itself.
+template <class F>
+int for_filter_chunks(const ConvGeom &g, F fn) {
+  int g0 = 0;
+  do {
+    ConvGeom gc = g;
+    gc.G = g.G - g0 < 128 ? g.G - g0 : 128;
+    const int rc = fn(gc, g0);
+    if (rc) return g0 == 0 ? rc : (rc < 0 ? (int)hipErrorLaunchFailure : rc);
+    g0 += 128;
+  } while (g0 < g.G);
+  return 0;
+}
+
 }  // namespace
 
 // The fused conv + pool forward's Y stores (fusion mode 2, Y kept for later)
@@ -1961,50 +1994,126 @@ unsigned frame_grid(const ConvGeom &g, int blocks_per_cu) {
 // conv, whose Y the pool reads right after (155 -> 181 us there).
 static constexpr int kYNt = 2;
 
-int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
-                        const float *K, int ks, const float *bias, float *out,
-                        int os, hipStream_t st) {
-  if (g.Kdim > 64 || g.P < 16) return -1;
-  if (g.G > 128 && g.G % 32 == 0 && g.Kdim <= 32) {
-    // filter chunks of 128: each is a column range of W, b and Y
-    for (int g0 = 0; g0 < g.G; g0 += 128) {
-      ConvGeom gc = g;
-      gc.G = g.G - g0 < 128 ? g.G - g0 : 128;
-      const int rc = kcnn_conv_fwd_frame(gc, X, xs, K + g0, ks, bias ? bias + g0 : nullptr,
-                                         out + (int64_t)g0 * g.P, os, st);
-      if (rc) return g0 == 0 ? rc : (rc < 0 ? (int)hipErrorLaunchFailure : rc);
+// conv_fwd_regs_kernel on one filter chunk.  The callers name the operands
+// (pc == 0, pool and mask NULL: the convolution alone; else a ph x pw x pc
+// max pool whose window the caller has checked); fwd_regs adds the launch
+// values below them.
+struct FwdRegs {
+  const float *X = nullptr, *K = nullptr, *bias = nullptr;
+  int xs = 0, ks = 0;
+  float *out = nullptr, *pool = nullptr;
+  int os = 0, ps = 0;
+  unsigned char *mask = nullptr;
+  int ms = 0, pc = 0, ph = 1, pw = 1;
+  // set by fwd_regs
+  int vec_ok = 0, clk = 0;
+  PoolWin pw3{};
+  bool rp = false;  // the register-pooled-only form (PC 4, f16x3): 8 more words of row slots
+  RpStats rps;
+  unsigned grid = 0;
+  size_t lds = 0;
+};
+
+template <int KS, int PC, int AR>
+static void fwd_regs_launch(const ConvGeom &g, const FwdRegs &a, hipStream_t st) {
+  if constexpr (PC == 4 && AR == 2) {
+    if (a.rp) {
+      hipLaunchKernelGGL((conv_fwd_regs_kernel<KS, 3, PC, AR, true>), dim3(a.grid), dim3(256),
+                         a.lds + 8 * 4, st, g, a.X, a.xs, a.K, a.ks, a.bias, a.out, a.os,
+                         a.vec_ok, a.clk, a.pool, a.ps, a.mask, a.ms, a.pw3, a.rps);
+      return;
     }
-    return 0;
   }
+  hipLaunchKernelGGL((conv_fwd_regs_kernel<KS, 3, PC, AR>), dim3(a.grid), dim3(256), a.lds, st,
+                     g, a.X, a.xs, a.K, a.ks, a.bias, a.out, a.os, a.vec_ok, a.clk, a.pool,
+                     a.ps, a.mask, a.ms, a.pw3, RpStats{});
+}
+
+// The kernel's k-steps and arithmetic for one pool form PC (0: no pool).
+template <int PC>
+static void fwd_regs_ks(const ConvGeom &g, const FwdRegs &a, int ar, hipStream_t st) {
+  const int ksn = (g.Kdim + 1) / 2;
+  if (ar == 2 && g.Kdim <= 16) fwd_regs_launch<1, PC, 2>(g, a, st);
+  else if (ar == 2) fwd_regs_launch<2, PC, 2>(g, a, st);
+  else if (ar == 1 && g.Kdim < 16) fwd_regs_launch<1, PC, 1>(g, a, st);
+  else if (ar == 1) fwd_regs_launch<2, PC, 1>(g, a, st);
+  else if (ksn <= 4) fwd_regs_launch<4, PC, 0>(g, a, st);
+  else if (ksn <= 8) fwd_regs_launch<8, PC, 0>(g, a, st);
+  else if (ksn <= 12) fwd_regs_launch<12, PC, 0>(g, a, st);
+  else fwd_regs_launch<16, PC, 0>(g, a, st);
+}
+
+// -1 outside the kernel's limits (fwd_regs_lds), nothing launched.
+static int fwd_regs(const ConvGeom &g, FwdRegs a, PoolStatsOut *stats, hipStream_t st) {
+  a.lds = fwd_regs_lds(g);
+  if (a.lds == 0) return -1;
+  const int pc = a.pc;
+  const bool win3 = a.ph > 1 || a.pw > 1;
+  if (win3) {
+    a.pw3.ph = a.ph; a.pw3.pw = a.pw; a.pw3.pc = pc;
+    a.pw3.oh2 = g.oh / a.ph;
+    a.pw3.OP = (g.oh / a.ph) * (g.ow / a.pw);
+    a.pw3.div_OP = FastDiv((uint32_t)a.pw3.OP);
+    a.pw3.div_oh2 = FastDiv((uint32_t)a.pw3.oh2);
+  }
+  // 16-B Y stores; streaming ones (kYNt) beside a pool only
+  const bool aligned = ((uintptr_t)a.out % 16 == 0) && (a.os % 4 == 0);
+  a.vec_ok = aligned ? (pc ? 1 | kYNt : 1) : 0;
+  a.clk = phase_timing();
+  const int ar = fwd_arith(g, family(kFamFwdX6));
+  a.grid = frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(a.lds));
+  // the register-pooled-only form: pooled output only, pc 4, G = 128 and
+  // exactly 12 position tiles, so each of the 4 waves has all 3 (the form
+  // runs every item unfiltered: with 9-11 tiles a wave's third tile would
+  // pool and take statistics from registers no gather wrote)
+  const int ntile = (g.P + 31) / 32;
+  a.rp = a.out == nullptr && pc == 4 && !win3 && g.G == 128 && ntile == 4 * 3 && ar == 2 &&
+         a.lds + 8 * 4 <= (size_t)kFrameLdsMax;
+  // the register-pooled kernel also gives the pooled output's max |value|
+  // bits per frame and per column (stats, when the caller passes room)
+  if (a.rp && stats && stats->partials &&
+      stats->partial_words >= ((size_t)a.grid * (g.G / pc) * g.P + 3) / 4 &&
+      (size_t)a.grid * 256 >= (size_t)(g.G / pc) * g.P) {
+    a.rps.rowmax = stats->rowmax;
+    a.rps.partials = stats->partials;
+    a.rps.colmax = stats->colmax;
+  }
+  uint32_t *pcol = a.rps.partials;
+  if (pc == 0) fwd_regs_ks<0>(g, a, ar, st);
+  else if (win3 && a.ph == 3 && a.pw == 1 && pc == 4) fwd_regs_ks<-3>(g, a, ar, st);
+  else if (win3) fwd_regs_ks<-1>(g, a, ar, st);
+  else if (pc == 2) fwd_regs_ks<2>(g, a, ar, st);
+  else if (pc == 4) fwd_regs_ks<4>(g, a, ar, st);
+  else fwd_regs_ks<8>(g, a, ar, st);
+  if (pcol) {
+    PoolColDeferred d;
+    d.pcol = reinterpret_cast<const uint8_t *>(pcol);
+    d.nblk = (int)a.grid;
+    d.npool = g.G / pc * g.P;
+    d.P = a.pool;
+    d.ps = a.ps;
+    d.R = g.R;
+    d.vec = a.ps % 4 == 0 && (uintptr_t)a.pool % 16 == 0;
+    d.rowblk = stats->rowmax;
+    d.colblk = stats->colmax;
+    d.pending = 1;
+    stats->produced = 1;
+    if (PoolColDeferred *req = kcnn_pool_defer_current())
+      *req = d;  // the consumer's statistics launches take it
+    else return kcnn_pool_cols_complete(&d, reinterpret_cast<kcnn_stream_t>(st));
+  }
+  return (int)hipGetLastError();
+}
+
+// One filter chunk of kcnn_conv_fwd_frame: the register kernel, else the
+// slab kernel, else conv_fwd_frame_kernel, each where its LDS plan fits.
+static int fwd_frame_chunk(const ConvGeom &g, const float *X, int xs, const float *K, int ks,
+                           const float *bias, float *out, int os, hipStream_t st) {
+  FwdRegs a;
+  a.X = X; a.xs = xs; a.K = K; a.ks = ks; a.bias = bias; a.out = out; a.os = os;
+  const int rc = fwd_regs(g, a, nullptr, st);
+  if (rc >= 0) return rc;
   const int Kpad = (g.Kdim + 1) & ~1;
-  if (g.Kdim <= 32 && g.G <= 128 && g.P <= 4 * 32 * 3 &&
-      g.C * g.HW <= 256 * 8) {
-    const size_t lds = (size_t)((32 * g.P + 3) & ~3) * 4 + 160 * 4 + 32 * 8 +
-                       (size_t)g.C * g.HW * 4 + 8 * 4;
-    if (lds <= (size_t)kFrameLdsMax) {
-      const int vec_ok = ((uintptr_t)out % 16 == 0) && (os % 4 == 0);
-      const int ksn = (g.Kdim + 1) / 2;
-      const int ar = fwd_arith(g, family(kFamFwdX6));
-      const unsigned grid = frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(lds));
-#define KCNN_FWD_REGS_T(KS_, AR_)                                                       \
-  hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, 0, AR_>), dim3(grid), dim3(256), lds, \
-                     st, g, X, xs, K, ks, bias, out, os, vec_ok, clk, nullptr, 0, nullptr, \
-                     0, PoolWin{}, RpStats{})
-#define KCNN_FWD_REGS(KS_) KCNN_FWD_REGS_T(KS_, 0)
-      const int clk = phase_timing();
-      if (ar == 2 && g.Kdim <= 16) KCNN_FWD_REGS_T(1, 2);
-      else if (ar == 2) KCNN_FWD_REGS_T(2, 2);
-      else if (ar == 1 && g.Kdim < 16) KCNN_FWD_REGS_T(1, 1);
-      else if (ar == 1) KCNN_FWD_REGS_T(2, 1);
-      else if (ksn <= 4) KCNN_FWD_REGS(4);
-      else if (ksn <= 8) KCNN_FWD_REGS(8);
-      else if (ksn <= 12) KCNN_FWD_REGS(12);
-      else KCNN_FWD_REGS(16);
-#undef KCNN_FWD_REGS
-#undef KCNN_FWD_REGS_T
-      return (int)hipGetLastError();
-    }
-  }
   {
     // slab-streamed: T [32][P] staged in LDS, written as whole 16-B lines
     const int Gp = (g.G + 31) & ~31;
@@ -2035,7 +2144,20 @@ int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
   return (int)hipGetLastError();
 }
 
-// Forward + channel-only max pool (pool 1 x 1 x pc) in one pass; -1 when the
+int kcnn_conv_fwd_frame(const ConvGeom &g, const float *X, int xs,
+                        const float *K, int ks, const float *bias, float *out,
+                        int os, hipStream_t st) {
+  if (!kcnn::in_frame_range(g)) return -1;
+  const auto chunk = [&](const ConvGeom &gc, int g0) {
+    return fwd_frame_chunk(gc, X, xs, K + g0, ks, bias ? bias + g0 : nullptr,
+                           out + (int64_t)g0 * g.P, os, st);
+  };
+  if (g.G > 128 && g.G % 32 == 0 && g.Kdim <= 32) return for_filter_chunks(g, chunk);
+  return chunk(g, 0);
+}
+
+// Forward + max pool (ph x pw x pc; 1 x 1 x pc: channel-only, 8-bit mask,
+// else a 16-bit mask with ms in mask elements) in one pass; -1 when the
 // geometry is outside the register-resident kernel's limits.
 int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
                              const float *K, int ks, const float *bias,
@@ -2043,7 +2165,7 @@ int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
                              unsigned char *mask, int ms, int pc,
                              hipStream_t st, int ph, int pw, PoolStatsOut *stats) {
   if (stats) stats->produced = 0;
-  const bool win3 = ph > 1 || pw > 1;  // 16-bit mask; ms in mask elements
+  const bool win3 = ph > 1 || pw > 1;
   if (win3) {
     if (pc < 1 || 32 % pc != 0 || ph * pw * pc > 16 || g.oh % ph != 0 || g.ow % pw != 0)
       return -1;
@@ -2052,110 +2174,22 @@ int kcnn_conv_fwd_frame_pool(const ConvGeom &g, const float *X, int xs,
   }
   if (g.G % pc != 0) return -1;
   const int OP = win3 ? (g.oh / ph) * (g.ow / pw) : g.P;  // pooled positions per map
-  if (g.G > 128 && g.G % 32 == 0) {  // filter chunks of 128 (pool groups never straddle)
-    for (int g0 = 0; g0 < g.G; g0 += 128) {
-      ConvGeom gc = g;
-      gc.G = g.G - g0 < 128 ? g.G - g0 : 128;
-      const int64_t pofs = (int64_t)(g0 / pc) * OP;
-      unsigned char *mc = win3 ? reinterpret_cast<unsigned char *>(
-                                     reinterpret_cast<unsigned short *>(mask) + pofs)
-                               : mask + pofs;
-      const int rc = kcnn_conv_fwd_frame_pool(gc, X, xs, K + g0, ks, bias ? bias + g0 : nullptr,
-                                              out ? out + (int64_t)g0 * g.P : nullptr, os,
-                                              pool + pofs, ps,
-                                              mc, ms, pc, st, ph, pw, nullptr);
-      if (rc) return g0 == 0 ? rc : (rc < 0 ? (int)hipErrorLaunchFailure : rc);
-    }
-    return 0;
-  }
-  PoolWin pw3{};
-  if (win3) {
-    pw3.ph = ph; pw3.pw = pw; pw3.pc = pc;
-    pw3.oh2 = g.oh / ph;
-    pw3.OP = OP;
-    pw3.div_OP = FastDiv((uint32_t)OP);
-    pw3.div_oh2 = FastDiv((uint32_t)pw3.oh2);
-  }
-  if (g.Kdim > 32 || g.G > 128 || g.P < 16 || g.P > 4 * 32 * 3 ||
-      g.C * g.HW > 256 * 8)
-    return -1;
-  const size_t lds = (size_t)((32 * g.P + 3) & ~3) * 4 + 160 * 4 + 32 * 8 +
-                     (size_t)g.C * g.HW * 4 + 8 * 4;
-  if (lds > (size_t)kFrameLdsMax) return -1;
-  const int vec_ok = ((uintptr_t)out % 16 == 0) && (os % 4 == 0) ? 1 | kYNt : 0;
-  const int ksn = (g.Kdim + 1) / 2;
-  const int ar = fwd_arith(g, family(kFamFwdX6));
-  const unsigned grid = frame_grid(g, ar ? 2 : fwd_regs_blocks_per_cu(lds));
-  const int clk = phase_timing();
-  // the register-pooled-only form: pooled output only, pc 4, G = 128 and
-  // exactly 12 position tiles, so each of the 4 waves has all 3 (the form
-  // runs every item unfiltered: with 9-11 tiles a wave's third tile would
-  // pool and take statistics from registers no gather wrote)
-  const int ntile = (g.P + 31) / 32;
-  // (its LDS: 8 more words of row slots)
-  const size_t lds_rp = lds + 8 * 4;
-  const bool rp = out == nullptr && pc == 4 && !win3 && g.G == 128 && ntile == 4 * 3 &&
-                  ar == 2 && lds_rp <= (size_t)kFrameLdsMax;
-  // the register-pooled kernel also gives the pooled output's max |value|
-  // bits per frame and per column (stats, when the caller passes room)
-  RpStats rps;
-  if (rp && stats && stats->partials &&
-      stats->partial_words >= ((size_t)grid * (g.G / pc) * g.P + 3) / 4 &&
-      (size_t)grid * 256 >= (size_t)(g.G / pc) * g.P) {
-    rps.rowmax = stats->rowmax;
-    rps.partials = stats->partials;
-    rps.colmax = stats->colmax;
-  }
-  uint32_t *pcol = rps.partials;
-#define KCNN_FWD_POOL_T(KS_, PC_, AR_)                                                      \
-  do {                                                                                       \
-    if (rp && PC_ == 4 && AR_ == 2)                                                          \
-      hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, PC_, AR_, PC_ == 4 && AR_ == 2>),     \
-                         dim3(grid), dim3(256), lds_rp, st, g, X, xs, K, ks, bias, out, os,  \
-                         vec_ok, clk, pool, ps, mask, ms, pw3, rps);                         \
-    else                                                                                     \
-      hipLaunchKernelGGL((conv_fwd_regs_kernel<KS_, 3, PC_, AR_>), dim3(grid), dim3(256), lds, \
-                         st, g, X, xs, K, ks, bias, out, os, vec_ok, clk, pool, ps, mask, ms, pw3, \
-                         RpStats{});                                                         \
-  } while (0)
-#define KCNN_FWD_POOL(KS_, PC_) KCNN_FWD_POOL_T(KS_, PC_, 0)
-#define KCNN_FWD_POOL_KS(PC_)                     \
-  do {                                            \
-    if (ar == 2 && g.Kdim <= 16) KCNN_FWD_POOL_T(1, PC_, 2); \
-    else if (ar == 2) KCNN_FWD_POOL_T(2, PC_, 2); \
-    else if (ar == 1 && g.Kdim < 16) KCNN_FWD_POOL_T(1, PC_, 1); \
-    else if (ar == 1) KCNN_FWD_POOL_T(2, PC_, 1); \
-    else if (ksn <= 4) KCNN_FWD_POOL(4, PC_);     \
-    else if (ksn <= 8) KCNN_FWD_POOL(8, PC_);     \
-    else if (ksn <= 12) KCNN_FWD_POOL(12, PC_);   \
-    else KCNN_FWD_POOL(16, PC_);                  \
-  } while (0)
-  if (win3 && ph == 3 && pw == 1 && pc == 4) KCNN_FWD_POOL_KS(-3);
-  else if (win3) KCNN_FWD_POOL_KS(-1);
-  else if (pc == 2) KCNN_FWD_POOL_KS(2);
-  else if (pc == 4) KCNN_FWD_POOL_KS(4);
-  else KCNN_FWD_POOL_KS(8);
-#undef KCNN_FWD_POOL_KS
-#undef KCNN_FWD_POOL
-#undef KCNN_FWD_POOL_T
-  if (pcol) {
-    PoolColDeferred d;
-    d.pcol = reinterpret_cast<const uint8_t *>(pcol);
-    d.nblk = (int)grid;
-    d.npool = g.G / pc * g.P;
-    d.P = pool;
-    d.ps = ps;
-    d.R = g.R;
-    d.vec = ps % 4 == 0 && (uintptr_t)pool % 16 == 0;
-    d.rowblk = stats->rowmax;
-    d.colblk = stats->colmax;
-    d.pending = 1;
-    stats->produced = 1;
-    if (PoolColDeferred *req = kcnn_pool_defer_current())
-      *req = d;  // the consumer's statistics launches take it
-    else return kcnn_pool_cols_complete(&d, reinterpret_cast<kcnn_stream_t>(st));
-  }
-  return (int)hipGetLastError();
+  // filter chunks (pool groups never straddle them) give no statistics
+  const bool chunked = g.G > 128 && g.G % 32 == 0;
+  const auto chunk = [&](const ConvGeom &gc, int g0) {
+    const int64_t pofs = (int64_t)(g0 / pc) * OP;
+    FwdRegs a;
+    a.X = X; a.xs = xs; a.K = K + g0; a.ks = ks;
+    a.bias = bias ? bias + g0 : nullptr;
+    a.out = out ? out + (int64_t)g0 * g.P : nullptr; a.os = os;
+    a.pool = pool + pofs; a.ps = ps;
+    a.mask = win3 ? reinterpret_cast<unsigned char *>(
+                        reinterpret_cast<unsigned short *>(mask) + pofs)
+                  : mask + pofs;
+    a.ms = ms; a.pc = pc; a.ph = ph; a.pw = pw;
+    return fwd_regs(gc, a, chunked ? nullptr : stats, st);
+  };
+  return chunked ? for_filter_chunks(g, chunk) : chunk(g, 0);
 }
 
 int kcnn_pool_cols_complete(PoolColDeferred *d, kcnn_stream_t stream) {
@@ -2216,7 +2250,6 @@ int kcnn_conv_wgrad_frame(const ConvGeom &g, const float *X, int xs,
   const int S = wgrad_frame_blocks(g);
   const int E = (g.Kdim + 1) * g.G;
   float *part = static_cast<float *>(ws);
-  float *tmp = part + (size_t)S * E;
   const size_t lds = (size_t)(4 * 32 * ZS + g.C * g.HW) * 4;
   if (g.G <= 128)
     hipLaunchKernelGGL(conv_wgrad_frame_kernel<1>, dim3(S), dim3(256), lds, st,
@@ -2226,7 +2259,6 @@ int kcnn_conv_wgrad_frame(const ConvGeom &g, const float *X, int xs,
                        g, X, xs, dY, dys, part);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
-  (void)tmp;
   hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, part, S,
                      E, g.Kdim * g.G, g.G, 0, gW, gws, gb, ConvUpdateEpi{});
   return (int)hipGetLastError();
@@ -2247,10 +2279,8 @@ size_t kcnn_conv_bwd_frame_ws(const ConvGeom &g) {
     gc.G = 128;
     return kcnn_conv_bwd_frame_ws(gc);
   }
-  if (g.Kdim > 31 || g.G % 32 != 0 || g.G > 128 || g.G == 0) return 0;
-  if ((g.P < 16 || g.P > 32 * BWD_WAVES * BWD_MAXT || 8 * g.P > BWD_THREADS * BWD_MAXV) &&
-      !kcnn_conv_bwd_x6_eligible(g, true, 0))
-    return 0;
+  if (!kcnn::bwd_chunk_shape_ok(g)) return 0;
+  if (!bwd_fp32_positions_ok(g) && !kcnn_conv_bwd_x6_eligible(g, true, 0)) return 0;
   const int S = (int)frame_grid(g, 1);
   const int E = (g.Kdim + 1) * g.G;
   return (size_t)S * E * 4 + kcnn_reduce_splits_ws(S, E);
@@ -2272,17 +2302,23 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
                            const unsigned char *pmask, int pms, int pc, int ph,
                            const ConvUpdateEpi *ue) {
   if (dX == nullptr && gW == nullptr) return -1;
-  if (g.Kdim > 31 || g.G % 32 != 0 || g.G > 128 || g.G == 0) return -1;
+  if (!kcnn::bwd_chunk_shape_ok(g)) return -1;
+  // the workgroups' gradient partials [S][E] and their reduction
+  const int S = (int)frame_grid(g, 1);
+  const int E = (g.Kdim + 1) * g.G;
+  float *part = static_cast<float *>(ws);
+  if (gW != nullptr) {
+    const size_t need = kcnn_conv_bwd_frame_ws(g);
+    if (need == 0 || ws == nullptr || ws_bytes < need) return -1;
+  }
+  const auto reduce = [&]() {
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, part, S,
+                       E, g.Kdim * g.G, g.G, 0, gW, gws, gb, ue ? *ue : ConvUpdateEpi{});
+    return (int)hipGetLastError();
+  };
   // the bf16x6 kernel (cnsl-conv-x6.hip) where the shape allows; KCNN_BWD_X6=0
   // keeps the fp32-MFMA kernels below
   if (family(kFamBwdX6) && kcnn_conv_bwd_x6_eligible(g, dX != nullptr, pc, ph)) {
-    const int S = (int)frame_grid(g, 1);
-    const int E = (g.Kdim + 1) * g.G;
-    float *part = static_cast<float *>(ws);
-    if (gW != nullptr) {
-      const size_t need = kcnn_conv_bwd_frame_ws(g);
-      if (need == 0 || ws == nullptr || ws_bytes < need) return -1;
-    }
     // The gradient's bf16-MFMA accumulation chains are kept to 16 frames per
     // workgroup: a longer chain grows its error linearly with the frames
     // (c2 stack, prev' normwise against fp64: 2.6e-6 at 4096 frames, 9.2e-6
@@ -2304,25 +2340,14 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
                             nch > 1 ? (int)frame_grid(gc, 1) : S, dx_acc, st,
                             pmask ? pmask + (int64_t)r0 * pms : pmask, pms, pc, ph, c > 0);
     }
-    if (rc || gW == nullptr) return rc;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, part, S,
-                       E, g.Kdim * g.G, g.G, 0, gW, gws, gb, ue ? *ue : ConvUpdateEpi{});
-    return (int)hipGetLastError();
+    return rc || gW == nullptr ? rc : reduce();
   }
   if (ph != 1) return -1;  // 3-D windows: the bf16x6 kernel only
-  if (g.P < 16 || g.P > 32 * BWD_WAVES * BWD_MAXT || 8 * g.P > BWD_THREADS * BWD_MAXV)
-    return -1;
+  if (!bwd_fp32_positions_ok(g)) return -1;
   if (pc == 0 && ((uintptr_t)dY % 16 != 0 || dys % 4 != 0)) return -1;  // 16-B slab loads
   // pc = 2 would stage 16 rows per slab: past the register budget
   if (pc != 0 && !(pc == 4 || pc == 8)) return -1;
-  const int S = (int)frame_grid(g, 1);
-  const int E = (g.Kdim + 1) * g.G;
   const int ZZ = g.Kdim | 1;
-  float *part = static_cast<float *>(ws);
-  if (gW != nullptr) {
-    const size_t need = kcnn_conv_bwd_frame_ws(g);
-    if (need == 0 || ws == nullptr || ws_bytes < need) return -1;
-  }
   // weight-gradient tiles per wave: dgrad tile T belongs to wave T % 8; the
   // wgrad tiles go to the least-loaded waves, so all waves carry the same
   // number of 16-MFMA chunks (deterministic: the same table with or without dX)
@@ -2399,12 +2424,7 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
 #undef KCNN_BWD1
   }
   int rc = (int)hipGetLastError();
-  if (rc || gW == nullptr) return rc;
-  float *tmp = part + (size_t)S * E;
-  (void)tmp;
-  hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, part, S,
-                     E, g.Kdim * g.G, g.G, 0, gW, gws, gb, ue ? *ue : ConvUpdateEpi{});
-  return (int)hipGetLastError();
+  return rc || gW == nullptr ? rc : reduce();
 }
 
 // dX (nullable) and/or gW, gb (nullable) from one pass over dY.  gW == NULL
@@ -2420,16 +2440,8 @@ int kcnn_conv_bwd_frame(const ConvGeom &g, const float *X, int xs,
   // the caller's update request (conv-update.h), for this layer's W
   ConvUpdateEpi *u = kcnn_conv_update_current();
   if (u && !(gW && gb && u->Kdim == g.Kdim && u->G == g.G)) u = nullptr;
-  if (g.G <= 128) {
-    const int rc = bwd_frame_chunk(g, X, xs, dY, dys, K, ks, dX, dxs, gW, gws, gb, ws,
-                                   ws_bytes, 0, st, pmask, pms, pc, ph, u);
-    if (rc == 0 && u) u->applied = 1;
-    return rc;
-  }
-  if (g.G % 32 != 0 || (int64_t)g.G * g.P * 4 % 16 != 0) return -1;
-  for (int g0 = 0; g0 < g.G; g0 += 128) {
-    ConvGeom gc = g;
-    gc.G = g.G - g0 < 128 ? g.G - g0 : 128;
+  if (g.G > 128 && (g.G % 32 != 0 || (int64_t)g.G * g.P * 4 % 16 != 0)) return -1;
+  const int rc = for_filter_chunks(g, [&](const ConvGeom &gc, int g0) {
     // pooled rows of P / ph values when pc, masks of 1 (ph == 1) or 2 bytes
     const int64_t dofs = pc ? (int64_t)(g0 / pc) * (g.P / ph) : (int64_t)g0 * g.P;
     const int64_t mofs = dofs * (ph > 1 ? 2 : 1);
@@ -2441,18 +2453,13 @@ int kcnn_conv_bwd_frame(const ConvGeom &g, const float *X, int xs,
       uc.b += g0;
       uc.G = gc.G;
     }
-    const int rc = bwd_frame_chunk(
-        gc, X, xs, dY + dofs, dys, K + g0, ks, dX, dxs, gW ? gW + g0 : nullptr, gws,
-        gb ? gb + g0 : nullptr, ws, ws_bytes, g0 > 0, st, pmask ? pmask + mofs : nullptr,
-        pms, pc, ph, u ? &uc : nullptr);
-    if (rc) {
-      // only the first chunk may decline (nothing written yet); a later
-      // failure is a launch error
-      return g0 == 0 ? rc : (rc < 0 ? (int)hipErrorLaunchFailure : rc);
-    }
-  }
-  if (u) u->applied = 1;
-  return 0;
+    return bwd_frame_chunk(gc, X, xs, dY + dofs, dys, K + g0, ks, dX, dxs,
+                           gW ? gW + g0 : nullptr, gws, gb ? gb + g0 : nullptr, ws, ws_bytes,
+                           g0 > 0, st, pmask ? pmask + mofs : nullptr, pms, pc, ph,
+                           u ? &uc : nullptr);
+  });
+  if (rc == 0 && u) u->applied = 1;
+  return rc;
 }
 
 size_t kcnn_reduce_splits_ws(int S, int E) {
@@ -2460,15 +2467,13 @@ size_t kcnn_reduce_splits_ws(int S, int E) {
 }
 
 // Generic: in [S][E] -> out (with the gW/gb mapping of the implicit-GEMM
-// wgrad: e = g*Kdim + k for e < G*Kdim); tmp is unused (one pass).  The
+// wgrad: e = g*Kdim + k for e < G*Kdim) in one pass.  The
 // caller's update request for this layer's W (conv-update.h: Kdim = inner,
 // G = nw / inner) is applied here instead of storing gW / gb, as the frame
 // kernels' reduction does (the long-kernel weight gradients run after the
 // data gradient, so W is stepped after its last read).
-int kcnn_reduce_splits_wgrad(const float *in, int S, int E, float *tmp, int nw,
-                             int inner, float *gW, int gws, float *gb,
-                             hipStream_t st) {
-  (void)tmp;
+int kcnn_reduce_splits_wgrad(const float *in, int S, int E, int nw, int inner, float *gW,
+                             int gws, float *gb, hipStream_t st) {
   ConvUpdateEpi *u = kcnn_conv_update_current();
   if (u && !(gW && gb && inner > 0 && u->Kdim == inner && (int64_t)u->G * inner == nw &&
              E == nw + u->G))
@@ -2488,9 +2493,7 @@ int kcnn_reduce_splits_pass1(const float *in, int S, int E, float *tmp,
   return (int)hipGetLastError();
 }
 
-int kcnn_reduce_splits(const float *in, int S, int E, float *tmp, float *out,
-                       hipStream_t st) {
-  (void)tmp;
+int kcnn_reduce_splits(const float *in, int S, int E, float *out, hipStream_t st) {
   hipLaunchKernelGGL(reduce_splits_kernel, dim3((E + 63) / 64), dim3(256), 0, st, in, S, E,
                      E, E, 0, out, 0, nullptr, ConvUpdateEpi{});
   return (int)hipGetLastError();

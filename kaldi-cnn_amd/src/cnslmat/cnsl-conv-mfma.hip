@@ -35,6 +35,7 @@ using kcnn::FastDiv;
 using kcnn::ConvGeom;
 using kcnn::floatx16;
 using kcnn::make_geom;
+using kcnn::use_direct;
 
 namespace {
 
@@ -810,8 +811,6 @@ IgemmPlan plan_igemm(const ConvGeom &g) {
   return pl;
 }
 
-bool use_direct(const ConvGeom &g, int concat) { return concat && g.G <= 8; }
-
 struct WgradPlan {
   int S;
   int64_t t_per_split;
@@ -913,7 +912,142 @@ bool use_dgrad_scatter(const ConvGeom &g) {
 
 size_t zbytes_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 
-size_t dgrad_scatter_ws(const ConvGeom &g) {
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// The family's launchers (conv-geom.h; the routes of conv-dispatch.cc):
+// 0 launched, -1 declined with nothing launched, > 0 a HIP error.
+
+int kcnn_conv_direct(const ConvGeom &g, int concat, const float *X, int xs, const float *K,
+                     int ks, const float *bias, float *out, int os, hipStream_t st) {
+  if (!use_direct(g, concat)) return -1;
+  const unsigned blocks = (unsigned)((g.M + 255) / 256);
+#define KCNN_DIRECT(NG)                                                                  \
+  hipLaunchKernelGGL(conv_direct_smallg_kernel<NG>, dim3(blocks), dim3(256), 0, st, g, X, \
+                     xs, K, ks, bias, out, os)
+  if (g.G <= 1) KCNN_DIRECT(1);
+  else if (g.G <= 2) KCNN_DIRECT(2);
+  else if (g.G <= 4) KCNN_DIRECT(4);
+  else KCNN_DIRECT(8);
+#undef KCNN_DIRECT
+  return kcnn::launch_status();
+}
+
+// Implicit GEMM v2: X and K addressable with 32-bit byte offsets, 16-B rows
+// of K, tap masks for padded maps need kh*kw <= 32.
+int kcnn_conv_igemm2(const ConvGeom &g, const float *X, int xs, const float *K, int ks,
+                     const float *bias, float *out, int os, int relu, hipStream_t st) {
+  const bool padded = g.pad_h > 0 || g.pad_w > 0;
+  if (!((int64_t)g.R * xs * 4 < ((int64_t)1 << 31) &&
+        (int64_t)g.Kdim * ks * 4 < ((int64_t)1 << 31) && g.G % 4 == 0 && ks % 4 == 0 &&
+        (uintptr_t)K % 16 == 0 && (!padded || g.kh * g.kw <= 32)))
+    return -1;
+  const int wgg = g.G > 64 ? 2 : 1;
+  const int bg = 64 * wgg, bm = 64 * (4 / wgg);
+  dim3 grid2((unsigned)((g.M + bm - 1) / bm), (unsigned)((g.G + bg - 1) / bg));
+  const bool tab = (g.Kdim + 15) / 16 * 16 <= IG2_KTAB &&
+                   (int64_t)g.HW * g.C < (1 << 28) && (!padded || g.kh * g.kw <= 31);
+#define KCNN_IG2(W_, P_)                                                                   \
+  do {                                                                                     \
+    if (tab)                                                                               \
+      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, true>), grid2, dim3(256), 0, st, g, X, \
+                         xs, K, ks, bias, out, os, relu);                                   \
+    else                                                                                   \
+      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, false>), grid2, dim3(256), 0, st, g,  \
+                         X, xs, K, ks, bias, out, os, relu);                                \
+  } while (0)
+  if (wgg == 2) {
+    if (padded) KCNN_IG2(2, true); else KCNN_IG2(2, false);
+  } else {
+    if (padded) KCNN_IG2(1, true); else KCNN_IG2(1, false);
+  }
+#undef KCNN_IG2
+  return kcnn::launch_status();
+}
+
+size_t kcnn_conv_igemm_ws(const ConvGeom &g) { return plan_igemm(g).ws_bytes; }
+
+// The first implicit GEMM: every geometry, either output layout.  Splits K
+// when ws holds kcnn_conv_igemm_ws(g) bytes, else runs unsplit.
+int kcnn_conv_igemm(const ConvGeom &g, const float *X, int xs, const float *K, int ks,
+                    const float *bias, float *out, int os, int concat, void *ws,
+                    size_t ws_bytes, hipStream_t st) {
+  IgemmPlan pl = plan_igemm(g);
+  if (pl.S > 1 && (ws == nullptr || ws_bytes < pl.ws_bytes)) {
+    pl.S = 1;
+    pl.k_per_split = (g.Kdim + IG_BK - 1) / IG_BK * IG_BK;
+  }
+  dim3 grid((unsigned)((g.M + IG_BM - 1) / IG_BM), (unsigned)((g.G + IG_BG - 1) / IG_BG),
+            (unsigned)pl.S);
+  if (pl.S > 1) {
+    float *part = static_cast<float *>(ws);
+    hipLaunchKernelGGL(conv_igemm_kernel<ST_PARTIAL>, grid, dim3(256), 0, st, g, X, xs, K, ks,
+                       nullptr, nullptr, 0, part, pl.k_per_split);
+    int rc = kcnn::launch_status();
+    if (rc) return rc;
+    // pass 1 (groups of 32 splits) into tmp, pass 2 = reduce + store epilogue
+    const int E = (int)(g.G * g.M);
+    const int Q = (pl.S + 31) / 32;
+    float *tmp = part + (size_t)pl.S * E;
+    rc = kcnn_reduce_splits_pass1(part, pl.S, E, tmp, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(kcnn::grid_for((int64_t)g.G * g.M)),
+                       dim3(256), 0, st, g, tmp, Q, bias, out, os, concat);
+  } else if (concat) {
+    hipLaunchKernelGGL(conv_igemm_kernel<ST_CONCAT>, grid, dim3(256), 0, st, g, X, xs, K, ks,
+                       bias, out, os, nullptr, pl.k_per_split);
+  } else {
+    hipLaunchKernelGGL(conv_igemm_kernel<ST_PLAIN>, grid, dim3(256), 0, st, g, X, xs, K, ks,
+                       nullptr, out, os, nullptr, pl.k_per_split);
+  }
+  return kcnn::launch_status();
+}
+
+size_t kcnn_conv_wgrad2_ws(const ConvGeom &g, int xs, int dys) {
+  Wgrad2Plan pl;
+  return plan_wgrad2(g, xs, dys, pl) ? pl.ws_bytes : 0;
+}
+
+// conv_wgrad2_kernel's partials, then their reduction into gW / gb.
+int kcnn_conv_wgrad2(const ConvGeom &g, const float *X, int xs, const float *dY, int dys,
+                     float *gW, int gws, float *gb, void *ws, size_t ws_bytes,
+                     hipStream_t st) {
+  Wgrad2Plan pl;
+  if (!plan_wgrad2(g, xs, dys, pl) || ws == nullptr || ws_bytes < pl.ws_bytes) return -1;
+  float *part = static_cast<float *>(ws);
+  const int rc = launch_wgrad2(g, pl, X, xs, dY, dys, part, st);
+  if (rc) return rc;
+  return kcnn_reduce_splits_wgrad(part, pl.S, g.G * g.Kdim + g.G, g.G * g.Kdim, g.Kdim, gW,
+                                  gws, gb, st);
+}
+
+size_t kcnn_conv_wgrad_ws(const ConvGeom &g) { return plan_wgrad(g).ws_bytes; }
+
+// The first weight gradient: every geometry (M == 0 gives zeros); never
+// declines, a workspace under kcnn_conv_wgrad_ws(g) is an invalid value.
+int kcnn_conv_wgrad(const ConvGeom &g, const float *X, int xs, const float *dY, int dys,
+                    float *gW, int gws, float *gb, void *ws, size_t ws_bytes,
+                    hipStream_t st) {
+  WgradPlan pl = plan_wgrad(g);
+  if (ws == nullptr || ws_bytes < pl.ws_bytes) return (int)hipErrorInvalidValue;
+  const int E = g.G * g.Kdim + g.G;
+  float *ws_w = static_cast<float *>(ws);
+  float *ws_b = ws_w + (size_t)g.G * g.Kdim;
+  if (g.M == 0) {
+    if (hipMemsetAsync(ws_w, 0, (size_t)pl.S * E * sizeof(float), st) != hipSuccess)
+      return (int)hipErrorInvalidValue;
+  } else {
+    dim3 grid((unsigned)pl.S, (unsigned)((g.G + WG_BG - 1) / WG_BG),
+              (unsigned)((g.Kdim + WG_BK - 1) / WG_BK));
+    hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, st, g, X, xs, dY, dys, ws_w,
+                       ws_b, pl.t_per_split);
+  }
+  const int rc = kcnn::launch_status();
+  if (rc) return rc;
+  return kcnn_reduce_splits_wgrad(ws_w, pl.S, E, g.G * g.Kdim, g.Kdim, gW, gws, gb, st);
+}
+
+size_t kcnn_conv_dgrad_scatter_ws(const ConvGeom &g) {
   if (!use_dgrad_scatter(g)) return 0;
   const int wts = (g.Kdim + 3) & ~3;
   const size_t wt = zbytes_pad((size_t)g.G * wts * 4);
@@ -922,23 +1056,13 @@ size_t dgrad_scatter_ws(const ConvGeom &g) {
   return wt + z + plan_igemm(g1).ws_bytes;
 }
 
-}  // namespace
-
-extern "C" {
-int hipF_conv2d(const float *in, MatrixDim in_dim, int in_height, int in_width,
-                int in_channel, int pad_h, int pad_w, const float *kernel,
-                MatrixDim kernel_dim, int kernel_height, int kernel_width,
-                int group, const float *bias, float *out, MatrixDim out_dim,
-                int concat, void *workspace, size_t workspace_bytes,
-                kcnn_stream_t stream);
-}
-
-namespace {
-
-int dgrad_scatter(const ConvGeom &g, const float *dY, MatrixDim dyd,
-                  const float *W, MatrixDim wd, float *dX, MatrixDim dxd,
-                  void *ws, size_t ws_bytes, kcnn_stream_t stream) {
-  hipStream_t st = kcnn::as_stream(stream);
+// W transposed, Z = the 1x1 convolution of dY by it (hipF_conv2d: the forward
+// routes), then col2im of Z into dX.
+int kcnn_conv_dgrad_scatter(const ConvGeom &g, const float *dY, int dys, const float *W,
+                            int ks, float *dX, int dxs, void *ws, size_t ws_bytes,
+                            hipStream_t st) {
+  if (!use_dgrad_scatter(g) || ws == nullptr || ws_bytes < kcnn_conv_dgrad_scatter_ws(g))
+    return -1;
   const int wts = (g.Kdim + 3) & ~3;
   float *wt = static_cast<float *>(ws);
   const size_t wt_b = zbytes_pad((size_t)g.G * wts * 4);
@@ -946,17 +1070,18 @@ int dgrad_scatter(const ConvGeom &g, const float *dY, MatrixDim dyd,
   const size_t z_b = zbytes_pad((size_t)g.R * g.Kdim * g.P * 4);
   const int64_t nt = (int64_t)g.Kdim * g.G;
   hipLaunchKernelGGL(conv_transpose_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256),
-                     0, st, W, g.Kdim, g.G, wd.stride, wt, wts);
+                     0, st, W, g.Kdim, g.G, ks, wt, wts);
   int rc = kcnn::launch_status();
   if (rc) return rc;
-  MatrixDim wtd, zd;
+  MatrixDim dyd, wtd, zd;
+  dyd.rows = g.R; dyd.cols = g.P * g.G; dyd.stride = dys;
   wtd.rows = g.G; wtd.cols = g.Kdim; wtd.stride = wts;
   zd.rows = g.R; zd.cols = g.Kdim * g.P; zd.stride = zd.cols;
   // Z[n][k*P + p] = sum_g dY[n][g*P + p] W[k][g]: a 1x1 convolution of the
   // (oh x ow x G) map dY into Kdim output maps.
-  rc = hipF_conv2d(dY, dyd, g.oh, g.ow, g.G, 0, 0, wt, wtd, 1, 1, g.Kdim, nullptr, z,
-                   zd, 1, static_cast<char *>(ws) + wt_b + z_b, ws_bytes - wt_b - z_b,
-                   stream);
+  rc = hipF_conv2d(dY, dyd, g.oh, g.ow, g.G, 0, 0, wt, wtd, 1, 1, g.Kdim, nullptr, z, zd, 1,
+                   static_cast<char *>(ws) + wt_b + z_b, ws_bytes - wt_b - z_b,
+                   reinterpret_cast<kcnn_stream_t>(st));
   if (rc) return rc;
   // one wave per (frame, channel) pays off for long runs only (c5 C2: 864
   // floats); short ones (nnet.config C5/C6: 12) go element-wise
@@ -966,574 +1091,12 @@ int dgrad_scatter(const ConvGeom &g, const float *dY, MatrixDim dyd,
     const bool vec = (g.kh * g.kw * g.P) % 4 == 0 && zd.stride % 4 == 0;
     hipLaunchKernelGGL(conv_col2im_plane_kernel,
                        dim3((unsigned)(units < 256 * 24 ? units : 256 * 24)), dim3(64), zlds,
-                       st, g, z, zd.stride, dX, dxd.stride, vec ? 1 : 0);
+                       st, g, z, zd.stride, dX, dxs, vec ? 1 : 0);
     return kcnn::launch_status();
   }
   const int64_t ne = (int64_t)g.R * g.C * g.HW;
   hipLaunchKernelGGL(conv_col2im_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0,
-                     st, g, z, zd.stride, dX, dxd.stride);
+                     st, g, z, zd.stride, dX, dxs);
   return kcnn::launch_status();
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t hipF_conv2d_workspace_bytes(MatrixDim in_dim, int in_height,
-                                   int in_width, int in_channel, int pad_h,
-                                   int pad_w, int kernel_height,
-                                   int kernel_width, int group) {
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0) return 0;
-  if (use_direct(g, 1)) return 0;  // caller decides concat; direct needs none
-  return plan_igemm(g).ws_bytes;
-}
-
-// Conv2D(concat) + bias + channel-only Maxpool_prop in one pass (see
-// include/cnsl-hip-kernels.h).  Returns -1 (nothing launched) when the
-// geometry is not covered, so the caller runs the two components unfused.
-int hipF_conv2d_maxpool(const float *in, MatrixDim in_dim, int in_height,
-                        int in_width, int in_channel, int pad_h, int pad_w,
-                        const float *kernel, MatrixDim kernel_dim,
-                        int kernel_height, int kernel_width, int group,
-                        const float *bias, float *out, MatrixDim out_dim,
-                        float *pool, MatrixDim pool_dim, unsigned char *mask,
-                        int mask_stride, int pool_channel_dim,
-                        kcnn_stream_t stream) {
-  return kcnn_conv2d_maxpool_stats(in, in_dim, in_height, in_width, in_channel, pad_h, pad_w,
-                                   kernel, kernel_dim, kernel_height, kernel_width, group,
-                                   bias, out, out_dim, pool, pool_dim, mask, mask_stride,
-                                   pool_channel_dim, stream, nullptr);
-}
-
-// The scratch words for the pooled output's statistics (pool-stats.h) of
-// hipF_conv2d_maxpool's geometry; 0 when the layer takes no frame kernel.
-size_t kcnn_conv2d_maxpool_stats_words(int rows, int in_height, int in_width,
-                                       int in_channel, int kernel_height, int kernel_width,
-                                       int group, int pool_channel_dim) {
-  ConvGeom g = make_geom(rows, in_height, in_width, in_channel, 0, 0, kernel_height,
-                         kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || pool_channel_dim <= 0) return 0;
-  return kcnn_pool_stats_partial_words(g, pool_channel_dim);
-}
-
-// hipF_conv2d_maxpool plus the pooled output's statistics when its kernel
-// gives them (stats nullable; stats->produced tells)
-int kcnn_conv2d_maxpool_stats(const float *in, MatrixDim in_dim, int in_height,
-                              int in_width, int in_channel, int pad_h, int pad_w,
-                              const float *kernel, MatrixDim kernel_dim,
-                              int kernel_height, int kernel_width, int group,
-                              const float *bias, float *out, MatrixDim out_dim,
-                              float *pool, MatrixDim pool_dim, unsigned char *mask,
-                              int mask_stride, int pool_channel_dim,
-                              kcnn_stream_t stream, PoolStatsOut *stats) {
-  if (stats) stats->produced = 0;
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group ||
-      out_dim.rows != g.R || out_dim.cols != g.P * group ||
-      pool_channel_dim <= 0 || pool_dim.rows != g.R ||
-      pool_dim.cols * pool_channel_dim != out_dim.cols ||
-      mask_stride < pool_dim.cols)
-    return (int)hipErrorInvalidValue;
-  if (g.R == 0) return 0;
-  if (g.M >= ((int64_t)1 << 31)) return -1;
-  return kcnn_conv_fwd_frame_pool(g, in, in_dim.stride, kernel, kernel_dim.stride,
-                                  bias, out, out_dim.stride, pool, pool_dim.stride,
-                                  mask, mask_stride, pool_channel_dim,
-                                  kcnn::as_stream(stream), 1, 1, stats) == 0 ? 0 : -1;
-}
-
-int hipF_conv2d_maxpool3d(const float *in, MatrixDim in_dim, int in_height,
-                          int in_width, int in_channel, int pad_h, int pad_w,
-                          const float *kernel, MatrixDim kernel_dim,
-                          int kernel_height, int kernel_width, int group,
-                          const float *bias, float *out, MatrixDim out_dim,
-                          float *pool, MatrixDim pool_dim, unsigned short *mask,
-                          int mask_stride, int pool_height_dim, int pool_width_dim,
-                          int pool_channel_dim, kcnn_stream_t stream) {
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  const int ph = pool_height_dim, pw = pool_width_dim, pc = pool_channel_dim;
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group ||
-      out_dim.rows != g.R || out_dim.cols != g.P * group || ph <= 0 || pw <= 0 ||
-      pc <= 0 || pool_dim.rows != g.R ||
-      (int64_t)pool_dim.cols * ph * pw * pc != out_dim.cols || mask_stride < pool_dim.cols)
-    return (int)hipErrorInvalidValue;
-  if (g.R == 0) return 0;
-  if (g.M >= ((int64_t)1 << 31)) return -1;
-  hipStream_t st = kcnn::as_stream(stream);
-  if (kcnn_conv_fwd_frame_pool(g, in, in_dim.stride, kernel, kernel_dim.stride, bias, out,
-                               out_dim.stride, pool, pool_dim.stride,
-                               reinterpret_cast<unsigned char *>(mask), mask_stride, pc, st,
-                               ph, pw) == 0)
-    return 0;
-  // long kernels: the implicit GEMM with the pool in its epilogue, for the
-  // shapes whose unfused convolution is that same kernel (conv2d_impl: not
-  // in the frame kernels' range, not the small-filter direct kernel)
-  if ((g.Kdim <= 64 && g.P >= 16) || use_direct(g, 1)) return -1;
-  return kcnn_conv_igemm_x6_pool(g, in, in_dim.stride, kernel, kernel_dim.stride, bias, out,
-                                 out_dim.stride, pool, pool_dim.stride, mask, mask_stride, ph,
-                                 pw, pc, st) == 0
-             ? 0
-             : -1;
-}
-
-// relu: the implicit-GEMM v2 path only (-1 for shapes that take another)
-static int conv2d_impl(const float *in, MatrixDim in_dim, int in_height, int in_width,
-                       int in_channel, int pad_h, int pad_w, const float *kernel,
-                       MatrixDim kernel_dim, int kernel_height, int kernel_width,
-                       int group, const float *bias, float *out, MatrixDim out_dim,
-                       int concat, void *workspace, size_t workspace_bytes,
-                       kcnn_stream_t stream, int relu) {
-  hipStream_t st = kcnn::as_stream(stream);
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group)
-    return (int)hipErrorInvalidValue;
-  if (concat ? (out_dim.rows != g.R || out_dim.cols != g.P * group)
-             : (out_dim.rows != g.M || out_dim.cols != group))
-    return (int)hipErrorInvalidValue;
-  if (g.M == 0) return 0;
-  if (g.M >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  if (!concat) bias = nullptr;
-
-  // shapes in the frame kernels' range (kcnn_conv_fwd_frame) run unfused:
-  // the fused result then comes from the same kernel as the unfused one
-  if (relu && g.Kdim <= 64 && g.P >= 16) return -1;
-  // likewise the small-filter-count shapes the direct kernel serves
-  if (relu && use_direct(g, concat)) return -1;
-  if (!relu && concat && kcnn_conv_fwd_frame(g, in, in_dim.stride, kernel,
-                                             kernel_dim.stride, bias, out,
-                                             out_dim.stride, st) == 0)
-    return 0;
-  if (!relu && use_direct(g, concat)) {
-    const unsigned blocks = (unsigned)((g.M + 255) / 256);
-#define KCNN_DIRECT(NG)                                                        \
-  hipLaunchKernelGGL(conv_direct_smallg_kernel<NG>, dim3(blocks), dim3(256), 0, \
-                     st, g, in, in_dim.stride, kernel, kernel_dim.stride, bias, \
-                     out, out_dim.stride)
-    if (g.G <= 1) KCNN_DIRECT(1);
-    else if (g.G <= 2) KCNN_DIRECT(2);
-    else if (g.G <= 4) KCNN_DIRECT(4);
-    else KCNN_DIRECT(8);
-#undef KCNN_DIRECT
-    return kcnn::launch_status();
-  }
-
-  // the implicit GEMM on the bf16 MFMAs (exact three-way operand splits)
-  if (concat && kcnn_conv_igemm_x6(g, in, in_dim.stride, kernel, kernel_dim.stride, bias,
-                                   out, out_dim.stride, relu, st) == 0)
-    return 0;
-  // implicit GEMM v2 (fp32 MFMA): concat layout, X addressable with 32-bit
-  // offsets, tap masks for padded maps need kh*kw <= 32
-  const bool padded = g.pad_h > 0 || g.pad_w > 0;
-  const int wgg = g.G > 64 ? 2 : 1;
-  if (concat && (int64_t)g.R * in_dim.stride * 4 < ((int64_t)1 << 31) &&
-      (int64_t)g.Kdim * kernel_dim.stride * 4 < ((int64_t)1 << 31) &&
-      g.G % 4 == 0 && kernel_dim.stride % 4 == 0 &&
-      (uintptr_t)kernel % 16 == 0 && (!padded || g.kh * g.kw <= 32)) {
-    const int bg = 64 * wgg, bm = 64 * (4 / wgg);
-    dim3 grid2((unsigned)((g.M + bm - 1) / bm), (unsigned)((g.G + bg - 1) / bg));
-    const bool tab = (g.Kdim + 15) / 16 * 16 <= IG2_KTAB &&
-                     (int64_t)g.HW * g.C < (1 << 28) && (!padded || g.kh * g.kw <= 31);
-#define KCNN_IG2(W_, P_)                                                                  \
-  do {                                                                                    \
-    if (tab)                                                                              \
-      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, true>), grid2, dim3(256), 0, st, g,  \
-                         in, in_dim.stride, kernel, kernel_dim.stride, bias, out,          \
-                         out_dim.stride, relu);                                            \
-    else                                                                                  \
-      hipLaunchKernelGGL((conv_igemm2_kernel<W_, P_, false>), grid2, dim3(256), 0, st, g, \
-                         in, in_dim.stride, kernel, kernel_dim.stride, bias, out,          \
-                         out_dim.stride, relu);                                            \
-  } while (0)
-    if (wgg == 2) {
-      if (padded) KCNN_IG2(2, true); else KCNN_IG2(2, false);
-    } else {
-      if (padded) KCNN_IG2(1, true); else KCNN_IG2(1, false);
-    }
-#undef KCNN_IG2
-    return kcnn::launch_status();
-  }
-  if (relu) return -1;
-
-  IgemmPlan pl = plan_igemm(g);
-  if (pl.S > 1 && (workspace == nullptr || workspace_bytes < pl.ws_bytes)) {
-    pl.S = 1;
-    pl.k_per_split = (g.Kdim + IG_BK - 1) / IG_BK * IG_BK;
-  }
-  dim3 grid((unsigned)((g.M + IG_BM - 1) / IG_BM),
-            (unsigned)((g.G + IG_BG - 1) / IG_BG), (unsigned)pl.S);
-  if (pl.S > 1) {
-    float *ws = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(conv_igemm_kernel<ST_PARTIAL>, grid, dim3(256), 0, st, g,
-                       in, in_dim.stride, kernel, kernel_dim.stride, nullptr,
-                       nullptr, 0, ws, pl.k_per_split);
-    int rc = kcnn::launch_status();
-    if (rc) return rc;
-    // pass 1 (groups of 32 splits) into tmp, pass 2 = reduce + store epilogue
-    const int E = (int)(g.G * g.M);
-    const int Q = (pl.S + 31) / 32;
-    float *tmp = ws + (size_t)pl.S * E;
-    rc =kcnn_reduce_splits_pass1(ws, pl.S, E, tmp, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel,
-                       dim3(kcnn::grid_for((int64_t)g.G * g.M)), dim3(256), 0,
-                       st, g, tmp, Q, bias, out, out_dim.stride, concat);
-  } else if (concat) {
-    hipLaunchKernelGGL(conv_igemm_kernel<ST_CONCAT>, grid, dim3(256), 0, st, g,
-                       in, in_dim.stride, kernel, kernel_dim.stride, bias, out,
-                       out_dim.stride, nullptr, pl.k_per_split);
-  } else {
-    hipLaunchKernelGGL(conv_igemm_kernel<ST_PLAIN>, grid, dim3(256), 0, st, g,
-                       in, in_dim.stride, kernel, kernel_dim.stride, nullptr,
-                       out, out_dim.stride, nullptr, pl.k_per_split);
-  }
-  return kcnn::launch_status();
-}
-
-int hipF_conv2d(const float *in, MatrixDim in_dim, int in_height, int in_width,
-                int in_channel, int pad_h, int pad_w, const float *kernel,
-                MatrixDim kernel_dim, int kernel_height, int kernel_width,
-                int group, const float *bias, float *out, MatrixDim out_dim,
-                int concat, void *workspace, size_t workspace_bytes,
-                kcnn_stream_t stream) {
-  return conv2d_impl(in, in_dim, in_height, in_width, in_channel, pad_h, pad_w, kernel,
-                     kernel_dim, kernel_height, kernel_width, group, bias, out, out_dim,
-                     concat, workspace, workspace_bytes, stream, 0);
-}
-
-int hipF_conv2d_relu(const float *in, MatrixDim in_dim, int in_height, int in_width,
-                     int in_channel, int pad_h, int pad_w, const float *kernel,
-                     MatrixDim kernel_dim, int kernel_height, int kernel_width,
-                     int group, const float *bias, float *out, MatrixDim out_dim,
-                     kcnn_stream_t stream) {
-  return conv2d_impl(in, in_dim, in_height, in_width, in_channel, pad_h, pad_w, kernel,
-                     kernel_dim, kernel_height, kernel_width, group, bias, out, out_dim,
-                     1, nullptr, 0, stream, 1);
-}
-
-size_t hipF_conv2d_wgrad_workspace_bytes(MatrixDim in_dim, int in_height,
-                                         int in_width, int in_channel,
-                                         int pad_h, int pad_w,
-                                         int kernel_height, int kernel_width,
-                                         int group) {
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0) return 0;
-  size_t a = kcnn_conv_wgrad_frame_ws(g);
-  const size_t b = plan_wgrad(g).ws_bytes, c = kcnn_conv_bwd_frame_ws(g);
-  if (b > a) a = b;
-  Wgrad2Plan p2;
-  if (plan_wgrad2(g, in_dim.stride > 0 ? in_dim.stride : g.HW * in_channel,
-                  g.P * group, p2) && p2.ws_bytes > a)
-    a = p2.ws_bytes;
-  int xS, xfps;
-  size_t xb;
-  if (kcnn_conv_wgrad_x6_plan(g, in_dim.stride > 0 ? in_dim.stride : g.HW * in_channel,
-                              g.P * group, xS, xfps, xb) && xb > a)
-    a = xb;
-  return c > a ? c : a;
-}
-
-int hipF_conv2d_wgrad(const float *in, MatrixDim in_dim, int in_height,
-                      int in_width, int in_channel, int pad_h, int pad_w,
-                      const float *out_deriv, MatrixDim out_deriv_dim,
-                      int kernel_height, int kernel_width, int group,
-                      float *grad_W, MatrixDim grad_W_dim, float *grad_b,
-                      void *workspace, size_t workspace_bytes,
-                      kcnn_stream_t stream) {
-  hipStream_t st = kcnn::as_stream(stream);
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      out_deriv_dim.rows != g.R || out_deriv_dim.cols != g.P * group ||
-      grad_W_dim.rows != g.Kdim || grad_W_dim.cols != group)
-    return (int)hipErrorInvalidValue;
-  if (g.M >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  // the fused backward's gradient-only pass (one stream of dY)
-  if (g.M > 0 && kcnn_conv_bwd_frame(g, in, in_dim.stride, out_deriv,
-                                     out_deriv_dim.stride, nullptr, 0, nullptr, 0,
-                                     grad_W, grad_W_dim.stride, grad_b, workspace,
-                                     workspace_bytes, st) == 0)
-    return 0;
-  if (g.M > 0 && kcnn_conv_wgrad_frame(g, in, in_dim.stride, out_deriv,
-                                       out_deriv_dim.stride, grad_W,
-                                       grad_W_dim.stride, grad_b, workspace,
-                                       workspace_bytes, st) == 0)
-    return 0;
-  {
-    // the long-kernel weight gradient on the bf16 MFMAs
-    int xS, xfps;
-    size_t xb;
-    if (g.M > 0 &&
-        kcnn_conv_wgrad_x6_plan(g, in_dim.stride, out_deriv_dim.stride, xS, xfps, xb) &&
-        workspace != nullptr && workspace_bytes >= xb) {
-      const int E = g.G * g.Kdim + g.G;
-      float *part = static_cast<float *>(workspace);
-      int rc = kcnn_conv_wgrad_x6(g, in, in_dim.stride, out_deriv, out_deriv_dim.stride,
-                                  part, xS, xfps, st);
-      if (rc) return rc;
-      return kcnn_reduce_splits_wgrad(part, xS, E, part + (size_t)xS * E, g.G * g.Kdim,
-                                      g.Kdim, grad_W, grad_W_dim.stride, grad_b, st);
-    }
-  }
-  Wgrad2Plan p2;
-  if (g.M > 0 && plan_wgrad2(g, in_dim.stride, out_deriv_dim.stride, p2) &&
-      workspace != nullptr && workspace_bytes >= p2.ws_bytes) {
-    const int E = g.G * g.Kdim + g.G;
-    float *part = static_cast<float *>(workspace);
-    int rc = launch_wgrad2(g, p2, in, in_dim.stride, out_deriv, out_deriv_dim.stride,
-                           part, st);
-    if (rc) return rc;
-    return kcnn_reduce_splits_wgrad(part, p2.S, E, part + (size_t)p2.S * E,
-                                    g.G * g.Kdim, g.Kdim, grad_W, grad_W_dim.stride,
-                                    grad_b, st);
-  }
-  WgradPlan pl = plan_wgrad(g);
-  if (workspace == nullptr || workspace_bytes < pl.ws_bytes)
-    return (int)hipErrorInvalidValue;
-  const int E = g.G * g.Kdim + g.G;
-  float *ws_w = static_cast<float *>(workspace);
-  float *ws_b = ws_w + (size_t)g.G * g.Kdim;
-  float *tmp = ws_w + (size_t)pl.S * E;
-  if (g.M == 0) {
-    if (hipMemsetAsync(ws_w, 0, (size_t)pl.S * E * sizeof(float), st) != hipSuccess)
-      return (int)hipErrorInvalidValue;
-  } else {
-    dim3 grid((unsigned)pl.S, (unsigned)((g.G + WG_BG - 1) / WG_BG),
-              (unsigned)((g.Kdim + WG_BK - 1) / WG_BK));
-    hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, st, g, in,
-                       in_dim.stride, out_deriv, out_deriv_dim.stride, ws_w,
-                       ws_b, pl.t_per_split);
-  }
-  int rc = kcnn::launch_status();
-  if (rc) return rc;
-  return kcnn_reduce_splits_wgrad(ws_w, pl.S, E, tmp, g.G * g.Kdim, g.Kdim,
-                                  grad_W, grad_W_dim.stride, grad_b, st);
-}
-
-size_t hipF_conv2d_dgrad_workspace_bytes(MatrixDim out_deriv_dim, int in_height,
-                                         int in_width, int in_channel,
-                                         int pad_h, int pad_w,
-                                         int kernel_height, int kernel_width,
-                                         int group) {
-  ConvGeom g = make_geom(out_deriv_dim.rows, in_height, in_width, in_channel,
-                         pad_h, pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0) return 0;
-  // fallback: flipped kernel + implicit GEMM over the virtually padded dY
-  ConvGeom gt = make_geom(out_deriv_dim.rows, g.oh, g.ow, group,
-                          kernel_height - 1 - pad_h, kernel_width - 1 - pad_w,
-                          kernel_height, kernel_width, in_channel);
-  const size_t flip_bytes = (size_t)kernel_height * kernel_width * group *
-                            in_channel * sizeof(float);
-  const size_t flip_pad = (flip_bytes + 255) & ~(size_t)255;
-  const size_t a = flip_pad + (use_direct(gt, 1) ? 0 : plan_igemm(gt).ws_bytes);
-  const size_t b = dgrad_scatter_ws(g);
-  return b > a ? b : a;
-}
-
-int hipF_conv2d_dgrad(const float *out_deriv, MatrixDim out_deriv_dim,
-                      int in_height, int in_width, int in_channel, int pad_h,
-                      int pad_w, const float *kernel, MatrixDim kernel_dim,
-                      int kernel_height, int kernel_width, int group,
-                      float *in_deriv, MatrixDim in_deriv_dim, void *workspace,
-                      size_t workspace_bytes, kcnn_stream_t stream) {
-  hipStream_t st = kcnn::as_stream(stream);
-  ConvGeom g = make_geom(out_deriv_dim.rows, in_height, in_width, in_channel,
-                         pad_h, pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || out_deriv_dim.cols != g.P * group ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group ||
-      in_deriv_dim.rows != g.R || in_deriv_dim.cols != g.HW * in_channel ||
-      pad_h > kernel_height - 1 || pad_w > kernel_width - 1)
-    return (int)hipErrorInvalidValue;
-  if (g.R == 0) return 0;
-  if (g.M >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  // the fused backward's data-gradient-only pass
-  if (kcnn_conv_bwd_frame(g, nullptr, 0, out_deriv, out_deriv_dim.stride, kernel,
-                          kernel_dim.stride, in_deriv, in_deriv_dim.stride, nullptr,
-                          0, nullptr, nullptr, 0, st) == 0)
-    return 0;
-  if (kcnn_conv_dgrad_frame(g, out_deriv, out_deriv_dim.stride, kernel,
-                            kernel_dim.stride, in_deriv, in_deriv_dim.stride,
-                            st) == 0)
-    return 0;
-  if (use_dgrad_scatter(g) && workspace != nullptr &&
-      workspace_bytes >= dgrad_scatter_ws(g))
-    return dgrad_scatter(g, out_deriv, out_deriv_dim, kernel, kernel_dim, in_deriv,
-                         in_deriv_dim, workspace, workspace_bytes, stream);
-  // General shapes: dX = Conv2D(virtually padded dY, FlipMat(W)) -- the
-  // reference's flip branch (nnet-component-nnet0.cc:529-540) in gather form.
-  const size_t flip_bytes = (size_t)kernel_height * kernel_width * group *
-                            in_channel * sizeof(float);
-  const size_t flip_pad = (flip_bytes + 255) & ~(size_t)255;
-  const size_t need = hipF_conv2d_dgrad_workspace_bytes(
-      out_deriv_dim, in_height, in_width, in_channel, pad_h, pad_w,
-      kernel_height, kernel_width, group);
-  if (workspace == nullptr || workspace_bytes < need)
-    return (int)hipErrorInvalidValue;
-  float *flip = static_cast<float *>(workspace);
-  MatrixDim fd;
-  fd.rows = kernel_height * kernel_width * group;
-  fd.cols = in_channel;
-  fd.stride = in_channel;
-  int rc = hipF_flip_mat(kernel, kernel_dim, kernel_height, kernel_width, group,
-                         flip, fd, stream);
-  if (rc) return rc;
-  return hipF_conv2d(out_deriv, out_deriv_dim, g.oh, g.ow, group,
-                     kernel_height - 1 - pad_h, kernel_width - 1 - pad_w, flip,
-                     fd, kernel_height, kernel_width, in_channel, nullptr,
-                     in_deriv, in_deriv_dim, 1,
-                     static_cast<char *>(workspace) + flip_pad,
-                     workspace_bytes - flip_pad, stream);
-}
-
-size_t hipF_conv2d_backward_workspace_bytes(MatrixDim in_dim, int in_height,
-                                            int in_width, int in_channel,
-                                            int pad_h, int pad_w,
-                                            int kernel_height, int kernel_width,
-                                            int group) {
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0) return 0;
-  MatrixDim od;
-  od.rows = in_dim.rows;
-  od.cols = g.P * group;
-  od.stride = od.cols;
-  size_t a = kcnn_conv_bwd_frame_ws(g);
-  const size_t b = hipF_conv2d_dgrad_workspace_bytes(
-      od, in_height, in_width, in_channel, pad_h, pad_w, kernel_height,
-      kernel_width, group);
-  const size_t c = hipF_conv2d_wgrad_workspace_bytes(
-      in_dim, in_height, in_width, in_channel, pad_h, pad_w, kernel_height,
-      kernel_width, group);
-  if (b > a) a = b;
-  return c > a ? c : a;
-}
-
-// The pooled backward of a ph x 1 x pc window (ph == 1: channel-only, 1-byte
-// mask; else a 2-byte mask), mask_bytes = the mask's row pitch in bytes.
-static int conv2d_backward_pooled(const float *in, MatrixDim in_dim, int in_height,
-                                  int in_width, int in_channel, int pad_h, int pad_w,
-                                  const unsigned char *mask, int64_t mask_pitch,
-                                  int64_t mask_cols, const float *pool_deriv,
-                                  MatrixDim pool_deriv_dim, int ph, int pc,
-                                  const float *kernel, MatrixDim kernel_dim,
-                                  int kernel_height, int kernel_width, int group,
-                                  float *in_deriv, MatrixDim in_deriv_dim, float *grad_W,
-                                  MatrixDim grad_W_dim, float *grad_b, void *workspace,
-                                  size_t workspace_bytes, hipStream_t st) {
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      !(pc == 2 || pc == 4 || pc == 8) || group % pc != 0 ||  // pc = 2: declined below
-      ph < 1 || g.oh % ph != 0 ||
-      pool_deriv_dim.rows != g.R ||
-      (int64_t)pool_deriv_dim.cols * pc * ph != (int64_t)g.P * group ||
-      mask == nullptr || mask_cols < pool_deriv_dim.cols ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group ||
-      (grad_W == nullptr && in_deriv == nullptr) ||
-      (grad_W != nullptr && (grad_W_dim.rows != g.Kdim || grad_W_dim.cols != group)))
-    return (int)hipErrorInvalidValue;
-  if (in_deriv != nullptr &&
-      (in_deriv_dim.rows != g.R || in_deriv_dim.cols != g.HW * in_channel ||
-       pad_h > kernel_height - 1 || pad_w > kernel_width - 1))
-    return (int)hipErrorInvalidValue;
-  if (g.M >= ((int64_t)1 << 31) || mask_pitch >= ((int64_t)1 << 31))
-    return (int)hipErrorInvalidValue;
-  if (g.R == 0) return 0;
-  return kcnn_conv_bwd_frame(g, in, in_dim.stride, pool_deriv, pool_deriv_dim.stride,
-                             kernel, kernel_dim.stride, in_deriv,
-                             in_deriv ? in_deriv_dim.stride : 0, grad_W,
-                             grad_W ? grad_W_dim.stride : 0, grad_b, workspace,
-                             workspace_bytes, st, mask, (int)mask_pitch, pc,
-                             ph);  // -1: declined, > 0: HIP error
-}
-
-int hipF_conv2d_backward_pooled(const float *in, MatrixDim in_dim, int in_height,
-                                int in_width, int in_channel, int pad_h, int pad_w,
-                                const unsigned char *mask, int mask_stride,
-                                const float *pool_deriv, MatrixDim pool_deriv_dim,
-                                int pool_channel_dim, const float *kernel,
-                                MatrixDim kernel_dim, int kernel_height,
-                                int kernel_width, int group, float *in_deriv,
-                                MatrixDim in_deriv_dim, float *grad_W,
-                                MatrixDim grad_W_dim, float *grad_b, void *workspace,
-                                size_t workspace_bytes, kcnn_stream_t stream) {
-  return conv2d_backward_pooled(in, in_dim, in_height, in_width, in_channel, pad_h, pad_w,
-                                mask, mask_stride, mask_stride, pool_deriv, pool_deriv_dim,
-                                1, pool_channel_dim, kernel, kernel_dim, kernel_height,
-                                kernel_width, group, in_deriv, in_deriv_dim, grad_W,
-                                grad_W_dim, grad_b, workspace, workspace_bytes,
-                                kcnn::as_stream(stream));
-}
-
-int hipF_conv2d_backward_pooled3d(const float *in, MatrixDim in_dim, int in_height,
-                                  int in_width, int in_channel, int pad_h, int pad_w,
-                                  const unsigned short *mask, int mask_stride,
-                                  const float *pool_deriv, MatrixDim pool_deriv_dim,
-                                  int pool_height_dim, int pool_width_dim,
-                                  int pool_channel_dim, const float *kernel,
-                                  MatrixDim kernel_dim, int kernel_height,
-                                  int kernel_width, int group, float *in_deriv,
-                                  MatrixDim in_deriv_dim, float *grad_W,
-                                  MatrixDim grad_W_dim, float *grad_b, void *workspace,
-                                  size_t workspace_bytes, kcnn_stream_t stream) {
-  if (pool_width_dim != 1 || pool_height_dim < 2) return -1;  // not covered
-  return conv2d_backward_pooled(in, in_dim, in_height, in_width, in_channel, pad_h, pad_w,
-                                reinterpret_cast<const unsigned char *>(mask),
-                                (int64_t)mask_stride * 2, mask_stride, pool_deriv,
-                                pool_deriv_dim, pool_height_dim, pool_channel_dim, kernel,
-                                kernel_dim, kernel_height, kernel_width, group, in_deriv,
-                                in_deriv_dim, grad_W, grad_W_dim, grad_b, workspace,
-                                workspace_bytes, kcnn::as_stream(stream));
-}
-
-int hipF_conv2d_backward(const float *in, MatrixDim in_dim, int in_height,
-                         int in_width, int in_channel, int pad_h, int pad_w,
-                         const float *out_deriv, MatrixDim out_deriv_dim,
-                         const float *kernel, MatrixDim kernel_dim,
-                         int kernel_height, int kernel_width, int group,
-                         float *in_deriv, MatrixDim in_deriv_dim, float *grad_W,
-                         MatrixDim grad_W_dim, float *grad_b, void *workspace,
-                         size_t workspace_bytes, kcnn_stream_t stream) {
-  hipStream_t st = kcnn::as_stream(stream);
-  ConvGeom g = make_geom(in_dim.rows, in_height, in_width, in_channel, pad_h,
-                         pad_w, kernel_height, kernel_width, group);
-  if (g.oh <= 0 || g.ow <= 0 || in_dim.cols != g.HW * in_channel ||
-      out_deriv_dim.rows != g.R || out_deriv_dim.cols != g.P * group ||
-      kernel_dim.rows != g.Kdim || kernel_dim.cols != group ||
-      grad_W_dim.rows != g.Kdim || grad_W_dim.cols != group || grad_W == nullptr)
-    return (int)hipErrorInvalidValue;
-  if (in_deriv != nullptr &&
-      (in_deriv_dim.rows != g.R || in_deriv_dim.cols != g.HW * in_channel ||
-       pad_h > kernel_height - 1 || pad_w > kernel_width - 1))
-    return (int)hipErrorInvalidValue;
-  if (g.M >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  if (g.R > 0 &&
-      kcnn_conv_bwd_frame(g, in, in_dim.stride, out_deriv, out_deriv_dim.stride,
-                          kernel, kernel_dim.stride, in_deriv,
-                          in_deriv ? in_deriv_dim.stride : 0, grad_W,
-                          grad_W_dim.stride, grad_b, workspace, workspace_bytes,
-                          st) == 0)
-    return 0;
-  if (in_deriv != nullptr) {
-    const int rc = hipF_conv2d_dgrad(out_deriv, out_deriv_dim, in_height,
-                                     in_width, in_channel, pad_h, pad_w, kernel,
-                                     kernel_dim, kernel_height, kernel_width,
-                                     group, in_deriv, in_deriv_dim, workspace,
-                                     workspace_bytes, stream);
-    if (rc) return rc;
-  }
-  return hipF_conv2d_wgrad(in, in_dim, in_height, in_width, in_channel, pad_h,
-                           pad_w, out_deriv, out_deriv_dim, kernel_height,
-                           kernel_width, group, grad_W, grad_W_dim, grad_b,
-                           workspace, workspace_bytes, stream);
-}
-
-}  // extern "C"

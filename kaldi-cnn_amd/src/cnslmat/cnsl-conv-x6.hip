@@ -1218,8 +1218,7 @@ size_t x6_lds(const ConvGeom &g, bool dx, int pc, int ph) {
 // C*H*W <= 2048, pc in {0, 4, 8}, a pool window ph x 1 x pc with ph in
 // {1, 2, 3} dividing oh and ph * pc <= 16, and the LDS plan within 160 KB.
 bool kcnn_conv_bwd_x6_eligible(const ConvGeom &g, bool dx, int pc, int ph) {
-  if (g.Kdim > 31 || g.Kdim < 1 || g.P < 1 || g.P > PP) return false;
-  if (g.G % 32 != 0 || g.G > 128 || g.G == 0) return false;
+  if (!kcnn::bwd_chunk_shape_ok(g) || g.Kdim < 1 || g.P < 1 || g.P > PP) return false;
   if (g.C * g.HW > NT * MAXX) return false;
   if (!(pc == 0 || pc == 4 || pc == 8)) return false;
   if (ph < 1 || ph > 3 || (ph > 1 && (pc == 0 || ph * pc > 16 || g.oh % ph != 0)))

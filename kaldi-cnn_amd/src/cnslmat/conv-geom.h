@@ -39,6 +39,34 @@ inline ConvGeom make_geom(int R, int H, int W, int C, int pad_h, int pad_w,
   return g;
 }
 
+// ---- Route predicates.  Each limit is written once, here or beside its
+// kernel, and read by the workspace sizers, the launchers and the routes of
+// conv-dispatch.cc alike.
+
+// The frame forward kernels' range (kcnn_conv_fwd_frame; cnsl-conv-frame.hip).
+inline bool in_frame_range(const ConvGeom &g) { return g.Kdim <= 64 && g.P >= 16; }
+
+// The small-filter direct kernel's shapes (kcnn_conv_direct): an MFMA tile
+// would be >= 80 % padding there.
+inline bool use_direct(const ConvGeom &g, int concat) { return concat && g.G <= 8; }
+
+// A fused forward (conv + ReLU, conv + 3-D pool in the implicit GEMM's
+// epilogue) must give the bits of the unfused convolution, so it runs only
+// where the unfused route is that same implicit GEMM: not in the frame
+// kernels' range (even where those then decline) and not on the direct
+// kernel's shapes.  Elsewhere the fused entry point declines and the caller
+// runs the components unfused.
+inline bool unfused_is_igemm(const ConvGeom &g, int concat) {
+  return !in_frame_range(g) && !use_direct(g, concat);
+}
+
+// One filter chunk of the fused backward (fp32 DMA, register-staged and
+// bf16x6 kernels): Kdim <= 31 (row Kdim is the bias gradient) and whole
+// 32-filter slabs, at most four.
+inline bool bwd_chunk_shape_ok(const ConvGeom &g) {
+  return g.Kdim <= 31 && g.G % 32 == 0 && g.G <= 128 && g.G != 0;
+}
+
 // MFMA 32x32 accumulator register r of lane l holds row
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
 __device__ __forceinline__ int mfma32_row(int r, int lane) {
@@ -111,14 +139,47 @@ int kcnn_conv_wgrad_frame(const kcnn::ConvGeom &g, const float *X, int xs,
 // in a fixed order: pass 1 sums groups of 32 rows into tmp [ceil(S/32) x E],
 // pass 2 sums the groups (cnsl-conv-frame.hip).
 size_t kcnn_reduce_splits_ws(int S, int E);
-int kcnn_reduce_splits(const float *in, int S, int E, float *tmp, float *out,
-                       hipStream_t st);
+int kcnn_reduce_splits(const float *in, int S, int E, float *out, hipStream_t st);
 int kcnn_reduce_splits_pass1(const float *in, int S, int E, float *tmp,
                              hipStream_t st);
-// pass 2 into the implicit-GEMM wgrad layout: e = g*inner + k (e < nw) ->
+// one pass into the implicit-GEMM wgrad layout: e = g*inner + k (e < nw) ->
 // gW[k][g]; e >= nw -> gb[e - nw].
-int kcnn_reduce_splits_wgrad(const float *in, int S, int E, float *tmp, int nw,
-                             int inner, float *gW, int gws, float *gb,
-                             hipStream_t st);
+int kcnn_reduce_splits_wgrad(const float *in, int S, int E, int nw, int inner, float *gW,
+                             int gws, float *gb, hipStream_t st);
+
+// The fp32-MFMA family (cnsl-conv-mfma.hip), same contract as the launchers
+// above: 0 launched, -1 declined with nothing launched, > 0 a HIP error.
+// Small filter counts (use_direct), one thread per output position.
+int kcnn_conv_direct(const kcnn::ConvGeom &g, int concat, const float *X, int xs,
+                     const float *K, int ks, const float *bias, float *out, int os,
+                     hipStream_t st);
+// conv_igemm2_kernel: Conv2D(concat) + bias (+ ReLU); declines operands past
+// 32-bit byte offsets, unaligned K and padded maps of more than 32 taps.
+int kcnn_conv_igemm2(const kcnn::ConvGeom &g, const float *X, int xs, const float *K, int ks,
+                     const float *bias, float *out, int os, int relu, hipStream_t st);
+// conv_igemm_kernel, either output layout, split over K with a fixed-order
+// reduction when ws holds kcnn_conv_igemm_ws(g) bytes; never declines.
+size_t kcnn_conv_igemm_ws(const kcnn::ConvGeom &g);
+int kcnn_conv_igemm(const kcnn::ConvGeom &g, const float *X, int xs, const float *K, int ks,
+                    const float *bias, float *out, int os, int concat, void *ws,
+                    size_t ws_bytes, hipStream_t st);
+// conv_wgrad2_kernel (G >= 32, Kdim >= 32, P <= 96) and its reduction;
+// kcnn_conv_wgrad2_ws is 0 outside its plan.
+size_t kcnn_conv_wgrad2_ws(const kcnn::ConvGeom &g, int xs, int dys);
+int kcnn_conv_wgrad2(const kcnn::ConvGeom &g, const float *X, int xs, const float *dY,
+                     int dys, float *gW, int gws, float *gb, void *ws, size_t ws_bytes,
+                     hipStream_t st);
+// conv_wgrad_kernel and its reduction: every geometry; a workspace under
+// kcnn_conv_wgrad_ws(g) is hipErrorInvalidValue, never -1.
+size_t kcnn_conv_wgrad_ws(const kcnn::ConvGeom &g);
+int kcnn_conv_wgrad(const kcnn::ConvGeom &g, const float *X, int xs, const float *dY,
+                    int dys, float *gW, int gws, float *gb, void *ws, size_t ws_bytes,
+                    hipStream_t st);
+// The scatter data gradient (Kdim >= 32, G >= 16, HW >= 1.25 P): 0 bytes and
+// -1 outside its shapes, -1 too when ws is short.
+size_t kcnn_conv_dgrad_scatter_ws(const kcnn::ConvGeom &g);
+int kcnn_conv_dgrad_scatter(const kcnn::ConvGeom &g, const float *dY, int dys,
+                            const float *W, int ks, float *dX, int dxs, void *ws,
+                            size_t ws_bytes, hipStream_t st);
 
 #endif  // KCNN_CNSLMAT_CONV_GEOM_H_

@@ -44,6 +44,17 @@ CONVS = {
     "x6_g96_k75": (9, 10, 5, 3, 5, 96, 0, 0),           # 128-row tile, 96 used
     "x6_5x5_pad2": (7, 7, 4, 5, 5, 64, 2, 2),           # 25 taps, pad 2
     "x6_p2": (1, 4, 40, 1, 3, 64, 0, 0),                # P = 2, Kdim 120
+    # conv_fwd_frame_kernel: Kdim 33..64 where the slab kernel's LDS plan is
+    # past 96 KB (here 118 KB) and its own fits
+    "fwd_frame_k40": (40, 20, 4, 5, 2, 128, 0, 0),      # Kdim 40, P 684
+    # conv_wgrad_kernel: a long kernel (Kdim 36) with fewer than 32 filters
+    "wgrad_g16": (6, 5, 4, 3, 3, 16, 1, 1),
+    # conv_direct_smallg_kernel<2>: two filters (and two channels, for the flip
+    # data gradient) on a map under the frame kernels' 16 positions
+    "direct_g2": (3, 4, 2, 2, 2, 2, 0, 0),
+    # conv_dgrad_frame_kernel<32> / <64>: Kdim 32 (past the fused backward's 31)
+    "dgrad_frame_g64": (10, 6, 2, 4, 4, 64, 0, 0),
+    "dgrad_frame_g128": (10, 6, 2, 4, 4, 128, 0, 0),
 }
 
 

@@ -25,6 +25,29 @@ FAMILY_SHAPES = {
 }
 
 
+# Fallback kernels no other case launches, by the template each shape reaches.
+# Listed after FAMILY_SHAPES so that the cases above keep their ids.
+FALLBACK_SHAPES = [
+    (("igemm_x6", 0), (2, 3, 1168, 2, 1, 64, 0, 0)),    # conv_igemm2_kernel<1, false, false>: Kdim 2336
+    (("igemm_x6", 0), (3, 4, 10, 3, 3, 10, 1, 1)),      # conv_igemm_kernel<ST_CONCAT>: G % 4 != 0
+    (("igemm_x6", 0), (6, 7, 9, 3, 3, 64, 1, 1)),       # conv_igemm2_kernel<1, true, true>
+    (("igemm_x6", 0), (1, 4, 40, 1, 3, 64, 0, 0)),      # conv_igemm2_kernel<1, false, true>, P = 2
+    (("wgrad_x6", 0), (7, 8, 16, 3, 3, 128, 1, 1)),     # conv_wgrad2_kernel<2, true>: P 56
+    (("wgrad_x6", 0), (4, 4, 32, 3, 3, 128, 1, 1)),     # conv_wgrad2_kernel<1, true>: P 16
+    (("wgrad_x6", 0), (11, 11, 64, 4, 3, 256, 0, 0)),   # conv_wgrad2_kernel<3, false>: P 72
+    (("wgrad_x6", 0), (9, 10, 5, 3, 5, 96, 0, 0)),      # conv_wgrad2_kernel<2, false>: P 42
+    # conv_wgrad_frame_kernel<2>: 160 filters on a map under the fp32 fused
+    # backward's 16 positions
+    (("bwd_x6", 0), (4, 4, 2, 2, 2, 160, 0, 0)),
+    # the other TAB = false forms of conv_igemm2_kernel: 128 filters, and a
+    # padded map with 4 x 8 = 32 taps (past the table's 31), whose gather
+    # takes the per-lane tap mask with taps up to 31
+    (("igemm_x6", 0), (2, 3, 1168, 2, 1, 128, 0, 0)),   # <2, false, false>
+    (("igemm_x6", 0), (12, 12, 3, 4, 8, 64, 1, 1)),     # <1, true, false>: Kdim 96, P 77
+    (("igemm_x6", 0), (12, 12, 3, 4, 8, 128, 1, 1)),    # <2, true, false>
+]
+
+
 @pytest.fixture
 def family(kc, request):
     name, value = request.param
@@ -34,7 +57,8 @@ def family(kc, request):
     kc.set_kernel_family(name, old)
 
 
-@pytest.mark.parametrize("family,cfg", [(f, c) for f, cs in FAMILY_SHAPES.items() for c in cs],
+@pytest.mark.parametrize("family,cfg",
+                         [(f, c) for f, cs in FAMILY_SHAPES.items() for c in cs] + FALLBACK_SHAPES,
                          indirect=["family"])
 def test_conv_family(kc, family, cfg):
     H, W, C, kh, kw, G, ph, pw = cfg

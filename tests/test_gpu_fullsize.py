@@ -124,7 +124,7 @@ def test_conv_input_over_2gb_fallback(kc):
     """A long-kernel conv whose input rows span more than 2^31 bytes (row
     stride 60 M floats): the bf16x6 implicit GEMM and the fp32 implicit GEMM
     v2 decline (32-bit buffer offsets, cnsl-conv-igemm-x6.hip
-    igemm_x6_blocks, cnsl-conv-mfma.hip conv2d_impl) and the general
+    igemm_x6_blocks, cnsl-conv-mfma.hip kcnn_conv_igemm2) and the general
     implicit-GEMM kernel runs; the backward's kernels take their own
     fallbacks.  Results equal the oracle's."""
     import torch
