@@ -74,6 +74,8 @@ Component *Component::NewComponentOfType(const std::string &component_type) {
     ans = new SoftmaxComponent();
   } else if (component_type == "DropoutComponent") {
     ans = new DropoutComponent();
+  } else if (component_type == "NormalizeComponent") {
+    ans = new NormalizeComponent();
   }
   return ans;
 }
@@ -669,6 +671,34 @@ void SoftmaxComponent::BackpropXent(const CuMatrixBase<BaseFloat> &out_value,
   CNSL_SAFE_CALL(kn_softmax_xent_backprop(out_value.Data(), out_value.Dim(), in_deriv->Data(),
                                           in_deriv->Dim(), row_start, label_col, label_weight,
                                           vs, stats_ws.p, tot, objf_ws.p, NS()));
+}
+
+// ---- NormalizeComponent (reference nnet-component.cc:576-639) ----------------
+void NormalizeComponent::Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                                   const CuMatrixBase<BaseFloat> &in,
+                                   CuMatrixBase<BaseFloat> *out) const {
+  in_info.CheckSize(in);
+  out_info.CheckSize(*out);
+  // CopyFromMat(in); AddDiagMat2(1 / D); ApplyFloor(kNormFloor); ApplyPow(-0.5);
+  // MulRowsVec -- one pass
+  CuProfileScope prof("kn_normalize_prop");
+  CNSL_SAFE_CALL(kn_normalize_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), NS()));
+}
+
+// to_update and out_value are not read (:616-639): no UpdateStats here.
+void NormalizeComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
+                                  const CuMatrixBase<BaseFloat> &in_value,
+                                  const CuMatrixBase<BaseFloat> &,
+                                  const CuMatrixBase<BaseFloat> &out_deriv, Component *,
+                                  CuMatrix<BaseFloat> *in_deriv) const {
+  in_deriv->Resize(out_deriv.NumRows(), out_deriv.NumCols(), kUndefined);
+  KALDI_ASSERT(SameDim(in_value, out_deriv));
+  // the two AddDiagVecMat, the row dot products and the floor's
+  // ReplaceValue(2^33, 0) -- one pass
+  CuProfileScope prof("kn_normalize_backprop");
+  CNSL_SAFE_CALL(kn_normalize_backprop(in_value.Data(), in_value.Dim(), out_deriv.Data(),
+                                       out_deriv.Dim(), in_deriv->Data(), in_deriv->Dim(),
+                                       NS()));
 }
 
 // ---- RandomComponent / DropoutComponent (reference nnet-component.cc:3540-3643) ----

@@ -360,6 +360,35 @@ class SoftmaxComponent : public NonlinearComponent {
   SoftmaxComponent &operator=(const SoftmaxComponent &other);
 };
 
+// reference nnet-component.h:555-582, nnet-component.cc:576-639: every row
+// scaled to root-mean-square 1 (the mean square floored at kNormFloor =
+// 2^-66).  Read, Write, Scale and Add are NonlinearComponent's; the
+// diagnostic stats are never updated (the reference's Backprop ignores
+// to_update), so they stay empty with count 0.
+class NormalizeComponent : public NonlinearComponent {
+ public:
+  explicit NormalizeComponent(int32 dim) : NonlinearComponent(dim) {}
+  explicit NormalizeComponent(const NormalizeComponent &other) : NonlinearComponent(other) {}
+  NormalizeComponent() {}
+  virtual std::string Type() const { return "NormalizeComponent"; }
+  virtual Component *Copy() const { return new NormalizeComponent(*this); }
+  virtual bool BackpropNeedsInput() const { return true; }
+  virtual bool BackpropNeedsOutput() const { return false; }
+  using Component::Propagate;
+  virtual void Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                         const CuMatrixBase<BaseFloat> &in,
+                         CuMatrixBase<BaseFloat> *out) const;
+  virtual void Backprop(const ChunkInfo &in_info, const ChunkInfo &out_info,
+                        const CuMatrixBase<BaseFloat> &in_value,
+                        const CuMatrixBase<BaseFloat> &out_value,
+                        const CuMatrixBase<BaseFloat> &out_deriv,
+                        Component *to_update,
+                        CuMatrix<BaseFloat> *in_deriv) const;
+
+ private:
+  NormalizeComponent &operator=(const NormalizeComponent &other);
+};
+
 // reference nnet-component.h:1555-1582: a component that draws random
 // numbers.  Here the generator is counter-based: the state is a 64-bit seed
 // and the number of Propagate calls so far, the draw of an element a pure

@@ -113,6 +113,24 @@ int kn_dropout_backprop(const float *in_value, MatrixDim iv_dim, const float *ou
                         MatrixDim ov_dim, const float *out_deriv, MatrixDim od_dim,
                         float *in_deriv, MatrixDim id_dim, kcnn_stream_t st);
 
+/* ---- nnet-normalize-kernels.hip: NormalizeComponent ---- */
+
+/* NormalizeComponent::Propagate (reference nnet-component.cc:580-592): per row
+ * p = (1 / cols) * sum x^2, floored at kNormFloor = 2^-66 (NaN stays),
+ * out = x * p^-0.5.  A product: a row with an inf entry or whose sum of
+ * squares overflows is scaled by 0.  Each element is read and written once
+ * for rows of up to 16384 columns; wider rows are read twice. */
+int kn_normalize_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                      kcnn_stream_t st);
+
+/* NormalizeComponent::Backprop (:616-639): with f = p^-0.5 as above,
+ * in_deriv = f * out_deriv - (1 / cols) * (rowdot(out_deriv, in_value) * g) *
+ * in_value, g = f^3, or 0 where p <= kNormFloor.  in_deriv may be out_deriv
+ * (same pointer and stride). */
+int kn_normalize_backprop(const float *in_value, MatrixDim iv_dim, const float *out_deriv,
+                          MatrixDim od_dim, float *in_deriv, MatrixDim id_dim,
+                          kcnn_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,84 +18,14 @@
 #include <type_traits>
 
 #include "nnet-kernels.h"
+#include "row-regs.h"
 #include "../cnslmat/hip-util.h"
 
 using kcnn::FastDiv;
+using namespace kcnn::rowregs;
 
 namespace {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// ---- a row in one wave's registers -------------------------------------------
-// TOT values a lane, as TOT / V vectors of V consecutive columns: value
-// k * V + s of a lane is column (k * 64 + lane) * V + s.  A vector that
-// crosses the row's end is accessed element by element.
-template <int V, int TOT>
-__device__ __forceinline__ int row_col(int lane, int j) {
-  return ((j / V) * 64 + lane) * V + (j % V);
-}
-
-template <int V, int TOT>
-__device__ __forceinline__ void load_row(const float *__restrict__ row, int cols, int lane,
-                                         float fill, float (&v)[TOT]) {
-#pragma unroll
-  for (int k = 0; k < TOT / V; k++) {
-    const int c = (k * 64 + lane) * V;
-    if (c + V <= cols) {
-      if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(row + c);
-        v[k * 4] = t.x; v[k * 4 + 1] = t.y; v[k * 4 + 2] = t.z; v[k * 4 + 3] = t.w;
-      } else if constexpr (V == 2) {
-        const float2 t = *reinterpret_cast<const float2 *>(row + c);
-        v[k * 2] = t.x; v[k * 2 + 1] = t.y;
-      } else {
-        v[k] = row[c];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < V; s++) v[k * V + s] = c + s < cols ? row[c + s] : fill;
-    }
-  }
-}
-
-template <int V, int TOT>
-__device__ __forceinline__ void store_row(float *__restrict__ row, int cols, int lane,
-                                          const float (&v)[TOT]) {
-#pragma unroll
-  for (int k = 0; k < TOT / V; k++) {
-    const int c = (k * 64 + lane) * V;
-    if (c + V <= cols) {
-      if constexpr (V == 4) {
-        *reinterpret_cast<float4 *>(row + c) =
-            make_float4(v[k * 4], v[k * 4 + 1], v[k * 4 + 2], v[k * 4 + 3]);
-      } else if constexpr (V == 2) {
-        *reinterpret_cast<float2 *>(row + c) = make_float2(v[k * 2], v[k * 2 + 1]);
-      } else {
-        row[c] = v[k];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < V; s++)
-        if (c + s < cols) row[c + s] = v[k * V + s];
-    }
-  }
-}
-
-constexpr int kWaveRowMaxCols = 4096;  // 64 lanes x 64 values
 constexpr float kSoftmaxFloor = 1.0e-20f;
 
 // ---- Softmax Propagate ---------------------------------------------------------
@@ -541,22 +471,6 @@ __global__ __launch_bounds__(256) void dropout_backprop4_kernel(
 }
 
 // ---- host side -------------------------------------------------------------------------------
-struct Operand {
-  const void *p;
-  int stride;
-};
-
-// Columns a lane takes at once: 4 (16-byte accesses) when every operand's
-// base and row stride allow, else 2, else 1.
-template <size_t N>
-int lane_width(const Operand (&ops)[N]) {
-  int v = 4;
-  for (const Operand &o : ops) {
-    while (v > 1 && ((uintptr_t)o.p % (4 * v) != 0 || o.stride % v != 0)) v >>= 1;
-  }
-  return v;
-}
-
 // Values a lane holds (the kernels are built for 4, 16 and 64).
 int lane_values(int cols) { return cols <= 256 ? 4 : cols <= 1024 ? 16 : 64; }
 
@@ -573,8 +487,6 @@ void dispatch_row_kernel(int v, int tot, F f) {
 }
 
 bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols == b.cols; }
-
-unsigned row_blocks(int rows) { return (unsigned)(rows < 65535 ? rows : 65535); }
 
 int wave_parts(int rows) { return (rows + kSmRowsPerPart - 1) / kSmRowsPerPart; }
 

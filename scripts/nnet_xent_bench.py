@@ -9,7 +9,10 @@ Prints one JSON line: frames_per_s, ms_per_step, the hipEvent-profile time of
 the six kernels of nnet-loss-kernels.hip with their bandwidth on algorithmic
 bytes (the four the step runs; kn_softmax_backprop and kn_comp_objf_and_deriv,
 which only the literal path runs, timed alone on the step's shapes), and the
-average log-probability per frame over the timed steps.
+average log-probability per frame over the timed steps.  With --config
+tests/golden/train_conv.config (the training recipes' topology) the line also
+carries the two NormalizeComponent kernels and the share of the step their
+scopes take.
 
   python scripts/nnet_xent_bench.py --steps 20 --warmup 5
 """
@@ -119,12 +122,28 @@ def main():
             row.update({"algorithmic_passes": np_, "GB/s": round(gbs, 1),
                         "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)})
         kernels[name] = row
+    # NormalizeComponent layers (tests/golden/train_conv.config): one scope a
+    # kernel over all of them, 2 passes forward and 3 backward per layer
+    norm_dims = [c.InputDim() for c in net.components if c.Type() == "NormalizeComponent"]
+    norm_ms = 0.0
+    for name, np_ in (("kn_normalize_prop", 2), ("kn_normalize_backprop", 3)):
+        if name not in prof:
+            continue
+        ms, calls = prof[name]
+        norm_ms += ms
+        gbs = np_ * B * sum(norm_dims) * 4 * (calls / len(norm_dims)) / (ms * 1e-3) / 1e9
+        kernels[name] = {"ms_per_call": round(ms / calls, 4), "calls": calls,
+                         "algorithmic_passes": np_, "GB/s": round(gbs, 1),
+                         "hbm_frac": round(gbs / HBM_PEAK_GBS, 4)}
     print(json.dumps({
-        "metric": "frames_per_s", "workload": "nnet.config whole, Propagate + BackpropXent",
+        "metric": "frames_per_s", "workload": f"{os.path.basename(args.config)} whole, Propagate + BackpropXent",
         "frames_per_step": B, "steps": args.steps, "warmup": args.warmup,
         "frames_per_s": round(B * args.steps / el, 1),
         "ms_per_step": round(el / args.steps * 1e3, 4),
         "kernels": kernels,
+        **({"normalize_layers": norm_dims,
+            "normalize_share_of_step": round(norm_ms / args.steps / (el / args.steps * 1e3), 4)}
+           if norm_dims else {}),
         "avg_logprob": objf / weight if weight else None,
         "note": "kernel times are hipEvent scopes (launch gaps included); "
                 "kn_softmax_backprop and kn_comp_objf_and_deriv are timed alone"}))
