@@ -1,0 +1,411 @@
+// capi/nnet-stack.cc -- kcnn::NnetStack (nnet-stack.h).
+#include "nnet-stack.h"
+
+#include <stdlib.h>
+
+#include <set>
+#include <sstream>
+#include <string>
+
+#include "../nnet2/nnet-kernels.h"
+#include "xent-labels.h"
+
+using namespace kaldi;
+using namespace kaldi::nnet2;
+
+namespace kcnn {
+
+namespace {
+int g_fusion = [] {
+  const char *e = getenv("KCNN_FUSE");
+  return e && *e ? atoi(e) : 1;
+}();
+
+// The non-virtual Component::Propagate's sizing (nnet-component.h:203-215):
+// resize (zero-filled) only when the size differs.
+void size_output(CuMatrix<BaseFloat> *m, int rows, int cols) {
+  if (m->NumRows() != rows || m->NumCols() != cols) m->Resize(rows, cols);
+}
+}  // namespace
+
+int fusion_mode() { return g_fusion; }
+void set_fusion_mode(int mode) { g_fusion = mode; }
+
+void comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const float *weights,
+                         int num, const float *probs, MatrixDim p_dim, float *deriv,
+                         MatrixDim d_dim, double *tot) {
+  CuScratch ws(kn_objf_ws(kn_comp_objf_blocks(num)));
+  CuProfileScope prof("kn_comp_objf_and_deriv");
+  CNSL_SAFE_CALL(kn_comp_objf_and_deriv(
+      rows, cols, weights, num, probs, p_dim, deriv, d_dim, tot, ws.p,
+      reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream())));
+}
+
+NnetStack::NnetStack(const char *config) {
+  std::vector<std::unique_ptr<Component>> parsed;
+  std::istringstream is(config);
+  std::string line;
+  while (std::getline(is, line)) {
+    const size_t b = line.find_first_not_of(" \t\r");
+    if (b == std::string::npos || line[b] == '#') continue;
+    parsed.emplace_back(Component::NewFromString(line.substr(b)));
+  }
+  if (parsed.empty()) KALDI_ERR << "empty nnet config";
+  const size_t nc = parsed.size();
+  for (size_t i = 0; i + 1 < nc; i++)
+    if (parsed[i]->OutputDim() != parsed[i + 1]->InputDim())
+      KALDI_ERR << "dimension mismatch between component " << i << " ("
+                << parsed[i]->OutputDim() << ") and " << i + 1 << " ("
+                << parsed[i + 1]->InputDim() << ")";
+  // sized once: handles, PoolColDeferreds and matrices are pointed at
+  comps_.resize(nc);
+  acts_.resize(nc + 1);
+  for (size_t i = 0; i < nc; i++) {
+    Comp &c = comps_[i];
+    c.c = std::move(parsed[i]);
+    Component *p = c.c.get();
+    c.handle.c = p;
+    c.conv = dynamic_cast<cnsl::nnet0::ConvolutionComponent *>(p);
+    c.pool = dynamic_cast<cnsl::nnet0::MaxpoolComponent *>(p);
+    c.relu = dynamic_cast<RectifiedLinearComponent *>(p);
+    c.affine = dynamic_cast<AffineComponent *>(p);
+    c.softmax = dynamic_cast<SoftmaxComponent *>(p);
+    c.updatable = dynamic_cast<UpdatableComponent *>(p);
+  }
+  // The last output is one frame per chunk; walking back, a component's input
+  // offsets are the set of output offset + Context().
+  acts_[nc].offsets.assign(1, 0);
+  for (size_t k = nc; k-- > 0;) {
+    const std::vector<int32> ctx = comps_[k].c->Context();
+    std::set<int32> in;
+    for (int32 o : acts_[k + 1].offsets)
+      for (int32 c : ctx) in.insert(o + c);
+    acts_[k].offsets.assign(in.begin(), in.end());
+  }
+  {  // MakeOffsetsContiguous on the network input
+    std::vector<int32> &first = acts_[0].offsets;
+    const int32 lo = first.front(), hi = first.back();
+    first.clear();
+    for (int32 o = lo; o <= hi; o++) first.push_back(o);
+  }
+  // ChunkInfo offsets must be >= 0: shift everything by -first input offset
+  const int32 shift = -acts_[0].offsets.front();
+  for (Activation &a : acts_)
+    for (int32 &o : a.offsets) o += shift;
+}
+
+NnetStack::LabelStaging::~LabelStaging() {
+  if (copied) {
+    (void)hipEventSynchronize(copied);
+    (void)hipEventDestroy(copied);
+  }
+  if (host) (void)hipHostFree(host);
+}
+
+kcnn_component *NnetStack::ComponentAt(int i) {
+  if (i < 0 || i >= NumComponents()) return nullptr;
+  return &comps_[i].handle;
+}
+
+ChunkInfo NnetStack::in_info(int i) {
+  return ChunkInfo(comps_[i].c->InputDim(), num_chunks_, in(i).offsets);
+}
+ChunkInfo NnetStack::out_info(int i) {
+  return ChunkInfo(comps_[i].c->OutputDim(), num_chunks_, out(i).offsets);
+}
+
+// Everything that held for the last minibatch only.
+void NnetStack::ForgetMinibatch() {
+  for (Comp &c : comps_) c.mask_valid = c.deriv_deferred = false;
+  for (Activation &a : acts_) {
+    a.stale = kStored;
+    a.stats_valid = false;
+    a.col_deferred.pending = 0;
+  }
+}
+
+// The statistics of component i's input while its Propagate / Backprop runs,
+// when the fused forward that wrote it gave them.
+std::unique_ptr<CuGemmStatsHint> NnetStack::input_stats(int i) {
+  Activation &a = in(i);
+  if (!a.stats_valid) return nullptr;
+  const CuMatrix<BaseFloat> &x = a.value;
+  uint32_t *stats = static_cast<uint32_t *>(a.stats.p);
+  std::unique_ptr<CuGemmStatsHint> h(new CuGemmStatsHint(
+      x.Data(), x.NumRows(), x.NumCols(), x.Stride(), stats, stats + 3 * (size_t)x.NumRows()));
+  if (a.col_deferred.pending) h->pending = &a.col_deferred;
+  return h;
+}
+
+// d(output of component i): the caller's for the last component, else the
+// input derivative of the component above.
+CuSubMatrix<BaseFloat> NnetStack::out_deriv_of(int i, const float *caller_ptr,
+                                               MatrixDim caller_dim) {
+  if (i == NumComponents() - 1)
+    return CuSubMatrix<BaseFloat>(const_cast<float *>(caller_ptr), caller_dim.rows,
+                                  caller_dim.cols, caller_dim.stride);
+  CuMatrix<BaseFloat> &d = comps_[i + 1].deriv;
+  return CuSubMatrix<BaseFloat>(d.Data(), d.NumRows(), d.NumCols(), d.Stride());
+}
+
+// NnetUpdater passes every component as to_update: updatable ones only update
+// in kUpdate; NonlinearComponent stats (per replica) always accumulate.
+Component *NnetStack::to_update(const Comp &c, BackpropMode mode) const {
+  return (mode == kUpdate || !c.updatable) ? c.c.get() : nullptr;
+}
+
+// Component i (Conv) and i + 1 (Maxpool with a fusable window) in one fused
+// pass; false, having launched nothing, when the pair does not qualify.
+bool NnetStack::PropagateMaxpoolPair(int i) {
+  if (!g_fusion || i + 1 >= NumComponents()) return false;
+  const cnsl::nnet0::ConvolutionComponent *conv = comps_[i].conv;
+  const cnsl::nnet0::MaxpoolComponent *pool = comps_[i + 1].pool;
+  if (!conv || !pool) return false;
+  const int mask_bytes = pool->FusedMaskBytes();  // 1: channel-only, 2: 3-D window
+  if (mask_bytes == 0) return false;
+  Activation &x = in(i), &y = out(i), &pooled = out(i + 1);
+  const int rows = x.value.NumRows();
+  unsigned char *mask = static_cast<unsigned char *>(
+      comps_[i + 1].mask.reserve((size_t)rows * pool->OutputDim() * mask_bytes));
+  size_output(&y.value, rows, conv->OutputDim());
+  size_output(&pooled.value, rows, pool->OutputDim());
+  const bool store = g_fusion == 2;
+  // room for the pooled output's statistics (the row block [max, min, cnt]
+  // and the column block [max, min, cnt], kept) and the kernel's column
+  // partials (kept too: the column work may run in the backward)
+  PoolStatsOut ps;
+  const size_t pw = mask_bytes == 1 && conv->In_pad_height() == 0 && conv->In_pad_width() == 0
+                        ? kcnn_conv2d_maxpool_stats_words(
+                              rows, conv->In_height(), conv->In_width(), conv->In_channels(),
+                              conv->Kernel_height(), conv->Kernel_width(), conv->Group(),
+                              pool->FusableChannelPool())
+                        : 0;
+  pooled.col_deferred.pending = 0;
+  if (pw) {
+    ps.partials = static_cast<uint32_t *>(pooled.col_partials.reserve(pw * 4));
+    ps.partial_words = pw;
+    ps.rowmax = static_cast<uint32_t *>(
+        pooled.stats.reserve(4 * 3 * ((size_t)rows + pool->OutputDim())));
+    ps.colmax = ps.rowmax + 3 * (size_t)rows;
+  }
+  {
+    PoolColDeferScope defer(pw ? &pooled.col_deferred : nullptr);
+    if (!conv->PropagateMaxpool(x.value, &y.value, *pool, &pooled.value, mask,
+                                pool->OutputDim(), store, pw ? &ps : nullptr))
+      return false;
+  }
+  pooled.stats_valid = ps.produced;
+  comps_[i + 1].mask_valid = true;
+  y.stale = store ? kStored : kRecomputable;
+  return true;
+}
+
+// Component i (Conv) and i + 1 (RectifiedLinearComponent) in one pass, fusion
+// mode 1 only: the conv output (the ReLU's in_value, which its Backprop does
+// not read) is left unstored; false when the pair does not qualify.
+bool NnetStack::PropagateReluPair(int i) {
+  if (g_fusion != 1 || i + 1 >= NumComponents()) return false;
+  const cnsl::nnet0::ConvolutionComponent *conv = comps_[i].conv;
+  const RectifiedLinearComponent *relu = comps_[i + 1].relu;
+  if (!conv || !relu || relu->InputDim() != conv->OutputDim()) return false;
+  const int rows = in(i).value.NumRows();
+  size_output(&out(i).value, rows, conv->OutputDim());
+  size_output(&out(i + 1).value, rows, relu->OutputDim());
+  if (!conv->PropagateRelu(in(i).value, &out(i + 1).value)) return false;
+  out(i).stale = kRecomputable;
+  return true;
+}
+
+void NnetStack::Propagate(const float *input, MatrixDim in_dim) {
+  KALDI_ASSERT(in_dim.cols == comps_[0].c->InputDim());
+  const int in_cs = (int)acts_[0].offsets.size();
+  if (in_dim.rows % in_cs != 0)
+    KALDI_ERR << "input rows " << in_dim.rows << " are not a multiple of the "
+              << in_cs << "-frame input chunk";
+  acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
+  num_chunks_ = in_dim.rows / in_cs;
+  ForgetMinibatch();
+  for (int i = 0; i < NumComponents(); i++) {
+    if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
+    ChunkInfo ii = in_info(i), oi = out_info(i);
+    auto hint = input_stats(i);
+    comps_[i].c->Propagate(ii, oi, in(i).value, &out(i).value);
+  }
+}
+
+const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
+  KALDI_ASSERT(i >= -1 && i < NumComponents());
+  Activation &a = out(i);
+  if (a.stale == kGone)
+    KALDI_ERR << "output of component " << i << " was not stored (fused with the "
+              << "next Maxpool, kcnn_set_fusion(1)) and its backprop has run; "
+              << "use kcnn_set_fusion(2) to keep it";
+  if (a.stale == kRecomputable) {  // a fused conv's output: run its Propagate now
+    comps_[i].c->Propagate(in_info(i), out_info(i), in(i).value, &a.value);
+    a.stale = kStored;
+  }
+  return a.value;
+}
+
+// A deferred pool Backprop (Comp::deriv_deferred), run now.
+void NnetStack::MaterialisePoolDeriv(int i) {
+  Comp &c = comps_[i];
+  KALDI_ASSERT(c.pool != NULL && c.mask_valid && i + 1 < NumComponents());
+  c.pool->BackpropFromMask(static_cast<unsigned char *>(c.mask.p), c.pool->OutputDim(),
+                           out_deriv_of(i, nullptr, MatrixDim()), &c.deriv);
+  c.deriv_deferred = false;
+}
+
+const CuMatrix<BaseFloat> &NnetStack::InputDeriv(int i) {
+  KALDI_ASSERT(i >= 0 && i < NumComponents());
+  if (comps_[i].deriv_deferred) MaterialisePoolDeriv(i);
+  return comps_[i].deriv;
+}
+
+void NnetStack::BackpropComponent(int i, const float *out_deriv, MatrixDim od_dim,
+                                  BackpropMode mode, float *grad, bool skip_first_dx) {
+  const int nc = NumComponents();
+  KALDI_ASSERT(i >= 0 && i < nc);
+  Comp &c = comps_[i];
+  auto hint = input_stats(i);
+  if (out(i).stale == kRecomputable) out(i).stale = kGone;
+  const CuMatrix<BaseFloat> &x = in(i).value, &y = out(i).value;
+  const bool pool_above_deferred = i + 1 < nc && comps_[i + 1].deriv_deferred;
+  CuMatrix<BaseFloat> *dx = &c.deriv;
+  if (i == 0 && skip_first_dx && c.updatable) dx = nullptr;
+  if (mode == kGradientOnly) {
+    KALDI_ASSERT(c.updatable != NULL && grad != NULL && !pool_above_deferred && !c.mask_valid);
+    c.updatable->BackpropGradient(in_info(i), out_info(i), x, y,
+                                  out_deriv_of(i, out_deriv, od_dim), nullptr, grad);
+    return;
+  }
+  if (pool_above_deferred) {  // the pool above left its Backprop here
+    const Comp &p = comps_[i + 1];
+    if (c.conv && p.pool &&
+        c.conv->BackpropPooled(x, *p.pool, static_cast<unsigned char *>(p.mask.p),
+                               p.pool->OutputDim(), out_deriv_of(i + 1, out_deriv, od_dim),
+                               to_update(c, mode), dx, mode == kGradient ? grad : nullptr))
+      return;
+    MaterialisePoolDeriv(i + 1);
+  }
+  CuSubMatrix<BaseFloat> od = out_deriv_of(i, out_deriv, od_dim);
+  ChunkInfo ii = in_info(i), oi = out_info(i);
+  if (mode == kGradient && c.updatable) {
+    c.updatable->BackpropGradient(ii, oi, x, y, od, dx, grad);
+    return;
+  }
+  if (c.mask_valid) {  // pool of a fused pair: route through its mask
+    KALDI_ASSERT(c.pool != NULL);
+    // fusion mode 1, not the last component: left to the conv below, which
+    // builds its out_deriv from od and the mask slab by slab
+    if (g_fusion == 1 && i < nc - 1 && c.pool->FoldsIntoConvBackprop()) {
+      c.deriv_deferred = true;
+      return;
+    }
+    c.pool->BackpropFromMask(static_cast<unsigned char *>(c.mask.p), c.pool->OutputDim(), od,
+                             dx);
+    return;
+  }
+  c.c->Backprop(ii, oi, x, y, od, to_update(c, mode), dx);
+}
+
+void NnetStack::BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, float *grad,
+                              bool skip_first_dx, void (*between)(void *), void *ctx) {
+  const int nc = NumComponents();
+  KALDI_ASSERT(i >= 0 && i < nc && grad != NULL);
+  Comp &c = comps_[i];
+  if (c.affine == NULL) KALDI_ERR << "kcnn_nnet_backprop_split: component " << i << " is not affine";
+  KALDI_ASSERT(!(i + 1 < nc && comps_[i + 1].deriv_deferred) && !c.mask_valid);
+  auto hint = input_stats(i);
+  if (out(i).stale == kRecomputable) out(i).stale = kGone;
+  const CuMatrix<BaseFloat> &x = in(i).value, &y = out(i).value;
+  CuSubMatrix<BaseFloat> od = out_deriv_of(i, out_deriv, od_dim);
+  CuMatrix<BaseFloat> *dx = (i == 0 && skip_first_dx) ? nullptr : &c.deriv;
+  ChunkInfo ii = in_info(i), oi = out_info(i);
+  CuGemmBackpropStats stats(od, c.affine->LinearParams(), true, &x);
+  c.affine->BackpropGradient(ii, oi, x, y, od, nullptr, grad);
+  if (between) between(ctx);
+  if (dx) c.c->Backprop(ii, oi, x, y, od, to_update(c, kDataOnly), dx);
+}
+
+void NnetStack::Backprop(const float *out_deriv, MatrixDim od_dim) {
+  for (int i = NumComponents() - 1; i >= 0; i--)
+    BackpropComponent(i, out_deriv, od_dim, kUpdate, nullptr, false);
+}
+
+double *NnetStack::objf_totals() {
+  kaldi::CuBuffer &t = labels_.totals;
+  if (!t.p)
+    CU_SAFE_CALL(hipMemsetAsync(t.reserve(2 * sizeof(double)), 0, 2 * sizeof(double),
+                                CuDevice::Instantiate().Stream()));
+  return static_cast<double *>(t.p);
+}
+
+const char *NnetStack::LabelStaging::Stage(const int32_t *rows, const int32_t *cols,
+                                           const float *weights, int num, int num_rows,
+                                           hipStream_t st) {
+  const size_t bytes = label_layout(num, num_rows).bytes;
+  if (copied == nullptr)
+    CU_SAFE_CALL(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+  else
+    CU_SAFE_CALL(hipEventSynchronize(copied));  // the last copy has left the buffer
+  if (host_bytes < bytes) {
+    if (host) CU_SAFE_CALL(hipHostFree(host));
+    host = nullptr;
+    host_bytes = 0;
+    CU_SAFE_CALL(hipHostMalloc(&host, bytes, hipHostMallocDefault));
+    host_bytes = bytes;
+  }
+  dev.reserve(bytes);
+  stage_labels(rows, cols, weights, num, num_rows, host);
+  CU_SAFE_CALL(hipMemcpyAsync(dev.p, host, bytes, hipMemcpyHostToDevice, st));
+  CU_SAFE_CALL(hipEventRecord(copied, st));
+  return static_cast<const char *>(dev.p);
+}
+
+void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights,
+                             int num, bool skip_first_dx) {
+  const int nc = NumComponents();
+  const Comp &last = comps_[nc - 1];
+  const CuMatrix<BaseFloat> &y = out(nc - 1).value;
+  const int N = y.NumRows(), dim = last.c->OutputDim();
+  if (N == 0 || y.NumCols() != dim) KALDI_ERR << "kcnn_nnet_backprop_xent: no Propagate ran";
+  if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_nnet_backprop_xent: bad label arrays";
+  // every check before any launch
+  const std::string bad = check_labels(rows, cols, num, N, dim, true);
+  if (!bad.empty()) KALDI_ERR << "kcnn_nnet_backprop_xent: " << bad;
+  // the list -> pinned staging buffer -> device, on the library's stream
+  const LabelLayout lay = label_layout(num, N);
+  const char *base = labels_.Stage(rows, cols, weights, num, N, CuDevice::Instantiate().Stream());
+  const int32_t *d_start = reinterpret_cast<const int32_t *>(base + lay.row_start);
+  const int32_t *d_row = reinterpret_cast<const int32_t *>(base + lay.row);
+  const int32_t *d_col = reinterpret_cast<const int32_t *>(base + lay.col);
+  const float *d_w = reinterpret_cast<const float *>(base + lay.weight);
+  double *tot = objf_totals();
+  int first = nc - 1;  // the component the generic backward starts at
+  if (last.softmax != nullptr && !cnsl::nnet0::LiteralPath()) {
+    // zeroed derivative + CompObjfAndDeriv + the Softmax's Backprop, fused
+    last.softmax->BackpropXent(y, d_start, d_col, d_w, tot, last.softmax,
+                               &comps_[nc - 1].deriv);
+    first = nc - 2;
+  } else {
+    // NnetUpdater::ComputeObjfAndDeriv: a zeroed [rows x OutputDim] matrix,
+    // CompObjfAndDeriv against the last output; Backprop follows
+    xent_deriv_.Resize(N, dim, kSetZero);
+    if (num > 0)
+      comp_objf_and_deriv(d_row, d_col, d_w, num, y.Data(), y.Dim(), xent_deriv_.Data(),
+                          xent_deriv_.Dim(), tot);
+  }
+  for (int i = first; i >= 0; i--)
+    BackpropComponent(i, xent_deriv_.Data(), xent_deriv_.Dim(), kUpdate, nullptr, skip_first_dx);
+}
+
+void NnetStack::ObjfTotal(double out[2], bool reset) {
+  hipStream_t st = CuDevice::Instantiate().Stream();
+  double *tot = objf_totals();
+  CU_SAFE_CALL(hipMemcpyAsync(out, tot, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (reset) CU_SAFE_CALL(hipMemsetAsync(tot, 0, 2 * sizeof(double), st));
+  CU_SAFE_CALL(hipStreamSynchronize(st));
+}
+
+}  // namespace kcnn

@@ -1,0 +1,177 @@
+// capi/nnet-stack.h -- the NnetUpdater-style component stack behind
+// kcnn_nnet_* (include/kcnn.h): the chunk offsets (Nnet::ComputeChunkInfo),
+// the Conv -> Maxpool and Conv -> ReLU fused passes and what they leave
+// unstored or deferred, the statistics hand-off to the FC GEMMs, the
+// data-parallel gradient / data-gradient split and the cross-entropy backward.
+// Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
+// error codes.
+#ifndef KCNN_CAPI_NNET_STACK_H_
+#define KCNN_CAPI_NNET_STACK_H_
+
+#include <memory>
+#include <vector>
+
+#include "kcnn.h"
+
+#include "../cnslmat/pool-stats.h"
+#include "../kaldi-lite/cu-device.h"
+#include "../kaldi-lite/cu-matrix.h"
+#include "../nnet0/nnet-component-nnet0.h"
+#include "../nnet2/nnet-component.h"
+
+struct kcnn_component {
+  kaldi::nnet2::Component *c;
+};
+
+// Internal to libkcnn.so, as the file-static functions this replaces were: the
+// library's exported surface stays include/kcnn.h.
+#pragma GCC visibility push(hidden)
+namespace kcnn {
+
+using kaldi::BaseFloat;
+using kaldi::CuMatrix;
+using kaldi::CuSubMatrix;
+
+// Runtime fusion of Conv -> Maxpool (kcnn_set_fusion; env KCNN_FUSE): 0 off,
+// 1 on without storing the conv output, 2 on and the conv output stored.
+int fusion_mode();
+void set_fusion_mode(int mode);
+
+// kn_comp_objf_and_deriv (nnet2/nnet-kernels.h) on the library's stream with
+// its workspace and profile scope: labels and totals are device pointers.
+void comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const float *weights,
+                         int num, const float *probs, MatrixDim p_dim, float *deriv,
+                         MatrixDim d_dim, double *tot);
+
+class NnetStack {
+ public:
+  // kcnn_nnet_backprop_component's `mode` (include/kcnn.h)
+  enum BackpropMode : int {
+    kUpdate = 0,        // Backprop, updatable components update
+    kGradient = 1,      // the parameter gradient to `grad` and dX, no update
+    kDataOnly = 2,      // dX alone
+    kGradientOnly = 3,  // the parameter gradient alone (a later kDataOnly adds dX)
+  };
+
+  // One component per config line ('#' comments and blank lines skipped);
+  // throws on a bad line, an empty config or mismatched dimensions.
+  explicit NnetStack(const char *config);
+
+  int NumComponents() const { return (int)comps_.size(); }
+  kcnn_component *ComponentAt(int i);  // NULL out of range
+
+  void Propagate(const float *in, MatrixDim in_dim);
+  // Output of component i (-1: the network input) and d(input of component
+  // i) of the last minibatch.  Not const: an unstored output is recomputed
+  // and a deferred pool derivative computed on request.
+  const CuMatrix<BaseFloat> &Output(int i);
+  const CuMatrix<BaseFloat> &InputDeriv(int i);
+
+  // out_deriv is read for the last component only; lower ones read the input
+  // derivative of the component above.
+  void BackpropComponent(int i, const float *out_deriv, MatrixDim od_dim, BackpropMode mode,
+                         float *grad, bool skip_first_dx);
+  // An affine layer's parameter gradient, then between(ctx) (the caller starts
+  // its all-reduce there), then the layer's data gradient: kGradientOnly and
+  // kDataOnly in one call, so both GEMMs' operand statistics come from one
+  // launch set that lives across the callback (the pair of calls computed
+  // them twice).
+  void BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, float *grad,
+                     bool skip_first_dx, void (*between)(void *), void *ctx);
+  void Backprop(const float *out_deriv, MatrixDim od_dim);  // kUpdate, top down
+  // Cross-entropy against the last output for (row, col, weight) labels
+  // sorted by row, accumulated into the objective totals, then Backprop.
+  // Does not synchronise.
+  void BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights, int num,
+                    bool skip_first_dx);
+  // {objective, weight} summed since the last reset; synchronises.
+  void ObjfTotal(double out[2], bool reset);
+
+ private:
+  struct Comp {
+    std::unique_ptr<kaldi::nnet2::Component> c;
+    kcnn_component handle{nullptr};
+    // what the component is, found once (the stack never changes); NULL
+    // where it is not of that kind
+    cnsl::nnet0::ConvolutionComponent *conv = nullptr;
+    cnsl::nnet0::MaxpoolComponent *pool = nullptr;
+    kaldi::nnet2::RectifiedLinearComponent *relu = nullptr;
+    kaldi::nnet2::AffineComponent *affine = nullptr;
+    kaldi::nnet2::SoftmaxComponent *softmax = nullptr;
+    kaldi::nnet2::UpdatableComponent *updatable = nullptr;
+    CuMatrix<BaseFloat> deriv;  // d(input of this component)
+    // a pool run fused with the conv below: its routing mask ([rows x
+    // OutputDim] x FusedMaskBytes), valid for the last Propagate's minibatch
+    kaldi::CuBuffer mask;
+    bool mask_valid = false;
+    // deriv of a mask-fused pool not computed (fusion mode 1): the conv
+    // below consumes the pool's out_deriv and mask directly; materialised by
+    // InputDeriv on request, or when that conv's pass declines
+    bool deriv_deferred = false;
+  };
+  // Whether an activation's matrix holds its values: a fused pass leaves the
+  // conv output unstored (fusion mode 1; nothing in training reads it).
+  // Output recomputes it on request until the producing component's backprop
+  // has run, which may have changed its parameters.
+  enum Stale { kStored, kRecomputable, kGone };
+  // acts_[i] is component i's input, acts_[i + 1] its output; acts_[0]
+  // borrows the caller's network input.
+  struct Activation {
+    CuMatrix<BaseFloat> value;
+    // frame offsets of this activation's chunk, ascending (upstream
+    // Nnet::ComputeChunkInfo).  Gapped contexts (SpliceComponent
+    // context=-3:0:3) make a middle layer's offsets non-contiguous.
+    std::vector<kaldi::int32> offsets;
+    Stale stale = kStored;
+    // max |value| per row and per column from the fused forward that wrote
+    // it (pool-stats.h), offered to the next component's GEMMs
+    // (CuGemmStatsHint) for the minibatch of the last Propagate
+    kaldi::CuBuffer stats;
+    bool stats_valid = false;
+    // the column statistics left pending by the fused forward (the next
+    // component's FC backward runs them, pool-stats.h PoolColDeferred) and
+    // the forward's per-workgroup column partials they read, kept until then
+    PoolColDeferred col_deferred;
+    kaldi::CuBuffer col_partials;
+  };
+  // BackpropXent: the label list's pinned staging buffer and its device image
+  // (xent-labels.h), the event after which the staging buffer may be
+  // rewritten, and the fp64 {objective, weight} totals on the device
+  struct LabelStaging {
+    void *host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t copied = nullptr;
+    kaldi::CuBuffer totals, dev;
+    LabelStaging() {}
+    ~LabelStaging();  // waits for the last copy to leave `host`
+    LabelStaging(const LabelStaging &) = delete;
+    LabelStaging &operator=(const LabelStaging &) = delete;
+    // the checked labels -> host -> dev on `st`; returns dev
+    const char *Stage(const int32_t *rows, const int32_t *cols, const float *weights, int num,
+                      int num_rows, hipStream_t st);
+  };
+
+  Activation &in(int i) { return acts_[i]; }
+  Activation &out(int i) { return acts_[i + 1]; }
+  kaldi::nnet2::ChunkInfo in_info(int i);
+  kaldi::nnet2::ChunkInfo out_info(int i);
+  void ForgetMinibatch();
+  std::unique_ptr<kaldi::CuGemmStatsHint> input_stats(int i);
+  bool PropagateMaxpoolPair(int i);
+  bool PropagateReluPair(int i);
+  void MaterialisePoolDeriv(int i);
+  CuSubMatrix<BaseFloat> out_deriv_of(int i, const float *caller_ptr, MatrixDim caller_dim);
+  kaldi::nnet2::Component *to_update(const Comp &c, BackpropMode mode) const;
+  double *objf_totals();
+
+  std::vector<Comp> comps_;
+  std::vector<Activation> acts_;  // comps_.size() + 1
+  int num_chunks_ = 0;
+  LabelStaging labels_;
+  CuMatrix<BaseFloat> xent_deriv_;  // the literal path's d(last output)
+};
+
+}  // namespace kcnn
+#pragma GCC visibility pop
+
+#endif  // KCNN_CAPI_NNET_STACK_H_

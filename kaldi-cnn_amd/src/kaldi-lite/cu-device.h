@@ -21,6 +21,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kaldi-common.h"
@@ -118,6 +119,37 @@ struct CuScratch {
   CuScratch(const CuScratch &) = delete;
   CuScratch &operator=(const CuScratch &) = delete;
   float *f() { return static_cast<float *>(p); }
+};
+
+// A device block that lives across calls and only grows (a routing mask, a
+// statistics block: sized by the largest minibatch so far).  reserve() goes
+// to the caching allocator only when `bytes` exceeds the capacity, freeing
+// the old block before it asks for the new one; a block that fits is left
+// alone and never shrinks.  Contents do not survive a growth.
+struct CuBuffer {
+  void *p = nullptr;
+  size_t capacity = 0;  // bytes
+  CuBuffer() {}
+  ~CuBuffer() { if (p) CuDevice::Instantiate().Free(p); }
+  CuBuffer(CuBuffer &&o) noexcept : p(o.p), capacity(o.capacity) {
+    o.p = nullptr;
+    o.capacity = 0;
+  }
+  CuBuffer &operator=(CuBuffer &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(capacity, o.capacity);
+    return *this;
+  }
+  void *reserve(size_t bytes) {
+    if (bytes > capacity) {
+      if (p) CuDevice::Instantiate().Free(p);
+      p = nullptr;
+      capacity = 0;
+      p = CuDevice::Instantiate().Malloc(bytes);
+      capacity = bytes;
+    }
+    return p;
+  }
 };
 
 // Times a scope with hipEvents on the device stream when profiling is on.

@@ -332,3 +332,73 @@ def test_pooled_backward_across_frames(kc, name):
     x = dev(randn(r, (N, net.components[0].InputDim())))
     dy = dev(randn(r, (N, net.components[2].OutputDim()), 0.1))
     check_step(kc, stack(*cfg)[0], net, x, dy, what=f"{name} N={N}")
+
+
+# One Nnet object across minibatches of changing size: what the runtime keeps
+# from one Propagate to the next (routing masks, statistics blocks, column
+# partials and the label image grow and are reused; the unstored-output,
+# deferred-derivative and pending-statistics flags are forgotten) must leave
+# every step bit-identical to the same step on a net that never ran before.
+REUSED = ["pc8_G64",     # 1-byte mask, statistics, column partials
+          "win_2x2x2",   # 2-byte mask, no statistics
+          "long_1x2x1"]  # pool in the implicit GEMM's epilogue
+WHICH = ("PARAM_LINEAR", "PARAM_BIAS", "PARAM_PREV_GRAD")
+
+
+def assert_bits(a, b, what):
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    diff = a.view(np.uint32) != b.view(np.uint32)
+    assert not diff.any(), f"{what}: {diff.sum()} of {diff.size} elements differ"
+
+
+def fresh_copy(kc, text, net):
+    """A new net with `net`'s current parameters."""
+    new = kc.Nnet(text)
+    for a, b in zip(net.components, new.components):
+        if a.NumGradientParams() > 0:
+            for w in WHICH:
+                b.SetParam(getattr(kc, w), a.GetParam(getattr(kc, w)))
+    return new
+
+
+def whole_step(kc, net, x, dy=None, labels=None):
+    n = net.NumComponents()
+    net.Propagate(x)
+    got = {f"output {i}": host(net.Output(i)) for i in range(n)}
+    if labels is None:
+        net.Backprop(dy)
+    else:
+        net.BackpropXent(labels)
+        got["objf"] = np.asarray(net.ObjfTotal(reset=True), np.float64).view(np.uint32)
+    got.update({f"input deriv {i}": host(net.InputDeriv(i)) for i in range(n)})
+    for i, c in enumerate(net.components):
+        if c.NumGradientParams() > 0:
+            got.update({f"component {i} {w}": host(c.GetParam(getattr(kc, w))) for w in WHICH})
+    return got
+
+
+@pytest.mark.parametrize("name", REUSED)
+def test_reused_net_matches_fresh_net(kc, name):
+    cfg = STACKS[name]
+    text = stack(*cfg)[0]
+    fo = cfg[7]
+    kc.set_fusion(1)
+    try:
+        # Backprop from an output derivative at 37, 300 and 8 rows, then (a
+        # Softmax on top) BackpropXent from 37 and 300 labels
+        for config, sizes, xent in ((text, (37, 300, 8), False),
+                                    (text + f"\nSoftmaxComponent dim={fo}", (37, 300), True)):
+            net = build(kc, cfg, seed=11) if not xent else fresh_copy(kc, config, build(kc, cfg, 11))
+            r = rng(3)
+            for N in sizes:
+                x = dev(randn(r, (N, net.components[0].InputDim())))
+                dy = dev(randn(r, (N, fo), 0.1))
+                labels = [(i, int(r.integers(fo)), 1.0) for i in range(N)] if xent else None
+                alone = fresh_copy(kc, config, net)
+                a = whole_step(kc, net, x, dy, labels)
+                b = whole_step(kc, alone, x, dy, labels)
+                assert sorted(a) == sorted(b)
+                for key in a:
+                    assert_bits(a[key], b[key], f"{name} N={N} xent={xent} {key}")
+    finally:
+        kc.set_fusion(1)
