@@ -1087,10 +1087,11 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void conv_bwd_frame_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l = lane & 31, h = lane >> 5;
-  for (int e = tid; e < NCH * 32 * 32; e += BWD_THREADS) {
-    const int gg = e >> 5, k = e & 31;
-    Wt[e] = (gg < g.G && k < g.Kdim) ? K[(int64_t)k * ks + gg] : 0.0f;
-  }
+  if (DX)  // K is only read by the data gradient (the gradient-only pass has K == NULL)
+    for (int e = tid; e < NCH * 32 * 32; e += BWD_THREADS) {
+      const int gg = e >> 5, k = e & 31;
+      Wt[e] = (gg < g.G && k < g.Kdim) ? K[(int64_t)k * ks + gg] : 0.0f;
+    }
   // wgrad A operand of this lane = row l of the [Kdim+1 x P] im2col tile,
   // read as Xs[min(abase + qmul * qtab[p], CHWp)] (byte offsets):
   //   conv row l < Kdim: abase = its tap offset in the zero-padded frame
@@ -1972,8 +1973,11 @@ bool bwd_fp32_positions_ok(const ConvGeom &g) {
 
 // Runs fn(chunk geometry, first filter) over g's filters in chunks of 128
 // (each a column range of W, b and Y).  Only the first chunk may decline
-// (-1: nothing is written yet); a later one that does is a launch failure.
-// G <= 128 is one chunk, g itself.
+// (-1: nothing is written yet); a later one that does has left the layer
+// half done and is hipErrorLaunchFailure, which every caller returns as an
+// error (none falls through to another route on it).  So fn must decide at
+// g0 == 0 whatever would make a later chunk decline.  G <= 128 is one
+// chunk, g itself.
 template <class F>
 int for_filter_chunks(const ConvGeom &g, F fn) {
   int g0 = 0;
@@ -2292,14 +2296,15 @@ static size_t bwd_dma_lds(const ConvGeom &g) {
           (size_t)((g.P + 31) & ~31)) * 4;
 }
 
-// One filter chunk (G <= 128) of kcnn_conv_bwd_frame; dx_acc adds to dX.
+// One filter chunk (G <= 128) of kcnn_conv_bwd_frame; dx_acc adds to dX,
+// chunked: the layer has more chunks than this one.
 // pc > 0: dY / dys are the pooled derivative dP of a 1 x 1 x pc Maxpool and
 // pmask / pms its routing mask (see conv_bwd_dma_kernel).
 static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
                            const float *dY, int dys, const float *K, int ks,
                            float *dX, int dxs, float *gW, int gws, float *gb,
-                           void *ws, size_t ws_bytes, int dx_acc, hipStream_t st,
-                           const unsigned char *pmask, int pms, int pc, int ph,
+                           void *ws, size_t ws_bytes, int dx_acc, bool chunked,
+                           hipStream_t st, const unsigned char *pmask, int pms, int pc, int ph,
                            const ConvUpdateEpi *ue) {
   if (dX == nullptr && gW == nullptr) return -1;
   if (!kcnn::bwd_chunk_shape_ok(g)) return -1;
@@ -2399,8 +2404,12 @@ static int bwd_frame_chunk(const ConvGeom &g, const float *X, int xs,
 #undef KCNN_BWD3P
   } else {
     // register-staged kernel (the DMA kernel's limits fail): needs the
-    // gradient outputs, writes dX
-    if (gW == nullptr || dx_acc || pc) return -1;
+    // gradient outputs and writes dX (it cannot add to it), so it takes a
+    // layer of one chunk only.  A chunked layer declines here at its first
+    // chunk, before anything is launched (the DMA kernel's LDS need does not
+    // grow with fewer filters, so a later chunk does not fail where the first
+    // passed).
+    if (gW == nullptr || chunked || pc) return -1;
     const int SP = bwd_sp(g);
     const size_t lds = bwd_lds(g, SP);
     if (lds > (size_t)kFrameLdsMax) return -1;
@@ -2455,7 +2464,7 @@ int kcnn_conv_bwd_frame(const ConvGeom &g, const float *X, int xs,
     }
     return bwd_frame_chunk(gc, X, xs, dY + dofs, dys, K + g0, ks, dX, dxs,
                            gW ? gW + g0 : nullptr, gws, gb ? gb + g0 : nullptr, ws, ws_bytes,
-                           g0 > 0, st, pmask ? pmask + mofs : nullptr, pms, pc, ph,
+                           g0 > 0, g.G > 128, st, pmask ? pmask + mofs : nullptr, pms, pc, ph,
                            u ? &uc : nullptr);
   });
   if (rc == 0 && u) u->applied = 1;

@@ -301,13 +301,13 @@ int hipF_conv2d_wgrad(const float *in, MatrixDim in_dim, int in_height, int in_w
   int rc;
   if (g.M > 0) {
     // fused backward: its gradient-only pass (Kdim <= 31; one stream of dY)
-    if (kcnn_conv_bwd_frame(g, in, xs, out_deriv, dys, nullptr, 0, nullptr, 0, grad_W, gws,
-                            grad_b, workspace, workspace_bytes, st) == 0)
-      return 0;
+    if ((rc = kcnn_conv_bwd_frame(g, in, xs, out_deriv, dys, nullptr, 0, nullptr, 0, grad_W,
+                                  gws, grad_b, workspace, workspace_bytes, st)) >= 0)
+      return rc;
     // frame: short kernels the fused backward declined (G up to 256)
-    if (kcnn_conv_wgrad_frame(g, in, xs, out_deriv, dys, grad_W, gws, grad_b, workspace,
-                              workspace_bytes, st) == 0)
-      return 0;
+    if ((rc = kcnn_conv_wgrad_frame(g, in, xs, out_deriv, dys, grad_W, gws, grad_b, workspace,
+                                    workspace_bytes, st)) >= 0)
+      return rc;
     // wgrad_x6: long kernels on the bf16 MFMAs
     if ((rc = wgrad_x6(g, in, xs, out_deriv, dys, grad_W, gws, grad_b, workspace,
                        workspace_bytes, st)) >= 0)
@@ -353,11 +353,12 @@ int hipF_conv2d_dgrad(const float *out_deriv, MatrixDim out_deriv_dim, int in_he
   const int dys = out_deriv_dim.stride, ks = kernel_dim.stride, dxs = in_deriv_dim.stride;
   int rc;
   // fused backward: its data-gradient-only pass (Kdim <= 31)
-  if (kcnn_conv_bwd_frame(g, nullptr, 0, out_deriv, dys, kernel, ks, in_deriv, dxs, nullptr, 0,
-                          nullptr, nullptr, 0, st) == 0)
-    return 0;
+  if ((rc = kcnn_conv_bwd_frame(g, nullptr, 0, out_deriv, dys, kernel, ks, in_deriv, dxs,
+                                nullptr, 0, nullptr, nullptr, 0, st)) >= 0)
+    return rc;
   // frame: Kdim <= 32 with 64 or 128 filters
-  if (kcnn_conv_dgrad_frame(g, out_deriv, dys, kernel, ks, in_deriv, dxs, st) == 0) return 0;
+  if ((rc = kcnn_conv_dgrad_frame(g, out_deriv, dys, kernel, ks, in_deriv, dxs, st)) >= 0)
+    return rc;
   // scatter: long kernels on maps with more positions than the output
   if ((rc = kcnn_conv_dgrad_scatter(g, out_deriv, dys, kernel, ks, in_deriv, dxs, workspace,
                                     workspace_bytes, st)) >= 0)
@@ -452,13 +453,15 @@ int hipF_conv2d_backward(const float *in, MatrixDim in_dim, int in_height, int i
                  in_deriv ? &in_deriv_dim : nullptr}, g) ||
       grad_W == nullptr || too_long(g))
     return kInvalid;
-  // fused backward: dX and gW / gb from one pass over dY (Kdim <= 31)
-  if (g.R > 0 &&
-      kcnn_conv_bwd_frame(g, in, in_dim.stride, out_deriv, out_deriv_dim.stride, kernel,
-                          kernel_dim.stride, in_deriv, in_deriv ? in_deriv_dim.stride : 0,
-                          grad_W, grad_W_dim.stride, grad_b, workspace, workspace_bytes,
-                          as_stream(stream)) == 0)
-    return 0;
+  // fused backward: dX and gW / gb from one pass over dY (Kdim <= 31); a
+  // route that declines (-1) has launched nothing, an error is returned
+  if (g.R > 0) {
+    const int rc = kcnn_conv_bwd_frame(
+        g, in, in_dim.stride, out_deriv, out_deriv_dim.stride, kernel, kernel_dim.stride,
+        in_deriv, in_deriv ? in_deriv_dim.stride : 0, grad_W, grad_W_dim.stride, grad_b,
+        workspace, workspace_bytes, as_stream(stream));
+    if (rc >= 0) return rc;
+  }
   // else the data gradient's routes, then the weight gradient's
   if (in_deriv != nullptr) {
     const int rc = hipF_conv2d_dgrad(out_deriv, out_deriv_dim, in_height, in_width, in_channel,

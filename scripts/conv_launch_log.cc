@@ -6,12 +6,17 @@
 // offset, grid, block, dynamic LDS bytes).  No kernel runs: hipLaunchKernel,
 // the call-configuration pair and the few device calls the host code makes
 // are defined here and take precedence over the runtime's.  The KCNN_*_X6
-// environment variables select the kernel families.  Two builds dispatch
+// environment variables select the kernel families.  Arguments after the
+// library replace the built-in sweep by a list of geometries, each
+// "H,W,C,kh,kw,G,pad_h,pad_w[,rows]" (9 rows when left out); "-" reads them
+// from standard input, one per line (tests/test_conv_routes.py pins the
+// routes of single shapes this way).  Two builds dispatch
 // alike when their logs are equal after scripts/conv_launch_names.py has
 // replaced the handle offsets by symbol names (profiles/conv_dispatch.md):
 //   g++ -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
 //       scripts/conv_launch_log.cc -o conv_launch_log -rdynamic -ldl
 //   ./conv_launch_log kaldi-cnn_amd/libkcnn.so > new.raw
+//   ./conv_launch_log kaldi-cnn_amd/libkcnn.so 20,13,8,3,1,32,0,0 40,61,1,8,3,256,0,0,5
 //   python scripts/conv_launch_names.py kaldi-cnn_amd/libkcnn.so new.raw > new.txt
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -19,6 +24,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <vector>
 
 #include "cnsl-hip-kernels.h"
 
@@ -82,8 +89,28 @@ static F sym(const char *n) {
 
 static MatrixDim md(int r, int c, int s = -1) { return MatrixDim{r, c, s < 0 ? c : s}; }
 
+// a geometry (H, W, C, kh, kw, G, pad_h, pad_w) and the row counts to run it at
+struct Job {
+  int s[8];
+  std::vector<int> rows;
+};
+
+// "H,W,C,kh,kw,G,pad_h,pad_w[,rows]" (blanks also separate)
+static bool parse_job(const char *txt, Job &j) {
+  int *s = j.s, R = 9;
+  const int n = sscanf(txt, "%d%*[, ]%d%*[, ]%d%*[, ]%d%*[, ]%d%*[, ]%d%*[, ]%d%*[, ]%d%*[, ]%d",
+                       s, s + 1, s + 2, s + 3, s + 4, s + 5, s + 6, s + 7, &R);
+  j.rows = {R};
+  if (n < 8) fprintf(stderr, "bad shape: %s\n", txt);
+  return n >= 8;
+}
+
 int main(int argc, char **argv) {
   setvbuf(stdout, nullptr, _IONBF, 0);
+  if (argc < 2) {
+    fprintf(stderr, "usage: %s libkcnn.so [H,W,C,kh,kw,G,pad_h,pad_w[,rows] ... | -]\n", argv[0]);
+    return 2;
+  }
   g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
   if (!g_lib) { fprintf(stderr, "%s\n", dlerror()); return 2; }
   auto conv2d = sym<decltype(&hipF_conv2d)>("hipF_conv2d");
@@ -127,9 +154,36 @@ int main(int argc, char **argv) {
       {14, 9, 64, 7, 5, 36, 3, 2}, {3, 3, 4, 5, 5, 16, 0, 0}, {40, 11, 3, 8, 1, 0, 0, 0},
       {12, 12, 1, 6, 6, 128, 0, 0}, {12, 12, 1, 4, 8, 96, 1, 1}, {20, 20, 5, 2, 3, 128, 0, 0},
       {12, 12, 3, 4, 8, 64, 1, 1}, {12, 12, 3, 4, 8, 128, 1, 1}, {2, 3, 1168, 2, 1, 128, 0, 0},
+      // short kernels past the fused backward's map limits (C*H*W > 2048 or P > 512)
+      {22, 12, 8, 3, 1, 32, 1, 0}, {33, 16, 4, 2, 2, 64, 0, 0}, {20, 13, 8, 3, 1, 256, 0, 0},
+      {20, 13, 8, 3, 1, 160, 0, 0}, {36, 16, 1, 3, 1, 32, 0, 0}, {33, 16, 4, 2, 2, 64, 1, 1},
+      {40, 61, 1, 8, 3, 256, 0, 0}, {43, 13, 1, 2, 2, 128, 0, 0},
   };
-  static const int rows[] = {0, 1, 9, 300, 4096, 9000};
-  for (auto &s : shapes) {
+  std::vector<Job> jobs;
+  if (argc == 2) {  // the built-in sweep
+    for (auto &s : shapes) {
+      Job j{{}, {0, 1, 9, 300, 4096, 9000}};
+      memcpy(j.s, s, sizeof j.s);
+      jobs.push_back(j);
+    }
+  } else if (argc == 3 && strcmp(argv[2], "-") == 0) {
+    char line[256];
+    while (fgets(line, sizeof line, stdin)) {
+      Job j;
+      if (line[strspn(line, " \t\r\n")] == 0) continue;
+      if (!parse_job(line, j)) return 2;
+      jobs.push_back(j);
+    }
+  } else {
+    for (int a = 2; a < argc; a++) {
+      Job j;
+      if (!parse_job(argv[a], j)) return 2;
+      jobs.push_back(j);
+    }
+  }
+  for (auto &job : jobs) {
+    const int *s = job.s;
+    const std::vector<int> &rows = job.rows;
     const int H = s[0], Wd = s[1], C = s[2], kh = s[3], kw = s[4], G = s[5], ph_ = s[6], pw_ = s[7];
     const int oh = H + 2 * ph_ - kh + 1, ow = Wd + 2 * pw_ - kw + 1, P = oh * ow, Kd = kh * kw * C;
     for (int R : rows) {

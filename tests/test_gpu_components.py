@@ -55,6 +55,15 @@ CONVS = {
     # conv_dgrad_frame_kernel<32> / <64>: Kdim 32 (past the fused backward's 31)
     "dgrad_frame_g64": (10, 6, 2, 4, 4, 64, 0, 0),
     "dgrad_frame_g128": (10, 6, 2, 4, 4, 128, 0, 0),
+    # short kernels (Kdim <= 31) past the fused backward's fast kernels, whose
+    # limits are C*H*W <= 2048 and P <= 512 (tests/test_conv_routes.py pins the routes):
+    # C*H*W 2080: conv_bwd_frame_kernel<1, true>, and <1, false> for ComputeGradient
+    "bigmap_G32": (20, 13, 8, 3, 1, 32, 0, 0),
+    # the same map with two filter chunks: conv_bwd_frame_kernel takes one chunk
+    # only, so the data gradient's ladder and conv_wgrad_frame_kernel<2>
+    "bigmap_G256": (20, 13, 8, 3, 1, 256, 0, 0),
+    # P 784: conv_wgrad_frame_kernel<1> and conv_dgrad_frame_kernel<32>
+    "P784_G64": (30, 30, 2, 3, 3, 64, 0, 0),
 }
 
 
@@ -137,6 +146,22 @@ FUSED_BWD = {
     "oh1": ((8, 40, 1, 8, 3, 64, 0, 0), 5),                  # oh = 1
     "c5_C1_G256": ((40, 11, 3, 8, 1, 256, 0, 0), 6),         # 2 chunks of 128 filters
     "G224": ((9, 7, 2, 2, 3, 224, 0, 0), 5),                 # chunks 128 + 96
+    # past those kernels' limits, C*H*W > 2048 or P > 512 (the kernels each case
+    # reaches are asserted in tests/test_conv_routes.py).  C*H*W 2080, Kdim 24,
+    # P 234: the register-staged conv_bwd_frame_kernel<1, true> / <1, false>
+    "bigmap_G32": ((20, 13, 8, 3, 1, 32, 0, 0), 9),
+    "bigmap_G32_grid_stride": ((20, 13, 8, 3, 1, 32, 0, 0), 300),  # R > its 256 workgroups
+    "bigmap_pad": ((22, 12, 8, 3, 1, 32, 1, 0), 9),          # its padded staging, C*Hp*Wp 2304
+    "bigmap_G64_P480": ((33, 16, 4, 2, 2, 64, 0, 0), 9),     # <2, .>, 80 KB of its 96 KB LDS
+    # two chunks there: one route only (dgrad ladder + conv_wgrad_frame_kernel<2>)
+    "bigmap_G256": ((20, 13, 8, 3, 1, 256, 0, 0), 9),
+    "bigmap_G160": ((20, 13, 8, 3, 1, 160, 0, 0), 9),        # chunks 128 + 32
+    "P544_C1": ((36, 16, 1, 3, 1, 32, 0, 0), 9),             # just past 512: wgrad_frame<1>, flip
+    "P784_G64": ((30, 30, 2, 3, 3, 64, 0, 0), 9),            # wgrad_frame<1> + dgrad_frame<32>
+    "P578_pad": ((33, 16, 4, 2, 2, 64, 1, 1), 9),            # the same pair, padded, C*H*W 2112
+    "P1947_G256": ((40, 61, 1, 8, 3, 256, 0, 0), 5),         # 40 x 61 first layer: wgrad_frame<2>
+    # 384 < P <= 512: conv_bwd_dma_kernel<4, ...> at 159,776 B of its 160 KB LDS
+    "P504_G128": ((43, 13, 1, 2, 2, 128, 0, 0), 9),
 }
 
 
@@ -196,27 +221,31 @@ def test_conv_wgrad_long(kc, cfg, N):
     assert_same(host(comp.ComputeGradient(dev(x), dev(dy))), g, what="repeat")
 
 
-def test_conv_backprop_gradient_special_values(kc):
+@pytest.mark.parametrize("name", ["c2", "bigmap_G32"])
+def test_conv_backprop_gradient_special_values(kc, name):
     """Inf in the last map's tail must not leak into other columns: the
-    fused kernel reads row tails past oh*ow (masked to exact zeros)."""
-    cfg = (40, 11, 3, 8, 1, 128, 0, 0)
+    fused kernel reads row tails past oh*ow (masked to exact zeros), and so
+    does the register-staged one (bigmap_G32)."""
+    cfg = CONVS[name]
+    H, W, C, kh, kw, G, ph, pw = cfg
+    P = (H + 2 * ph - kh + 1) * (W + 2 * pw - kw + 1)  # c2: 363, bigmap_G32: 234
     comp, oc = make_pair(kc, cfg, seed=11)
     r = rng(11)
     N = 3
-    x = randn(r, (N, 40 * 11 * 3))
-    dy = randn(r, (N, 363 * 128))
-    dy[1, 5 * 363 + 0] = np.inf      # start of map 5: adjacent to map 4's tail
-    dy[2, 127 * 363 + 362] = -np.inf  # very last element of the frame
+    x = randn(r, (N, H * W * C))
+    dy = randn(r, (N, P * G))
+    dy[1, 5 * P + 0] = np.inf      # start of map 5: adjacent to map 4's tail
+    dy[2, (G - 1) * P + P - 1] = -np.inf  # very last element of the frame
     with O.accum(1):
         gW_t, gb_t = oc.gradient(x, dy)
         dx_t = oc.backprop(x, dy, update=False)
     dx, g = comp.BackpropGradient(dev(x), dev(dy))
     g = host(g)
-    kd = 24
-    gW = g[:kd * 128].reshape(kd, 128)
+    kd = kh * kw * C  # 24 for both
+    gW = g[:kd * G].reshape(kd, G)
     # non-finite pattern identical to the reference's
     np.testing.assert_array_equal(np.isfinite(gW), np.isfinite(gW_t))
-    np.testing.assert_array_equal(np.isfinite(g[kd * 128:]), np.isfinite(gb_t))
+    np.testing.assert_array_equal(np.isfinite(g[kd * G:]), np.isfinite(gb_t))
     np.testing.assert_array_equal(np.isfinite(host(dx)), np.isfinite(dx_t))
 
 
@@ -359,7 +388,8 @@ def test_fc_update_equals_gradient_then_apply(kc, I, Od, N, spread):
 
 
 @pytest.mark.parametrize("name,N", [("c2", 600), ("nnet_cfg_l1", 2048), ("nnet_cfg_l2", 2048),
-                                    ("c5_C3_pad", 1024), ("c5_C4", 1024)])
+                                    ("c5_C3_pad", 1024), ("c5_C4", 1024),
+                                    ("bigmap_G32", 33), ("bigmap_G256", 33), ("P784_G64", 33)])
 def test_conv_update_equals_gradient_then_apply(kc, name, N):
     """ConvolutionComponent's update inside Backprop (:738-777) gives the
     bits of BackpropGradient + ApplyGradient (the DP step's split), and the

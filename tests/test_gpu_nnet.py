@@ -50,6 +50,10 @@ STACKS = {
     # statistics must equal the unfused statistics pass's (bitwise FC output)
     "G128_P300": (32, 10, 3, 3, 1, 128, 4, 16, 0, 0),
     "G128_P352": (39, 11, 3, 8, 1, 128, 4, 16, 0, 0),
+    # C*H*W 2080, past the 2048 of the fused forward (conv_fwd_regs_kernel) and
+    # of the pooled backward's kernels: both decline, the pair runs unfused and
+    # the conv's own Backprop takes the register-staged conv_bwd_frame_kernel
+    "bigmap_pc4": (20, 13, 8, 3, 1, 32, 4, 8, 0, 0),
     # 3-D windows (qh x qw x pc, 16-bit routing mask): (..., pad_h, pad_w, qh, qw)
     "c5_P1_3x1x4": (40, 11, 3, 8, 1, 256, 4, 16, 0, 0, 3, 1),
     "win_2x2x2": (9, 8, 2, 2, 1, 64, 2, 8, 0, 0, 2, 2),
@@ -181,13 +185,16 @@ def _calls(kc, key):
 @pytest.mark.parametrize("name,pooled", [("c2", True), ("pc8_G64", True), ("G256_pc4", True),
                                          ("c5_P1_3x1x4", True), ("win_2x1x8_pad", True),
                                          ("win_2x1x4_G96", True), ("pc2_G96", False),
-                                         ("G48_pad", False), ("win_2x2x2", False)])
+                                         ("G48_pad", False), ("win_2x2x2", False),
+                                         ("bigmap_pc4", False)])
 def test_pooled_backward_path(kc, name, pooled):
     """Fusion mode 1 runs a 1x1x4 / 1x1x8 pool's Backprop (and a 3x1x4, 2x1x4,
     2x1x8 window's) inside the conv's
     (ConvolutionComponent::BackpropPooled); other shapes fall back to
     BackpropFromMask + the conv's own Backprop (the exactness tests above
-    cover both routes)."""
+    cover both routes).  bigmap_pc4's pool folds, but the pooled backward
+    declines the map (C*H*W > 2048): a declined call cancels its profile scope
+    (CuProfileScope::Cancel), so the scope's count stays."""
     key = "ConvolutionComponent::BackpropPooled"
     kc.set_profiling(True)
     try:
@@ -219,11 +226,14 @@ def test_fused_pool_matches_oracle(kc, name, ties):
 
 @pytest.mark.parametrize("name,fused", [("c2", True), ("c5_P1_3x1x4", True),
                                         ("long_2x1x4_pad", True), ("long_1x2x1", True),
-                                        ("long_2x1x2_G96", True), ("pc3_unfused", False)])
+                                        ("long_2x1x2_G96", True), ("pc3_unfused", False),
+                                        ("bigmap_pc4", False)])
 def test_fused_forward_path(kc, name, fused):
     """The conv + pool forward runs as one pass (PropagateMaxpool) for the
     frame kernels' pools and for two-position windows after long kernels
-    (the implicit GEMM's pooled epilogue); other pools run unfused."""
+    (the implicit GEMM's pooled epilogue); other pools run unfused, and so
+    does a fusable pool on a map the fused forward declines (bigmap_pc4: its
+    PropagateMaxpool scope is cancelled, not counted)."""
     key = "ConvolutionComponent::PropagateMaxpool"
     kc.set_profiling(True)
     try:
