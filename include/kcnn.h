@@ -271,10 +271,45 @@ int kcnn_comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const flo
                              int num, const float *probs, MatrixDim p_dim, float *deriv,
                              MatrixDim d_dim, double *tot_objf, double *tot_weight);
 
+/* The forward half of the above plus the frame accuracy (upstream
+ * NnetUpdater::ComputeTotAccuracy over CuMatrixBase::FindRowMaxId, reference
+ * cudamatrix/cu-matrix.h:257), with no derivative: for num HOST elements as
+ * above (checked; an error runs no kernel) and the DEVICE matrix probs,
+ * out[0] = sum weight * log probs(row, col), out[1] = sum weight and out[2] =
+ * the sum of the weights of the elements whose column is their row's best
+ * column: the lowest column whose value is greater than every earlier
+ * column's, the comparison starting from -1e21 (so a NaN is never the best,
+ * and a row may have no best column).  Host fp64, reduced in a fixed order.
+ * Synchronises. */
+int kcnn_comp_objf_accuracy(const int32_t *rows, const int32_t *cols, const float *weights,
+                            int num, const float *probs, MatrixDim p_dim, double out[3]);
+
 /* ---- component stack (NnetUpdater-style) -------------------------------- */
 typedef struct kcnn_nnet kcnn_nnet;
 /* One component initializer line per '\n'-separated line of `config`. */
 kcnn_nnet *kcnn_nnet_new(const char *config);
+/* A whole network from / to a Kaldi stream file in the layout of upstream
+ * Nnet::Read / Nnet::Write (what nnet-init writes and nnet-am-copy and
+ * nnet-train* pass around):
+ *   <Nnet> <NumComponents> int32 n <Components> n x Component::Write
+ *   </Components> </Nnet>
+ * binary after the "\0B" header, else text with a newline after each
+ * component.  Reading expects exactly these tokens in this order, then checks
+ * the network as kcnn_nnet_new does; anything else (a missing or unknown
+ * token, a count that disagrees with the content, a truncated file,
+ * mismatched dimensions) returns NULL with the message in kcnn_last_error().
+ * The AmNnet wrapper of a .mdl file (TransitionModel and priors around the
+ * Nnet) is not read. */
+kcnn_nnet *kcnn_nnet_read(const char *path);
+int kcnn_nnet_write(const kcnn_nnet *n, const char *path, int binary);
+/* nnet-am-copy: a NEW network of Component::Copy()s of n's components; n is
+ * not changed.  scales != NULL (upstream --scales, Nnet::ScaleComponents):
+ * num_scales must be the number of updatable components, and the k-th of them
+ * is scaled by UpdatableComponent::Scale(scales[k]).  remove_dropout != 0
+ * (--remove-dropout, Nnet::RemoveDropout): every DropoutComponent is left
+ * out.  The result is checked as kcnn_nnet_new checks; NULL on error. */
+kcnn_nnet *kcnn_nnet_copy(const kcnn_nnet *n, const float *scales, int num_scales,
+                          int remove_dropout);
 void kcnn_nnet_free(kcnn_nnet *n);
 int kcnn_nnet_num_components(const kcnn_nnet *n);
 kcnn_component *kcnn_nnet_component(kcnn_nnet *n, int i);  /* borrowed */
@@ -325,6 +360,32 @@ int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *co
  * kcnn_nnet_backprop_xent since the last reset (their ratio is the average
  * log-probability per frame); reset != 0 zeroes them.  Synchronises. */
 int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset);
+/* nnet-compute-prob on one minibatch: the forward pass over `in` and, for num
+ * HOST label elements under the contract of kcnn_nnet_backprop_xent (checked
+ * by the same code before anything is launched; a violation runs no kernel),
+ * the objective sum weight * log output(row, col), the weight, and the
+ * accuracy weight of kcnn_comp_objf_accuracy, added to device fp64 totals of
+ * their own (kcnn_nnet_prob_total; not those of kcnn_nnet_objf_total).  The
+ * call does not synchronise.  It changes no parameter, no momentum buffer and
+ * no NonlinearComponent statistic, and it runs the components as they are: a
+ * DropoutComponent still draws its mask, so evaluate the network that
+ * kcnn_nnet_copy(n, scales, k, 1) gives.  When the last component is a
+ * SoftmaxComponent it is not run: one kernel forms each probability from the
+ * logits with the Softmax's own operation sequence and takes the three sums,
+ * and the output matrix is never written; kcnn_set_literal_path(1) asks for
+ * the literal sequence (Propagate, then one pass over the stored output).
+ * Afterwards there is nothing to backpropagate: kcnn_nnet_backprop,
+ * _backprop_component, _backprop_split and _backprop_xent fail until the
+ * next kcnn_nnet_propagate.  kcnn_nnet_output still works: the last output,
+ * where it was not stored, is recomputed on request. */
+int kcnn_nnet_compute_prob(kcnn_nnet *n, const float *in, MatrixDim in_dim,
+                           const int32_t *rows, const int32_t *cols,
+                           const float *weights, int num);
+/* out[0] = the objective, out[1] = the weight and out[2] = the accuracy weight
+ * accumulated by kcnn_nnet_compute_prob since the last reset (out[0] / out[1]
+ * is the average log-probability per frame, out[2] / out[1] the frame
+ * accuracy); reset != 0 zeroes them.  Synchronises. */
+int kcnn_nnet_prob_total(kcnn_nnet *n, double out[3], int reset);
 
 #ifdef __cplusplus
 }

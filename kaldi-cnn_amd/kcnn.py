@@ -70,6 +70,13 @@ def lib():
         L.kcnn_component_learning_rate.restype = ctypes.c_float
         L.kcnn_nnet_new.restype = ctypes.c_void_p
         L.kcnn_nnet_new.argtypes = [ctypes.c_char_p]
+        if hasattr(L, "kcnn_nnet_read"):  # (absent from builds before the <Nnet> files)
+            L.kcnn_nnet_read.restype = ctypes.c_void_p
+            L.kcnn_nnet_read.argtypes = [ctypes.c_char_p]
+            L.kcnn_nnet_write.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+            L.kcnn_nnet_copy.restype = ctypes.c_void_p
+            L.kcnn_nnet_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_int]
         L.kcnn_nnet_free.argtypes = [ctypes.c_void_p]
         L.kcnn_nnet_component.restype = ctypes.c_void_p
         L.kcnn_nnet_component.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -625,18 +632,65 @@ def comp_objf_and_deriv(probs, labels, deriv):
     return objf.value, weight.value
 
 
+def comp_objf_accuracy(probs, labels):
+    """The objective and frame accuracy of nnet-compute-prob on a device
+    matrix (kcnn_comp_objf_accuracy): for the (row, col, weight) elements of
+    `labels` (host) returns (sum of weight * log probs(row, col), sum of
+    weight, sum of the weights of the elements whose column is their row's
+    best column)."""
+    _ensure_init()
+    rows, cols, weights = _label_arrays(labels)
+    out = (ctypes.c_double * 3)()
+    check(lib().kcnn_comp_objf_accuracy(
+        rows.ctypes.data_as(ctypes.c_void_p), cols.ctypes.data_as(ctypes.c_void_p),
+        weights.ctypes.data_as(ctypes.c_void_p), len(rows), ptr(probs), dim(probs), out))
+    return out[0], out[1], out[2]
+
+
 class Nnet:
     """A stack of components run like upstream nnet2's NnetUpdater."""
 
     def __init__(self, config: str):
         _ensure_init()
-        h = lib().kcnn_nnet_new(config.encode())
+        self._adopt(lib().kcnn_nnet_new(config.encode()))
+
+    def _adopt(self, h):
+        self._h = None
         if not h:
             raise KcnnError(lib().kcnn_last_error().decode(errors="replace"))
         self._h = ctypes.c_void_p(h)
         n = lib().kcnn_nnet_num_components(self._h)
         self.components = [Component(lib().kcnn_nnet_component(self._h, i),
                                      owned=False, keep=self) for i in range(n)]
+
+    @classmethod
+    def _from_handle(cls, h) -> "Nnet":
+        net = cls.__new__(cls)
+        net._adopt(h)
+        return net
+
+    @classmethod
+    def Read(cls, path: str) -> "Nnet":
+        """A whole network from a Kaldi <Nnet> stream file, binary or text
+        (kcnn_nnet_read; upstream Nnet::Read)."""
+        _ensure_init()
+        return cls._from_handle(lib().kcnn_nnet_read(str(path).encode()))
+
+    def Write(self, path: str, binary: bool = True):
+        """The network as a Kaldi <Nnet> stream file (upstream Nnet::Write)."""
+        check(lib().kcnn_nnet_write(self._h, str(path).encode(), int(bool(binary))))
+
+    def Copy(self, scales=None, remove_dropout=False) -> "Nnet":
+        """nnet-am-copy: a new network of copies of the components.  scales:
+        one factor per updatable component (--scales); remove_dropout: leave
+        the DropoutComponents out (--remove-dropout).  Both together give the
+        test model of the dropout recipes."""
+        import numpy as np
+        p, n = None, 0
+        if scales is not None:
+            s = np.ascontiguousarray(scales, np.float32).ravel()
+            p, n = s.ctypes.data_as(ctypes.c_void_p), len(s)
+        return Nnet._from_handle(lib().kcnn_nnet_copy(self._h, p, n, int(bool(remove_dropout))))
 
     def __del__(self):
         try:
@@ -723,6 +777,26 @@ class Nnet:
         out = (ctypes.c_double * 2)()
         check(lib().kcnn_nnet_objf_total(self._h, out, int(bool(reset))))
         return out[0], out[1]
+
+    def ComputeProb(self, inp, labels):
+        """nnet-compute-prob on one minibatch (kcnn_nnet_compute_prob): the
+        forward pass over `inp`, then the objective, weight and accuracy
+        weight of `labels` (as for BackpropXent) added to the totals ProbTotal
+        returns.  Changes nothing in the network and does not synchronise;
+        Backprop* raise until the next Propagate."""
+        rows, cols, weights = _label_arrays(labels)
+        self._input = inp
+        check(lib().kcnn_nnet_compute_prob(
+            self._h, ptr(inp), dim(inp), rows.ctypes.data_as(ctypes.c_void_p),
+            cols.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
+            len(rows)))
+
+    def ProbTotal(self, reset=False):
+        """(sum of weight * log-probability, sum of weight, accuracy weight)
+        over the ComputeProb calls since the last reset; synchronises."""
+        out = (ctypes.c_double * 3)()
+        check(lib().kcnn_nnet_prob_total(self._h, out, int(bool(reset))))
+        return out[0], out[1], out[2]
 
 
 def _device_view(addr, d: MatrixDim):

@@ -12,6 +12,7 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../cnslmat/hip-util.h"
@@ -21,6 +22,7 @@
 #include "../kaldi-lite/kaldi-io.h"
 #include "../nnet0/nnet-component-nnet0.h"
 #include "../nnet2/nnet-component.h"
+#include "../nnet2/nnet-kernels.h"
 #include "nnet-stack.h"
 #include "xent-labels.h"
 
@@ -29,7 +31,8 @@ using namespace kaldi::nnet2;
 
 struct kcnn_nnet {
   kcnn::NnetStack stack;
-  explicit kcnn_nnet(const char *config) : stack(config) {}
+  template <typename... Args>
+  explicit kcnn_nnet(Args &&...args) : stack(std::forward<Args>(args)...) {}
 };
 
 namespace {
@@ -621,11 +624,80 @@ int kcnn_comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const flo
   });
 }
 
+int kcnn_comp_objf_accuracy(const int32_t *rows, const int32_t *cols, const float *weights,
+                            int num, const float *probs, MatrixDim p_dim, double *out) {
+  return guard([&] {
+    const std::string bad = kcnn::check_labels(rows, cols, num, p_dim.rows, p_dim.cols, false);
+    if (!bad.empty()) KALDI_ERR << "kcnn_comp_objf_accuracy: " << bad;
+    if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_comp_objf_accuracy: bad label arrays";
+    out[0] = out[1] = out[2] = 0.0;
+    if (num == 0 || p_dim.rows == 0) return;
+    // the kernel takes the labels by row: a stable sort keeps a row's order
+    std::vector<int> order(num);
+    for (int i = 0; i < num; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int a, int b) { return rows[a] < rows[b]; });
+    std::vector<int32_t> r(num), c(num);
+    std::vector<float> w(num);
+    for (int i = 0; i < num; i++) {
+      r[i] = rows[order[i]];
+      c[i] = cols[order[i]];
+      w[i] = weights[order[i]];
+    }
+    const kcnn::LabelLayout lay = kcnn::label_layout(num, p_dim.rows);
+    std::vector<char> image(lay.bytes);
+    kcnn::stage_labels(r.data(), c.data(), w.data(), num, p_dim.rows, image.data());
+    hipStream_t st = CuDevice::Instantiate().Stream();
+    CuScratch dev(lay.bytes), dtot(3 * sizeof(double));
+    CuScratch ws(kn_prob_ws(kn_prob_blocks(p_dim)));
+    CU_SAFE_CALL(hipMemcpyAsync(dev.p, image.data(), lay.bytes, hipMemcpyHostToDevice, st));
+    CU_SAFE_CALL(hipMemsetAsync(dtot.p, 0, 3 * sizeof(double), st));
+    const char *base = static_cast<const char *>(dev.p);
+    {
+      CuProfileScope prof("kn_objf_accuracy");
+      CNSL_SAFE_CALL(kn_objf_accuracy(
+          probs, p_dim, reinterpret_cast<const int32_t *>(base + lay.row_start),
+          reinterpret_cast<const int32_t *>(base + lay.col),
+          reinterpret_cast<const float *>(base + lay.weight), static_cast<double *>(dtot.p),
+          ws.p, reinterpret_cast<kcnn_stream_t>(st)));
+    }
+    CU_SAFE_CALL(hipMemcpyAsync(out, dtot.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    CU_SAFE_CALL(hipStreamSynchronize(st));
+  });
+}
+
 // ---- component stack (kcnn::NnetStack) ---------------------------------------------
 kcnn_nnet *kcnn_nnet_new(const char *config) {
   kcnn_nnet *n = nullptr;
   guard([&] { n = new kcnn_nnet(config); });
   return n;
+}
+kcnn_nnet *kcnn_nnet_read(const char *path) {
+  kcnn_nnet *n = nullptr;
+  guard([&] {
+    std::ifstream is(path, std::ios::binary);
+    if (!is) KALDI_ERR << "cannot open " << path;
+    bool binary = false;
+    if (!InitKaldiInputStream(is, &binary)) KALDI_ERR << "bad Kaldi header in " << path;
+    n = new kcnn_nnet(is, binary);
+  });
+  return n;
+}
+int kcnn_nnet_write(const kcnn_nnet *n, const char *path, int binary) {
+  return guard([&] {
+    std::ofstream os(path, std::ios::binary);
+    if (!os) KALDI_ERR << "cannot open " << path << " for writing";
+    InitKaldiOutputStream(os, binary != 0);
+    n->stack.Write(os, binary != 0);
+    os.flush();
+    if (!os) KALDI_ERR << "write failed: " << path;
+  });
+}
+kcnn_nnet *kcnn_nnet_copy(const kcnn_nnet *n, const float *scales, int num_scales,
+                          int remove_dropout) {
+  kcnn_nnet *copy = nullptr;
+  guard([&] { copy = new kcnn_nnet(n->stack, scales, num_scales, remove_dropout != 0); });
+  return copy;
 }
 void kcnn_nnet_free(kcnn_nnet *n) { delete n; }
 int kcnn_nnet_num_components(const kcnn_nnet *n) { return n->stack.NumComponents(); }
@@ -665,6 +737,14 @@ int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *co
 }
 int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset) {
   return guard([&] { n->stack.ObjfTotal(out, reset != 0); });
+}
+int kcnn_nnet_compute_prob(kcnn_nnet *n, const float *in, MatrixDim in_dim,
+                           const int32_t *rows, const int32_t *cols, const float *weights,
+                           int num) {
+  return guard([&] { n->stack.ComputeProb(in, in_dim, rows, cols, weights, num); });
+}
+int kcnn_nnet_prob_total(kcnn_nnet *n, double out[3], int reset) {
+  return guard([&] { n->stack.ProbTotal(out, reset != 0); });
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <sstream>
 #include <string>
 
+#include "../kaldi-lite/kaldi-io.h"
 #include "../nnet2/nnet-kernels.h"
 #include "xent-labels.h"
 
@@ -50,7 +51,59 @@ NnetStack::NnetStack(const char *config) {
     if (b == std::string::npos || line[b] == '#') continue;
     parsed.emplace_back(Component::NewFromString(line.substr(b)));
   }
-  if (parsed.empty()) KALDI_ERR << "empty nnet config";
+  Init(std::move(parsed));
+}
+
+NnetStack::NnetStack(std::istream &is, bool binary) {
+  ExpectToken(is, binary, "<Nnet>");
+  ExpectToken(is, binary, "<NumComponents>");
+  int32 num = 0;
+  ReadBasicType(is, binary, &num);
+  if (num < 0) KALDI_ERR << "<NumComponents> " << num;
+  ExpectToken(is, binary, "<Components>");
+  std::vector<std::unique_ptr<Component>> parsed;
+  // one at a time: a count the content does not back fails at its first
+  // missing component, whatever it claims
+  for (int32 i = 0; i < num; i++) parsed.emplace_back(Component::ReadNew(is, binary));
+  ExpectToken(is, binary, "</Components>");
+  ExpectToken(is, binary, "</Nnet>");
+  Init(std::move(parsed));
+}
+
+NnetStack::NnetStack(const NnetStack &src, const float *scales, int num_scales,
+                     bool remove_dropout) {
+  int num_updatable = 0;
+  for (const Comp &c : src.comps_) num_updatable += c.updatable != nullptr;
+  if (scales != nullptr && num_scales != num_updatable)
+    KALDI_ERR << num_scales << " scales for " << num_updatable << " updatable components";
+  std::vector<std::unique_ptr<Component>> copies;
+  int k = 0;
+  for (const Comp &c : src.comps_) {
+    const float scale = (c.updatable && scales) ? scales[k] : 1.0f;
+    k += c.updatable != nullptr;
+    if (remove_dropout && dynamic_cast<const DropoutComponent *>(c.c.get())) continue;
+    copies.emplace_back(c.c->Copy());
+    if (c.updatable && scales)
+      dynamic_cast<UpdatableComponent &>(*copies.back()).Scale(scale);
+  }
+  Init(std::move(copies));
+}
+
+void NnetStack::Write(std::ostream &os, bool binary) const {
+  WriteToken(os, binary, "<Nnet>");
+  WriteToken(os, binary, "<NumComponents>");
+  WriteBasicType(os, binary, (int32)comps_.size());
+  WriteToken(os, binary, "<Components>");
+  for (const Comp &c : comps_) {
+    c.c->Write(os, binary);
+    if (!binary) os << std::endl;
+  }
+  WriteToken(os, binary, "</Components>");
+  WriteToken(os, binary, "</Nnet>");
+}
+
+void NnetStack::Init(std::vector<std::unique_ptr<Component>> parsed) {
+  if (parsed.empty()) KALDI_ERR << "a network needs at least one component";
   const size_t nc = parsed.size();
   for (size_t i = 0; i + 1 < nc; i++)
     if (parsed[i]->OutputDim() != parsed[i + 1]->InputDim())
@@ -216,21 +269,32 @@ bool NnetStack::PropagateReluPair(int i) {
   return true;
 }
 
-void NnetStack::Propagate(const float *input, MatrixDim in_dim) {
-  KALDI_ASSERT(in_dim.cols == comps_[0].c->InputDim());
-  const int in_cs = (int)acts_[0].offsets.size();
+// The rows of the last output for an input of in_dim (one per chunk); throws
+// on an input the network cannot take.
+static int checked_num_chunks(MatrixDim in_dim, int input_dim, int in_cs) {
+  KALDI_ASSERT(in_dim.cols == input_dim);
   if (in_dim.rows % in_cs != 0)
     KALDI_ERR << "input rows " << in_dim.rows << " are not a multiple of the "
               << in_cs << "-frame input chunk";
+  return in_dim.rows / in_cs;
+}
+
+void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count) {
+  num_chunks_ =
+      checked_num_chunks(in_dim, comps_[0].c->InputDim(), (int)acts_[0].offsets.size());
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
-  num_chunks_ = in_dim.rows / in_cs;
   ForgetMinibatch();
-  for (int i = 0; i < NumComponents(); i++) {
+  prob_forward_ = false;
+  for (int i = 0; i < count; i++) {
     if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
     ChunkInfo ii = in_info(i), oi = out_info(i);
     auto hint = input_stats(i);
     comps_[i].c->Propagate(ii, oi, in(i).value, &out(i).value);
   }
+}
+
+void NnetStack::Propagate(const float *input, MatrixDim in_dim) {
+  PropagateFirst(input, in_dim, NumComponents());
 }
 
 const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
@@ -240,7 +304,9 @@ const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
     KALDI_ERR << "output of component " << i << " was not stored (fused with the "
               << "next Maxpool, kcnn_set_fusion(1)) and its backprop has run; "
               << "use kcnn_set_fusion(2) to keep it";
-  if (a.stale == kRecomputable) {  // a fused conv's output: run its Propagate now
+  if (a.stale == kRecomputable) {
+    // a fused conv's output, or the last Softmax's after ComputeProb: run its
+    // Propagate (which sizes the matrix) now
     comps_[i].c->Propagate(in_info(i), out_info(i), in(i).value, &a.value);
     a.stale = kStored;
   }
@@ -266,6 +332,7 @@ void NnetStack::BackpropComponent(int i, const float *out_deriv, MatrixDim od_di
                                   BackpropMode mode, float *grad, bool skip_first_dx) {
   const int nc = NumComponents();
   KALDI_ASSERT(i >= 0 && i < nc);
+  RequireTrainingForward("kcnn_nnet_backprop_component");
   Comp &c = comps_[i];
   auto hint = input_stats(i);
   if (out(i).stale == kRecomputable) out(i).stale = kGone;
@@ -313,6 +380,7 @@ void NnetStack::BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, f
                               bool skip_first_dx, void (*between)(void *), void *ctx) {
   const int nc = NumComponents();
   KALDI_ASSERT(i >= 0 && i < nc && grad != NULL);
+  RequireTrainingForward("kcnn_nnet_backprop_split");
   Comp &c = comps_[i];
   if (c.affine == NULL) KALDI_ERR << "kcnn_nnet_backprop_split: component " << i << " is not affine";
   KALDI_ASSERT(!(i + 1 < nc && comps_[i + 1].deriv_deferred) && !c.mask_valid);
@@ -366,6 +434,7 @@ const char *NnetStack::LabelStaging::Stage(const int32_t *rows, const int32_t *c
 void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights,
                              int num, bool skip_first_dx) {
   const int nc = NumComponents();
+  RequireTrainingForward("kcnn_nnet_backprop_xent");
   const Comp &last = comps_[nc - 1];
   const CuMatrix<BaseFloat> &y = out(nc - 1).value;
   const int N = y.NumRows(), dim = last.c->OutputDim();
@@ -374,13 +443,9 @@ void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const flo
   // every check before any launch
   const std::string bad = check_labels(rows, cols, num, N, dim, true);
   if (!bad.empty()) KALDI_ERR << "kcnn_nnet_backprop_xent: " << bad;
-  // the list -> pinned staging buffer -> device, on the library's stream
-  const LabelLayout lay = label_layout(num, N);
-  const char *base = labels_.Stage(rows, cols, weights, num, N, CuDevice::Instantiate().Stream());
-  const int32_t *d_start = reinterpret_cast<const int32_t *>(base + lay.row_start);
-  const int32_t *d_row = reinterpret_cast<const int32_t *>(base + lay.row);
-  const int32_t *d_col = reinterpret_cast<const int32_t *>(base + lay.col);
-  const float *d_w = reinterpret_cast<const float *>(base + lay.weight);
+  const DeviceLabels lab = StageLabels(rows, cols, weights, num, N);
+  const int32_t *d_start = lab.row_start, *d_row = lab.row, *d_col = lab.col;
+  const float *d_w = lab.weight;
   double *tot = objf_totals();
   int first = nc - 1;  // the component the generic backward starts at
   if (last.softmax != nullptr && !cnsl::nnet0::LiteralPath()) {
@@ -398,6 +463,77 @@ void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const flo
   }
   for (int i = first; i >= 0; i--)
     BackpropComponent(i, xent_deriv_.Data(), xent_deriv_.Dim(), kUpdate, nullptr, skip_first_dx);
+}
+
+// The list -> pinned staging buffer -> device, on the library's stream.
+NnetStack::DeviceLabels NnetStack::StageLabels(const int32_t *rows, const int32_t *cols,
+                                               const float *weights, int num, int num_rows) {
+  const LabelLayout lay = label_layout(num, num_rows);
+  const char *base =
+      labels_.Stage(rows, cols, weights, num, num_rows, CuDevice::Instantiate().Stream());
+  DeviceLabels d;
+  d.row_start = reinterpret_cast<const int32_t *>(base + lay.row_start);
+  d.row = reinterpret_cast<const int32_t *>(base + lay.row);
+  d.col = reinterpret_cast<const int32_t *>(base + lay.col);
+  d.weight = reinterpret_cast<const float *>(base + lay.weight);
+  return d;
+}
+
+void NnetStack::RequireTrainingForward(const char *who) const {
+  if (prob_forward_)
+    KALDI_ERR << who << ": the last forward pass was kcnn_nnet_compute_prob's, which keeps "
+              << "nothing for a backprop; run kcnn_nnet_propagate first";
+}
+
+double *NnetStack::prob_totals() {
+  if (!prob_totals_.p)
+    CU_SAFE_CALL(hipMemsetAsync(prob_totals_.reserve(3 * sizeof(double)), 0, 3 * sizeof(double),
+                                CuDevice::Instantiate().Stream()));
+  return static_cast<double *>(prob_totals_.p);
+}
+
+void NnetStack::ComputeProb(const float *input, MatrixDim in_dim, const int32_t *rows,
+                            const int32_t *cols, const float *weights, int num) {
+  const int nc = NumComponents();
+  const Comp &last = comps_[nc - 1];
+  // every check before any launch
+  const int N =
+      checked_num_chunks(in_dim, comps_[0].c->InputDim(), (int)acts_[0].offsets.size());
+  const int dim = last.c->OutputDim();
+  if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_nnet_compute_prob: bad label arrays";
+  const std::string bad = check_labels(rows, cols, num, N, dim, true);
+  if (!bad.empty()) KALDI_ERR << "kcnn_nnet_compute_prob: " << bad;
+  const bool fused = last.softmax != nullptr && !cnsl::nnet0::LiteralPath();
+  // The labels go first: staging waits for the last call's copy to have left
+  // the pinned buffer, and behind the forward pass that wait would be for the
+  // whole of the last call, every call.
+  const DeviceLabels lab = StageLabels(rows, cols, weights, num, N);
+  PropagateFirst(input, in_dim, fused ? nc - 1 : nc);
+  prob_forward_ = true;
+  if (fused) out(nc - 1).stale = kRecomputable;  // the Softmax did not run
+  // the matrix the sums are taken from: the Softmax's input, or the last output
+  const CuMatrix<BaseFloat> &x = fused ? in(nc - 1).value : out(nc - 1).value;
+  KALDI_ASSERT(x.NumRows() == N && x.NumCols() == dim);
+  double *tot = prob_totals();
+  CuScratch ws(kn_prob_ws(kn_prob_blocks(x.Dim())));
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  if (fused) {
+    CuProfileScope prof("kn_softmax_objf_accuracy");
+    CNSL_SAFE_CALL(kn_softmax_objf_accuracy(x.Data(), x.Dim(), lab.row_start, lab.col,
+                                            lab.weight, tot, ws.p, st));
+  } else {
+    CuProfileScope prof("kn_objf_accuracy");
+    CNSL_SAFE_CALL(
+        kn_objf_accuracy(x.Data(), x.Dim(), lab.row_start, lab.col, lab.weight, tot, ws.p, st));
+  }
+}
+
+void NnetStack::ProbTotal(double out[3], bool reset) {
+  hipStream_t st = CuDevice::Instantiate().Stream();
+  double *tot = prob_totals();
+  CU_SAFE_CALL(hipMemcpyAsync(out, tot, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (reset) CU_SAFE_CALL(hipMemsetAsync(tot, 0, 3 * sizeof(double), st));
+  CU_SAFE_CALL(hipStreamSynchronize(st));
 }
 
 void NnetStack::ObjfTotal(double out[2], bool reset) {

@@ -2,12 +2,16 @@
 // kcnn_nnet_* (include/kcnn.h): the chunk offsets (Nnet::ComputeChunkInfo),
 // the Conv -> Maxpool and Conv -> ReLU fused passes and what they leave
 // unstored or deferred, the statistics hand-off to the FC GEMMs, the
-// data-parallel gradient / data-gradient split and the cross-entropy backward.
+// data-parallel gradient / data-gradient split and the cross-entropy backward;
+// and what follows a training iteration: the <Nnet> file (Nnet::Read / Write),
+// the scaled, Dropout-free copy (nnet-am-copy) and ComputeProb
+// (nnet-compute-prob).
 // Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
 // error codes.
 #ifndef KCNN_CAPI_NNET_STACK_H_
 #define KCNN_CAPI_NNET_STACK_H_
 
+#include <iosfwd>
 #include <memory>
 #include <vector>
 
@@ -56,6 +60,18 @@ class NnetStack {
   // One component per config line ('#' comments and blank lines skipped);
   // throws on a bad line, an empty config or mismatched dimensions.
   explicit NnetStack(const char *config);
+  // Upstream Nnet::Read: <Nnet> <NumComponents> n <Components> n x
+  // Component::ReadNew </Components> </Nnet>, then the checks of the config
+  // constructor.  Throws on anything else.
+  NnetStack(std::istream &is, bool binary);
+  // A new stack of src's components' Copy()s (upstream nnet-am-copy): with
+  // scales, the k-th updatable component Scale(scales[k]) (Nnet::
+  // ScaleComponents; num_scales must be their number); with remove_dropout,
+  // without the DropoutComponents (Nnet::RemoveDropout).  Checked as above.
+  NnetStack(const NnetStack &src, const float *scales, int num_scales, bool remove_dropout);
+
+  // Upstream Nnet::Write; in text mode a newline follows each component.
+  void Write(std::ostream &os, bool binary) const;
 
   int NumComponents() const { return (int)comps_.size(); }
   kcnn_component *ComponentAt(int i);  // NULL out of range
@@ -86,6 +102,18 @@ class NnetStack {
                     bool skip_first_dx);
   // {objective, weight} summed since the last reset; synchronises.
   void ObjfTotal(double out[2], bool reset);
+  // nnet-compute-prob on one minibatch: the forward pass, then the objective,
+  // the weight and the accuracy weight of the labels (as for BackpropXent)
+  // added to totals of their own.  No component changes.  A last Softmax is
+  // not run: one kernel takes the three sums from its input (the literal path
+  // runs it and reads its output).  Backprop* throw until the next Propagate;
+  // Output recomputes the unstored last output on request.  Does not
+  // synchronise.
+  void ComputeProb(const float *in, MatrixDim in_dim, const int32_t *rows, const int32_t *cols,
+                   const float *weights, int num);
+  // {objective, weight, accuracy weight} of ComputeProb since the last reset;
+  // synchronises.
+  void ProbTotal(double out[3], bool reset);
 
  private:
   struct Comp {
@@ -151,6 +179,20 @@ class NnetStack {
                       int num_rows, hipStream_t st);
   };
 
+  // the constructors' shared tail: the checks, the kinds, the chunk offsets
+  void Init(std::vector<std::unique_ptr<kaldi::nnet2::Component>> parsed);
+  // Propagate's checks and its first `count` components
+  void PropagateFirst(const float *in, MatrixDim in_dim, int count);
+  void RequireTrainingForward(const char *who) const;
+  // the checked labels staged on the device (xent-labels.h)
+  struct DeviceLabels {
+    const int32_t *row_start, *row, *col;
+    const float *weight;
+  };
+  DeviceLabels StageLabels(const int32_t *rows, const int32_t *cols, const float *weights,
+                           int num, int num_rows);
+  double *prob_totals();
+
   Activation &in(int i) { return acts_[i]; }
   Activation &out(int i) { return acts_[i + 1]; }
   kaldi::nnet2::ChunkInfo in_info(int i);
@@ -169,6 +211,9 @@ class NnetStack {
   int num_chunks_ = 0;
   LabelStaging labels_;
   CuMatrix<BaseFloat> xent_deriv_;  // the literal path's d(last output)
+  kaldi::CuBuffer prob_totals_;     // ComputeProb's fp64 {objective, weight, accuracy}
+  // the last forward was ComputeProb's: there is nothing to backpropagate
+  bool prob_forward_ = false;
 };
 
 }  // namespace kcnn

@@ -99,6 +99,7 @@ void MatrixBase<Real>::Read(std::istream &is, bool binary) {
     int32 r, c;
     ReadBasicType(is, binary, &r);
     ReadBasicType(is, binary, &c);
+    if (r < 0 || c < 0) KALDI_ERR << "bad matrix size " << r << " x " << c;
     Resize(r, c);
     is.read(reinterpret_cast<char *>(data_.data()), sizeof(Real) * data_.size());
     if (is.fail()) KALDI_ERR << "failed to read matrix data";
@@ -166,6 +167,7 @@ void VectorBase<Real>::Read(std::istream &is, bool binary) {
       KALDI_ERR << "expected vector token FV, got " << tok;
     int32 d;
     ReadBasicType(is, binary, &d);
+    if (d < 0) KALDI_ERR << "bad vector size " << d;
     Resize(d);
     is.read(reinterpret_cast<char *>(data_.data()), sizeof(Real) * d);
     if (is.fail()) KALDI_ERR << "failed to read vector data";

@@ -52,7 +52,12 @@ Component *Component::ReadNew(std::istream &is, bool binary) {
   token.erase(token.length() - 1);
   Component *ans = NewComponentOfType(token);
   if (!ans) KALDI_ERR << "Unknown component type " << token;
-  ans->Read(is, binary);
+  try {
+    ans->Read(is, binary);
+  } catch (...) {
+    delete ans;
+    throw;
+  }
   return ans;
 }
 

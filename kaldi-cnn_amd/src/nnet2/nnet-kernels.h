@@ -98,6 +98,31 @@ int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in
                              const float *lab_w, double *value_sum, void *stats_ws, double *tot,
                              void *objf_ws, kcnn_stream_t st);
 
+/* The objective and the frame accuracy of nnet-compute-prob (upstream
+ * NnetUpdater::ComputeObjfAndDeriv without the derivative, ComputeTotAccuracy
+ * over CuMatrixBase::FindRowMaxId, reference cu-matrix.h:257), forward only.
+ * Labels sorted by row as for kn_softmax_xent_backprop (device; all inside the
+ * matrix, none repeated).  tot[0] += sum weight * log((double)probs(row, col)),
+ * tot[1] += sum weight, tot[2] += sum of the weights of the labels whose
+ * column is their row's best column: the lowest column whose value is greater
+ * than every earlier column's, starting from -1e21 (a NaN is never the best;
+ * a row may have none).  Device fp64, per-block partials reduced in a fixed
+ * order.  Each labelled row is read once; nothing but tot and ws is written.
+ * ws: kn_prob_ws(kn_prob_blocks(dim)) bytes. */
+int kn_prob_blocks(MatrixDim dim);
+size_t kn_prob_ws(int num_blocks);
+int kn_objf_accuracy(const float *probs, MatrixDim p_dim, const int *row_start,
+                     const int *lab_col, const float *lab_w, double *tot, void *ws,
+                     kcnn_stream_t st);
+
+/* The same from the logits of a last SoftmaxComponent: each probability is
+ * formed in registers by kn_softmax_prop's operation sequence (the bits
+ * kn_softmax_prop gives for this input into a 16-byte aligned output with a
+ * row stride that is a multiple of 4) and never stored. */
+int kn_softmax_objf_accuracy(const float *logits, MatrixDim l_dim, const int *row_start,
+                             const int *lab_col, const float *lab_w, double *tot, void *ws,
+                             kcnn_stream_t st);
+
 /* DropoutComponent::Propagate (:3592-3625).  The uniform draw of element
  * (row, col) is output col % 4 of Philox4x32-10 with key = seed and counter =
  * (col / 4, row, call low, call high), u = (x >> 8) * 2^-24; then in fp32

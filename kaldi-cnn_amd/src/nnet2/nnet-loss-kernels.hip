@@ -362,6 +362,194 @@ __global__ __launch_bounds__(256) void softmax_xent_block_kernel(
   block_objf_store(objf, wsum, dred, objf_part);
 }
 
+// ---- objective and frame accuracy, forward only (nnet-compute-prob) ----------------------
+// CuMatrixBase::FindRowMaxId: a row's best column is the lowest column whose
+// value is greater than every earlier column's, the comparison starting from
+// -1e21; a NaN is never greater, and a row with no such column has none
+// (kNoBest).  That is the first column holding the largest value above -1e21.
+constexpr float kRowMaxStart = -1.0e21f;
+constexpr int kNoBest = 0x7fffffff;
+
+struct RowBest {
+  float v;
+  int c;
+};
+// a's columns all come before b's, or the two are merged by (value, column)
+__device__ __forceinline__ RowBest better(RowBest a, RowBest b) {
+  return (b.v > a.v || (b.v == a.v && b.c < a.c)) ? b : a;
+}
+__device__ __forceinline__ RowBest wave_best(RowBest a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    RowBest b;
+    b.v = __shfl_xor(a.v, o);
+    b.c = __shfl_xor(a.c, o);
+    a = better(a, b);
+  }
+  return a;
+}
+
+// Each wave's {objective, weight, accuracy weight} (lane 0's), added in wave
+// order into the block's partial.
+__device__ __forceinline__ void block_prob_store(double objf, double wsum, double acc,
+                                                 double (*dred)[3],
+                                                 double *__restrict__ prob_part) {
+  if ((threadIdx.x & 63) == 0) {
+    dred[threadIdx.x >> 6][0] = objf;
+    dred[threadIdx.x >> 6][1] = wsum;
+    dred[threadIdx.x >> 6][2] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3)
+    prob_part[3 * (size_t)blockIdx.x + threadIdx.x] =
+        ((dred[0][threadIdx.x] + dred[1][threadIdx.x]) + dred[2][threadIdx.x]) +
+        dred[3][threadIdx.x];
+}
+
+// One wave per row, four rows to a block, the row in registers.  SOFTMAX: the
+// row holds logits and P is formed as softmax_prop_wave_kernel forms it, to
+// the bit, and never stored; else the row holds P.  Then the row's best
+// column, and per label w log P, w, and w where the label is the best column.
+// A row without labels is not read.  Every lane carries the same totals.
+template <int V, int TOT, bool SOFTMAX>
+__global__ __launch_bounds__(256) void objf_accuracy_wave_kernel(
+    const float *__restrict__ X, int64_t xs, int rows, int cols,
+    const int *__restrict__ row_start, const int *__restrict__ lab_col,
+    const float *__restrict__ lab_w, double *__restrict__ prob_part) {
+  __shared__ double dred[4][3];
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  double objf = 0.0, wsum = 0.0, acc = 0.0;
+  const int lb = r < rows ? row_start[r] : 0, le = r < rows ? row_start[r + 1] : 0;
+  if (lb < le) {
+    float v[TOT];
+    load_row<V, TOT>(X + (int64_t)r * xs, cols, lane, -INFINITY, v);
+    if constexpr (SOFTMAX) {
+      float m = v[0];
+#pragma unroll
+      for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
+      m = wave_max(m);
+      float s = 0.0f;
+#pragma unroll
+      for (int j = 0; j < TOT; j++) {
+        v[j] = expf(v[j] - m);
+        s += v[j];
+      }
+      s = wave_sum(s);
+#pragma unroll
+      for (int j = 0; j < TOT; j++) {
+        float y = v[j] / s;
+        if (y < kSoftmaxFloor) y = kSoftmaxFloor;  // NaN stays
+        v[j] = y;
+      }
+    }
+    RowBest best{kRowMaxStart, kNoBest};
+#pragma unroll
+    for (int j = 0; j < TOT; j++) {  // a lane's columns ascend with j
+      const int c = row_col<V, TOT>(lane, j);
+      if (c < cols && v[j] > best.v) best = RowBest{v[j], c};
+    }
+    best = wave_best(best);
+    for (int l = lb; l < le; l++) {
+      // the label's column is value jl of lane `owner`; jl is wave-uniform
+      const int c = __builtin_amdgcn_readfirstlane(lab_col[l]);
+      if (c < 0 || c >= cols) continue;  // (the hosts validate before they launch)
+      const float lw = lab_w[l];
+      const int q = c / V;
+      const int jl = (q >> 6) * V + (c % V);
+      float pv = 0.0f;
+#pragma unroll
+      for (int j = 0; j < TOT; j++)
+        if (j == jl) pv = v[j];
+      pv = __shfl(pv, q & 63);
+      objf += (double)lw * log((double)pv);
+      wsum += (double)lw;
+      if (c == best.c) acc += (double)lw;
+    }
+  }
+  block_prob_store(objf, wsum, acc, dred, prob_part);
+}
+
+// The four waves' best columns of a block, merged in wave order.
+__device__ __forceinline__ RowBest block_best(RowBest b, RowBest *bred) {
+  b = wave_best(b);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) bred[threadIdx.x >> 6] = b;
+  __syncthreads();
+  return better(better(bred[0], bred[1]), better(bred[2], bred[3]));
+}
+
+// The wide-row form: a block per row.  SOFTMAX forms each P value as
+// softmax_prop_block_kernel does, from logits read three times.
+template <bool SOFTMAX>
+__global__ __launch_bounds__(256) void objf_accuracy_block_kernel(
+    const float *__restrict__ X, int64_t xs, int rows, int cols,
+    const int *__restrict__ row_start, const int *__restrict__ lab_col,
+    const float *__restrict__ lab_w, double *__restrict__ prob_part) {
+  __shared__ float red[4];
+  __shared__ RowBest bred[4];
+  __shared__ double dred[4][3];
+  const int r = blockIdx.x;
+  const float *x = X + (int64_t)r * xs;
+  const int lb = row_start[r], le = row_start[r + 1];
+  double objf = 0.0, wsum = 0.0, acc = 0.0;
+  if (lb < le) {  // block-uniform
+    float m = 0.0f, s = 1.0f;
+    if constexpr (SOFTMAX) {
+      m = -INFINITY;
+      for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
+      m = block_max(m, red);
+      s = 0.0f;
+      for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
+      s = block_sum(s, red);
+    }
+    auto prob = [&](int c) {
+      if constexpr (SOFTMAX) {
+        float y = expf(x[c] - m) / s;
+        if (y < kSoftmaxFloor) y = kSoftmaxFloor;
+        return y;
+      } else {
+        return x[c];
+      }
+    };
+    RowBest best{kRowMaxStart, kNoBest};
+    for (int c = threadIdx.x; c < cols; c += 256) {
+      const float y = prob(c);
+      if (y > best.v) best = RowBest{y, c};
+    }
+    best = block_best(best, bred);
+    for (int l = lb + (int)threadIdx.x; l < le; l += 256) {
+      const int c = lab_col[l];
+      if (c < 0 || c >= cols) continue;
+      const float lw = lab_w[l];
+      objf += (double)lw * log((double)prob(c));
+      wsum += (double)lw;
+      if (c == best.c) acc += (double)lw;
+    }
+    objf = wave_sum(objf);
+    wsum = wave_sum(wsum);
+    acc = wave_sum(acc);
+  }
+  block_prob_store(objf, wsum, acc, dred, prob_part);
+}
+
+// tot[0..2] += the partials' objective, weight and accuracy weight: one wave,
+// each lane its partials in order, then the cross-lane sum.
+__global__ __launch_bounds__(64) void prob_final_kernel(const double *__restrict__ prob_part,
+                                                        int nparts, double *__restrict__ tot) {
+  double t[3] = {0.0, 0.0, 0.0};
+  for (int p = threadIdx.x; p < nparts; p += 64) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] += prob_part[3 * (size_t)p + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) t[k] = wave_sum(t[k]);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) tot[k] += t[k];
+  }
+}
+
 // ---- Dropout -----------------------------------------------------------------------------
 struct Philox4 { uint32_t x, y, z, w; };
 
@@ -653,6 +841,60 @@ int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in
   rc = kcnn::launch_status();
   if (rc || !stats) return rc;
   return finish_colsum(out_value, ov_dim, wide, value_sum, part, s);
+}
+
+}  // extern "C"
+
+namespace {
+template <bool SOFTMAX>
+int launch_objf_accuracy(const float *x, MatrixDim dim, const int *row_start, const int *lab_col,
+                         const float *lab_w, double *tot, void *ws, kcnn_stream_t st) {
+  if (dim.stride < dim.cols || tot == nullptr || ws == nullptr || row_start == nullptr)
+    return (int)hipErrorInvalidValue;
+  const int rows = dim.rows, cols = dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  double *prob_part = static_cast<double *>(ws);
+  hipStream_t s = kcnn::as_stream(st);
+  const int nb = kn_prob_blocks(dim);
+  if (cols > kWaveRowMaxCols) {
+    hipLaunchKernelGGL(objf_accuracy_block_kernel<SOFTMAX>, dim3(nb), dim3(256), 0, s, x,
+                       (int64_t)dim.stride, rows, cols, row_start, lab_col, lab_w, prob_part);
+  } else {
+    const Operand ops[] = {{x, dim.stride}};
+    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+      hipLaunchKernelGGL(
+          (objf_accuracy_wave_kernel<decltype(V)::value, decltype(TOT)::value, SOFTMAX>),
+          dim3(nb), dim3(256), 0, s, x, (int64_t)dim.stride, rows, cols, row_start, lab_col,
+          lab_w, prob_part);
+    });
+  }
+  const int rc = kcnn::launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(prob_final_kernel, dim3(1), dim3(64), 0, s, prob_part, nb, tot);
+  return kcnn::launch_status();
+}
+}  // namespace
+
+extern "C" {
+
+int kn_prob_blocks(MatrixDim dim) {
+  return dim.cols > kWaveRowMaxCols ? dim.rows : (dim.rows + 3) / 4;
+}
+
+size_t kn_prob_ws(int num_blocks) {
+  return (size_t)3 * (num_blocks > 0 ? num_blocks : 1) * sizeof(double);
+}
+
+int kn_objf_accuracy(const float *probs, MatrixDim p_dim, const int *row_start,
+                     const int *lab_col, const float *lab_w, double *tot, void *ws,
+                     kcnn_stream_t st) {
+  return launch_objf_accuracy<false>(probs, p_dim, row_start, lab_col, lab_w, tot, ws, st);
+}
+
+int kn_softmax_objf_accuracy(const float *logits, MatrixDim l_dim, const int *row_start,
+                             const int *lab_col, const float *lab_w, double *tot, void *ws,
+                             kcnn_stream_t st) {
+  return launch_objf_accuracy<true>(logits, l_dim, row_start, lab_col, lab_w, tot, ws, st);
 }
 
 int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
