@@ -472,6 +472,16 @@ def test_fd_gradient_check(kc):
     pred = float((Wd.double().flatten() * g[:kd * 4].double()).sum())
     obs = float((perturbed.Propagate(x).double() * w.double()).sum()) - base
     assert abs(pred - obs) <= 0.05 * abs(pred + obs) / 2 + 1e-4, (pred, obs)
+    # the same prediction as the reference's test forms it: the gradient held
+    # by a component, DotProduct with a component holding the perturbation
+    grad_comp.SetParam(kc.PARAM_LINEAR, g[:kd * 4].reshape(kd, 4))
+    grad_comp.SetParam(kc.PARAM_BIAS, g[kd * 4:])
+    delta_comp = comp.Copy()
+    delta_comp.SetParam(kc.PARAM_LINEAR, Wd)
+    delta_comp.SetParam(kc.PARAM_BIAS, torch.zeros(4, device="cuda"))
+    pred_dp = grad_comp.DotProduct(delta_comp)
+    assert abs(pred_dp - obs) <= 0.05 * abs(pred_dp + obs) / 2 + 1e-4, (pred_dp, obs)
+    assert delta_comp.DotProduct(grad_comp) == pred_dp
 
 
 def test_init_from_string_quirks(kc):

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from _util import dev, randn, rng
+from f16_stats_ref import ebits
 
 pytestmark = pytest.mark.gpu
 
@@ -36,13 +37,6 @@ class PoolStatsOut(ctypes.Structure):
     _fields_ = [("rowmax", ctypes.c_void_p), ("colmax", ctypes.c_void_p),
                 ("partials", ctypes.c_void_p), ("partial_words", ctypes.c_size_t),
                 ("produced", ctypes.c_int)]
-
-
-def ebits(b):
-    """f16-split.h ebits over an array of nonzero |x| bit patterns."""
-    b = b.astype(np.int64)
-    sub = np.floor(np.log2(np.maximum(b, 1))).astype(np.int64) - 149
-    return np.where(b >= 0x00800000, (b >> 23) - 127, sub)
 
 
 def expected(Pm):

@@ -220,6 +220,7 @@ def test_copy_scales(kc):
         for got, want in zip(params(c), params(ref)):
             assert (bits(got) == bits(want)).all()
         assert (bits(params(c)[0]) == bits(params(orig)[0] * np.float32(s))).all()
+        assert (bits(params(c)[1]) == bits(params(orig)[1] * np.float32(s))).all()
     for c, orig in zip(copy.components, net.components):
         if c.NumGradientParams() == 0:
             assert c.Info() == orig.Info()
