@@ -387,6 +387,53 @@ int kcnn_nnet_compute_prob(kcnn_nnet *n, const float *in, MatrixDim in_dim,
  * accuracy); reset != 0 zeroes them.  Synchronises. */
 int kcnn_nnet_prob_total(kcnn_nnet *n, double out[3], int reset);
 
+/* The frames the network reads before / after the frame it computes: the sums
+ * over the components of -Context().front() / Context().back() (upstream
+ * Nnet::LeftContext / Nnet::RightContext; 10 and 10 for nnet.config). */
+int kcnn_nnet_left_context(const kcnn_nnet *n);
+int kcnn_nnet_right_context(const kcnn_nnet *n);
+/* The forward pass of upstream NnetComputer (nnet-am-compute, the decodable
+ * of nnet-latgen-faster) on num_utts >= 1 whole utterances: `in` is the
+ * DEVICE matrix [sum of lengths x InputDim] of their feature frames stacked
+ * row-wise, lengths the HOST array of their frame counts (each >= 1).  Each
+ * utterance is propagated as ONE chunk of many rows (Nnet::ComputeChunkInfo
+ * (num_rows, 1)), all of them in one pass.  With L and R the contexts above:
+ *   pad_input != 0 (upstream's default): an utterance of T frames is seen as
+ *     frames -L .. T-1+R, frame f being frame clamp(f, 0, T-1), and gives T
+ *     rows.  The padded frames are never stored.
+ *   pad_input == 0: it is seen as it is and gives T - L - R rows; T <= L + R
+ *     is an error.
+ * The result, *data / *dim, is a borrowed device view, valid until the next
+ * forward call (kcnn_nnet_propagate, _compute_prob, _compute), of [sum of the
+ * utterances' result rows x OutputDim], utterances in order.  From the last
+ * output P it is
+ *   apply_log != 0: log(max(P, 1e-20)) - prior_scale * log(priors[col])
+ *     (nnet-am-compute --apply-log --divide-by-priors, DecodableAmNnet), a NaN
+ *     staying NaN; priors == NULL drops the second term.  log in fp64 of the
+ *     fp32 P, the log-priors formed on the host in fp64, one fp64 subtraction,
+ *     one rounding to fp32.  A last SoftmaxComponent is then not run: one
+ *     kernel forms each probability from its input and writes the result
+ *     (kcnn_set_literal_path(1): Softmax, then a pass over its stored output;
+ *     the same bits).
+ *   apply_log == 0: P itself; priors are then REFUSED (P / prior^prior_scale
+ *     is not offered).
+ * priors: num_priors == OutputDim HOST floats, all finite and > 0.  Every
+ * check (lengths, their sum against in_dim.rows, the columns, the priors) is
+ * made before anything is launched; a violation is an error that runs no
+ * kernel and leaves the last result as it was.  The call does not synchronise
+ * and reads nothing back.  It changes no component (a DropoutComponent still
+ * draws its mask: use the test model kcnn_nnet_copy(n, scales, k, 1) gives)
+ * and leaves the state kcnn_nnet_compute_prob leaves: the backprop calls fail
+ * until the next kcnn_nnet_propagate, and kcnn_nnet_objf_total / _prob_total
+ * are untouched.  kcnn_nnet_output(n, i) gives layer i's whole-utterance
+ * activation: an utterance has there the rows of its result plus the context
+ * of the components above (i = -1: the input, or, when component 0 is not a
+ * SpliceComponent, pad_input != 0 and L + R > 0, the clamped frames laid out
+ * for it). */
+int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int32_t *lengths,
+                      int num_utts, int pad_input, const float *priors, int num_priors,
+                      float prior_scale, int apply_log, const float **data, MatrixDim *dim);
+
 #ifdef __cplusplus
 }
 #endif

@@ -798,6 +798,48 @@ class Nnet:
         check(lib().kcnn_nnet_prob_total(self._h, out, int(bool(reset))))
         return out[0], out[1], out[2]
 
+    def LeftContext(self):
+        """The frames the network reads before the frame it computes
+        (upstream Nnet::LeftContext)."""
+        return lib().kcnn_nnet_left_context(self._h)
+
+    def RightContext(self):
+        """The frames it reads after that frame (Nnet::RightContext)."""
+        return lib().kcnn_nnet_right_context(self._h)
+
+    def Compute(self, feats, lengths=None, pad_input=True, priors=None, prior_scale=1.0,
+                apply_log=False):
+        """The forward pass of upstream NnetComputer (nnet-am-compute, the
+        decodable) on whole utterances (kcnn_nnet_compute).  `feats`: the
+        utterances' frames stacked row-wise in one device matrix; `lengths`:
+        their frame counts (host; None: one utterance).  With pad_input each
+        utterance is padded with copies of its first and last frame by
+        LeftContext() / RightContext() and gives one row per frame; without,
+        it gives LeftContext() + RightContext() fewer rows.  apply_log: the
+        log of the output, minus prior_scale * log(priors) when `priors` (one
+        per output, host) are given.  Returns a torch view of the result,
+        valid until the next forward call; changes nothing in the network and
+        does not synchronise; Backprop* raise until the next Propagate."""
+        import numpy as np
+        if lengths is None:
+            lengths = [feats.shape[0]]
+        try:
+            lens = np.ascontiguousarray(lengths, np.int32).ravel()
+        except (OverflowError, ValueError) as e:
+            raise KcnnError(f"Compute: bad lengths: {e}") from None
+        pp, np_ = None, 0
+        if priors is not None:
+            pr = np.ascontiguousarray(priors, np.float32).ravel()
+            pp, np_ = pr.ctypes.data_as(ctypes.c_void_p), len(pr)
+        self._input = feats  # the library borrows it as Propagate does
+        p = ctypes.c_void_p()
+        d = MatrixDim()
+        check(lib().kcnn_nnet_compute(
+            self._h, ptr(feats), dim(feats), lens.ctypes.data_as(ctypes.c_void_p), len(lens),
+            int(bool(pad_input)), pp, np_, ctypes.c_float(prior_scale), int(bool(apply_log)),
+            ctypes.byref(p), ctypes.byref(d)))
+        return _device_view(p.value, d)
+
 
 def _device_view(addr, d: MatrixDim):
     """A torch tensor aliasing library-owned device memory (read-mostly)."""

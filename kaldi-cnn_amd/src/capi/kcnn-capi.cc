@@ -746,5 +746,17 @@ int kcnn_nnet_compute_prob(kcnn_nnet *n, const float *in, MatrixDim in_dim,
 int kcnn_nnet_prob_total(kcnn_nnet *n, double out[3], int reset) {
   return guard([&] { n->stack.ProbTotal(out, reset != 0); });
 }
+int kcnn_nnet_left_context(const kcnn_nnet *n) { return n->stack.LeftContext(); }
+int kcnn_nnet_right_context(const kcnn_nnet *n) { return n->stack.RightContext(); }
+int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int32_t *lengths,
+                      int num_utts, int pad_input, const float *priors, int num_priors,
+                      float prior_scale, int apply_log, const float **data, MatrixDim *dim) {
+  return guard([&] {
+    if (data == nullptr || dim == nullptr) KALDI_ERR << "kcnn_nnet_compute: no result pointers";
+    matrix_out(n->stack.Compute(in, in_dim, lengths, num_utts, pad_input != 0, priors,
+                                num_priors, prior_scale, apply_log != 0),
+               data, dim);
+  });
+}
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 
 #include <stdlib.h>
 
+#include <cmath>
 #include <set>
 #include <sstream>
 #include <string>
@@ -123,6 +124,7 @@ void NnetStack::Init(std::vector<std::unique_ptr<Component>> parsed) {
     c.relu = dynamic_cast<RectifiedLinearComponent *>(p);
     c.affine = dynamic_cast<AffineComponent *>(p);
     c.softmax = dynamic_cast<SoftmaxComponent *>(p);
+    c.splice = dynamic_cast<SpliceComponent *>(p);
     c.updatable = dynamic_cast<UpdatableComponent *>(p);
   }
   // The last output is one frame per chunk; walking back, a component's input
@@ -161,9 +163,11 @@ kcnn_component *NnetStack::ComponentAt(int i) {
 }
 
 ChunkInfo NnetStack::in_info(int i) {
+  if (whole_utts_) return ChunkInfo(comps_[i].c->InputDim(), 1, 0, in(i).utt_rows - 1);
   return ChunkInfo(comps_[i].c->InputDim(), num_chunks_, in(i).offsets);
 }
 ChunkInfo NnetStack::out_info(int i) {
+  if (whole_utts_) return ChunkInfo(comps_[i].c->OutputDim(), 1, 0, out(i).utt_rows - 1);
   return ChunkInfo(comps_[i].c->OutputDim(), num_chunks_, out(i).offsets);
 }
 
@@ -284,7 +288,7 @@ void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count) 
       checked_num_chunks(in_dim, comps_[0].c->InputDim(), (int)acts_[0].offsets.size());
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   ForgetMinibatch();
-  prob_forward_ = false;
+  prob_forward_ = whole_utts_ = false;
   for (int i = 0; i < count; i++) {
     if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
     ChunkInfo ii = in_info(i), oi = out_info(i);
@@ -413,6 +417,11 @@ const char *NnetStack::LabelStaging::Stage(const int32_t *rows, const int32_t *c
                                            const float *weights, int num, int num_rows,
                                            hipStream_t st) {
   const size_t bytes = label_layout(num, num_rows).bytes;
+  stage_labels(rows, cols, weights, num, num_rows, Begin(bytes));
+  return Commit(bytes, st);
+}
+
+char *NnetStack::LabelStaging::Begin(size_t bytes) {
   if (copied == nullptr)
     CU_SAFE_CALL(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
   else
@@ -424,8 +433,11 @@ const char *NnetStack::LabelStaging::Stage(const int32_t *rows, const int32_t *c
     CU_SAFE_CALL(hipHostMalloc(&host, bytes, hipHostMallocDefault));
     host_bytes = bytes;
   }
+  return static_cast<char *>(host);
+}
+
+const char *NnetStack::LabelStaging::Commit(size_t bytes, hipStream_t st) {
   dev.reserve(bytes);
-  stage_labels(rows, cols, weights, num, num_rows, host);
   CU_SAFE_CALL(hipMemcpyAsync(dev.p, host, bytes, hipMemcpyHostToDevice, st));
   CU_SAFE_CALL(hipEventRecord(copied, st));
   return static_cast<const char *>(dev.p);
@@ -481,8 +493,9 @@ NnetStack::DeviceLabels NnetStack::StageLabels(const int32_t *rows, const int32_
 
 void NnetStack::RequireTrainingForward(const char *who) const {
   if (prob_forward_)
-    KALDI_ERR << who << ": the last forward pass was kcnn_nnet_compute_prob's, which keeps "
-              << "nothing for a backprop; run kcnn_nnet_propagate first";
+    KALDI_ERR << who << ": the last forward pass was kcnn_nnet_compute_prob's or "
+              << "kcnn_nnet_compute's, which keep nothing for a backprop; run "
+              << "kcnn_nnet_propagate first";
 }
 
 double *NnetStack::prob_totals() {
@@ -526,6 +539,166 @@ void NnetStack::ComputeProb(const float *input, MatrixDim in_dim, const int32_t 
     CNSL_SAFE_CALL(
         kn_objf_accuracy(x.Data(), x.Dim(), lab.row_start, lab.col, lab.weight, tot, ws.p, st));
   }
+}
+
+int NnetStack::LeftContext() const {
+  int left = 0;
+  for (const Comp &c : comps_) left -= c.c->Context().front();
+  return left;
+}
+
+int NnetStack::RightContext() const {
+  int right = 0;
+  for (const Comp &c : comps_) right += c.c->Context().back();
+  return right;
+}
+
+void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
+                                    const int32_t *utt_start, int num_utts, int total,
+                                    bool pad_input, int count) {
+  const int nc = NumComponents();
+  // an activation's extra rows per utterance: the contexts still to come
+  int ext = 0;
+  acts_[nc].utt_ext = 0;
+  for (int k = nc; k-- > 0;) {
+    const std::vector<int32> ctx = comps_[k].c->Context();
+    ext += ctx.back() - ctx.front();
+    acts_[k].utt_ext = ext;
+  }
+  for (Activation &a : acts_) a.utt_rows = total + num_utts * a.utt_ext;
+  const int left = LeftContext();
+  // the caller's frames alone feed a first Splice, which clamps its reads
+  const bool clamp_in_splice = pad_input && ext > 0 && comps_[0].splice != nullptr;
+  if (clamp_in_splice) acts_[0].utt_rows = in_dim.rows;
+  ForgetMinibatch();
+  prob_forward_ = whole_utts_ = true;
+  if (pad_input && ext > 0 && !clamp_in_splice) {
+    // component 0 is row-wise: the clamped frames laid out by a one-slot Splice
+    size_output(&padded_input_, acts_[0].utt_rows, in_dim.cols);
+    kn_ragged_splice_geom g;
+    g.num_utts = num_utts;
+    g.total = total;
+    g.in_ext = 0;
+    g.out_ext = ext;
+    g.shift = g.const_shift = -left;
+    g.dim = in_dim.cols;
+    g.const_dim = 0;
+    g.num_splice = 1;
+    g.context[0] = 0;
+    CuProfileScope prof("kn_splice_ragged_prop");
+    CNSL_SAFE_CALL(kn_splice_ragged_prop(
+        input, in_dim, padded_input_.Data(), padded_input_.Dim(), utt_start, g,
+        reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream())));
+    acts_[0].value.Borrow(padded_input_.Data(), padded_input_.NumRows(),
+                          padded_input_.NumCols(), padded_input_.Stride());
+  } else {
+    acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
+  }
+  KALDI_ASSERT(acts_[0].value.NumRows() == acts_[0].utt_rows);
+  // Every batch of utterances has another row count, and every forward kernel
+  // writes its whole output: the outputs are sized here without the zero fill
+  // of Component::Propagate's Resize (at 26438 rows of nnet.config that fill
+  // is 1.7 ms of an 11.2 ms call, profiles/compute.md).  The literal path
+  // keeps the reference's zeroing Resize.
+  if (!cnsl::nnet0::LiteralPath())
+    for (int i = 0; i < count; i++) {
+      CuMatrix<BaseFloat> &y = out(i).value;
+      if (y.NumRows() != out(i).utt_rows || y.NumCols() != comps_[i].c->OutputDim())
+        y.Resize(out(i).utt_rows, comps_[i].c->OutputDim(), kUndefined);
+    }
+  for (int i = 0; i < count; i++) {
+    if (const SpliceComponent *splice = comps_[i].splice) {
+      const bool clamp = i == 0 && clamp_in_splice;
+      size_output(&out(i).value, out(i).utt_rows, splice->OutputDim());
+      splice->PropagateRagged(in(i).value, &out(i).value, utt_start, num_utts, total,
+                              clamp ? 0 : in(i).utt_ext, out(i).utt_ext, clamp ? left : 0);
+      continue;
+    }
+    if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
+    ChunkInfo ii = in_info(i), oi = out_info(i);
+    auto hint = input_stats(i);
+    comps_[i].c->Propagate(ii, oi, in(i).value, &out(i).value);
+  }
+}
+
+const CuMatrix<BaseFloat> &NnetStack::Compute(const float *input, MatrixDim in_dim,
+                                              const int32_t *lengths, int num_utts,
+                                              bool pad_input, const float *priors,
+                                              int num_priors, float prior_scale,
+                                              bool apply_log) {
+  const int nc = NumComponents();
+  const Comp &last = comps_[nc - 1];
+  const int dim = last.c->OutputDim();
+  const int context = LeftContext() + RightContext();
+  // every check before any launch
+  if (lengths == nullptr || num_utts < 1) KALDI_ERR << "kcnn_nnet_compute: no utterances";
+  if (in_dim.cols != comps_[0].c->InputDim())
+    KALDI_ERR << "kcnn_nnet_compute: input of " << in_dim.cols << " columns for a network of "
+              << comps_[0].c->InputDim();
+  const int min_len = pad_input ? 1 : context + 1;
+  int64_t sum = 0, total = 0;  // input rows, result rows
+  for (int u = 0; u < num_utts; u++) {
+    if (lengths[u] < min_len)
+      KALDI_ERR << "kcnn_nnet_compute: utterance " << u << " has " << lengths[u]
+                << " frames; at least " << min_len << " are needed"
+                << (pad_input ? "" : " without pad_input");
+    sum += lengths[u];
+    total += pad_input ? lengths[u] : lengths[u] - context;
+  }
+  if (sum != in_dim.rows)
+    KALDI_ERR << "kcnn_nnet_compute: the lengths sum to " << sum << ", the input has "
+              << in_dim.rows << " rows";
+  if (total + (int64_t)num_utts * context >= ((int64_t)1 << 31))
+    KALDI_ERR << "kcnn_nnet_compute: too many rows";
+  if (priors != nullptr) {
+    if (!apply_log)
+      KALDI_ERR << "kcnn_nnet_compute: priors without apply_log are not supported";
+    if (num_priors != dim)
+      KALDI_ERR << "kcnn_nnet_compute: " << num_priors << " priors for " << dim << " outputs";
+    for (int c = 0; c < dim; c++)
+      if (!(priors[c] > 0.0f) || !std::isfinite(priors[c]))
+        KALDI_ERR << "kcnn_nnet_compute: prior " << c << " is " << priors[c]
+                  << "; priors must be finite and > 0";
+  }
+  // The starts of the utterances' result rows and the fp64 prior offsets, in
+  // one staged image (first, as ComputeProb stages its labels first).
+  const size_t off_at = ((size_t)(num_utts + 1) * sizeof(int32_t) + 7) / 8 * 8;
+  const size_t bytes = off_at + (priors ? (size_t)dim * sizeof(double) : 0);
+  char *image = utts_.Begin(bytes);
+  int32_t *starts = reinterpret_cast<int32_t *>(image);
+  starts[0] = 0;
+  for (int u = 0; u < num_utts; u++)
+    starts[u + 1] = starts[u] + (pad_input ? lengths[u] : lengths[u] - context);
+  if (priors) {
+    double *off = reinterpret_cast<double *>(image + off_at);
+    for (int c = 0; c < dim; c++) off[c] = (double)prior_scale * log((double)priors[c]);
+  }
+  const char *base = utts_.Commit(bytes, CuDevice::Instantiate().Stream());
+  const int32_t *d_starts = reinterpret_cast<const int32_t *>(base);
+  const double *d_off = priors ? reinterpret_cast<const double *>(base + off_at) : nullptr;
+
+  const bool fused = apply_log && last.softmax != nullptr && !cnsl::nnet0::LiteralPath();
+  PropagateUtterances(input, in_dim, d_starts, num_utts, (int)total, pad_input,
+                      fused ? nc - 1 : nc);
+  if (!apply_log) return out(nc - 1).value;
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  if (loglikes_.NumRows() != total || loglikes_.NumCols() != dim)
+    loglikes_.Resize((int)total, dim, kUndefined);  // written whole
+  if (fused) {
+    out(nc - 1).stale = kRecomputable;  // the Softmax did not run
+    const CuMatrix<BaseFloat> &x = in(nc - 1).value;
+    KALDI_ASSERT(x.NumRows() == total && x.NumCols() == dim);
+    CuProfileScope prof("kn_softmax_loglikes");
+    CNSL_SAFE_CALL(
+        kn_softmax_loglikes(x.Data(), x.Dim(), loglikes_.Data(), loglikes_.Dim(), d_off, st));
+  } else {
+    const CuMatrix<BaseFloat> &p = out(nc - 1).value;
+    KALDI_ASSERT(p.NumRows() == total && p.NumCols() == dim);
+    CuProfileScope prof("kn_loglikes");
+    CNSL_SAFE_CALL(
+        kn_loglikes(p.Data(), p.Dim(), loglikes_.Data(), loglikes_.Dim(), d_off, st));
+  }
+  return loglikes_;
 }
 
 void NnetStack::ProbTotal(double out[3], bool reset) {

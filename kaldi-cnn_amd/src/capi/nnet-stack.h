@@ -4,8 +4,9 @@
 // unstored or deferred, the statistics hand-off to the FC GEMMs, the
 // data-parallel gradient / data-gradient split and the cross-entropy backward;
 // and what follows a training iteration: the <Nnet> file (Nnet::Read / Write),
-// the scaled, Dropout-free copy (nnet-am-copy) and ComputeProb
-// (nnet-compute-prob).
+// the scaled, Dropout-free copy (nnet-am-copy), ComputeProb
+// (nnet-compute-prob) and Compute, the whole-utterance forward pass of
+// upstream NnetComputer (nnet-am-compute, the decodable).
 // Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
 // error codes.
 #ifndef KCNN_CAPI_NNET_STACK_H_
@@ -115,6 +116,39 @@ class NnetStack {
   // synchronises.
   void ProbTotal(double out[3], bool reset);
 
+  // The frames the network reads before / after the frame it computes: the
+  // sums over the components of -Context().front() / Context().back()
+  // (upstream Nnet::LeftContext / RightContext).
+  int LeftContext() const;
+  int RightContext() const;
+  // Upstream NnetComputer on num_utts whole utterances stacked row-wise in
+  // `in` ([sum of lengths x InputDim], device; lengths on the host), each
+  // propagated as ONE chunk of many rows.  pad_input: an utterance of T
+  // frames is seen as frames -L .. T-1+R, frame f being frame clamp(f, 0,
+  // T-1), and gives T rows; else it gives T - L - R rows and T <= L + R is an
+  // error.  The padded frames are never stored: the first SpliceComponent
+  // clamps its reads (when component 0 is not one, a one-slot pass of its
+  // kernel lays the clamped frames out first, and Output(-1) is that
+  // matrix).  Every activation keeps the frames the contexts still to come
+  // need, so rows shrink Splice by Splice, per utterance; all other
+  // components see one chunk of all rows, the fused Conv -> Maxpool and Conv
+  // -> ReLU passes and the statistics hand-off included.  A DropoutComponent
+  // draws its mask: use the test model.
+  // The result (returned; valid until the next forward call), from the last
+  // output P: with apply_log, log(max(P, 1e-20)) - prior_scale * log(prior
+  // [col]) (nnet-am-compute --apply-log --divide-by-priors; kn_loglikes),
+  // without priors (NULL) the log alone; without apply_log, P itself, and
+  // priors are then refused.  priors: OutputDim host floats, all finite and
+  // > 0.  A last Softmax is then not run: one kernel forms each probability
+  // from its input and writes the log-likelihood (the literal path runs it
+  // and reads its output; the same bits).  Every check precedes every launch.
+  // Outputs are sized without Resize's zero fill (every forward kernel writes
+  // its whole output); the literal path keeps the fill.
+  // Leaves the state ComputeProb leaves; does not synchronise.
+  const CuMatrix<BaseFloat> &Compute(const float *in, MatrixDim in_dim, const int32_t *lengths,
+                                     int num_utts, bool pad_input, const float *priors,
+                                     int num_priors, float prior_scale, bool apply_log);
+
  private:
   struct Comp {
     std::unique_ptr<kaldi::nnet2::Component> c;
@@ -126,6 +160,7 @@ class NnetStack {
     kaldi::nnet2::RectifiedLinearComponent *relu = nullptr;
     kaldi::nnet2::AffineComponent *affine = nullptr;
     kaldi::nnet2::SoftmaxComponent *softmax = nullptr;
+    kaldi::nnet2::SpliceComponent *splice = nullptr;
     kaldi::nnet2::UpdatableComponent *updatable = nullptr;
     CuMatrix<BaseFloat> deriv;  // d(input of this component)
     // a pool run fused with the conv below: its routing mask ([rows x
@@ -150,6 +185,9 @@ class NnetStack {
     // Nnet::ComputeChunkInfo).  Gapped contexts (SpliceComponent
     // context=-3:0:3) make a middle layer's offsets non-contiguous.
     std::vector<kaldi::int32> offsets;
+    // Compute: the rows more than its final output frames that an utterance
+    // has here (the contexts still to come), and all the utterances' rows
+    int utt_ext = 0, utt_rows = 0;
     Stale stale = kStored;
     // max |value| per row and per column from the fused forward that wrote
     // it (pool-stats.h), offered to the next component's GEMMs
@@ -164,7 +202,8 @@ class NnetStack {
   };
   // BackpropXent: the label list's pinned staging buffer and its device image
   // (xent-labels.h), the event after which the staging buffer may be
-  // rewritten, and the fp64 {objective, weight} totals on the device
+  // rewritten, and the fp64 {objective, weight} totals on the device.
+  // Compute stages its utterance starts and prior offsets through another.
   struct LabelStaging {
     void *host = nullptr;
     size_t host_bytes = 0;
@@ -174,6 +213,10 @@ class NnetStack {
     ~LabelStaging();  // waits for the last copy to leave `host`
     LabelStaging(const LabelStaging &) = delete;
     LabelStaging &operator=(const LabelStaging &) = delete;
+    // the staging buffer, of `bytes` at least and free to be written
+    char *Begin(size_t bytes);
+    // its first `bytes` -> dev on `st`; returns dev
+    const char *Commit(size_t bytes, hipStream_t st);
     // the checked labels -> host -> dev on `st`; returns dev
     const char *Stage(const int32_t *rows, const int32_t *cols, const float *weights, int num,
                       int num_rows, hipStream_t st);
@@ -192,6 +235,9 @@ class NnetStack {
   DeviceLabels StageLabels(const int32_t *rows, const int32_t *cols, const float *weights,
                            int num, int num_rows);
   double *prob_totals();
+  // Compute's forward pass over the first `count` components
+  void PropagateUtterances(const float *in, MatrixDim in_dim, const int32_t *utt_start,
+                           int num_utts, int total, bool pad_input, int count);
 
   Activation &in(int i) { return acts_[i]; }
   Activation &out(int i) { return acts_[i + 1]; }
@@ -212,8 +258,14 @@ class NnetStack {
   LabelStaging labels_;
   CuMatrix<BaseFloat> xent_deriv_;  // the literal path's d(last output)
   kaldi::CuBuffer prob_totals_;     // ComputeProb's fp64 {objective, weight, accuracy}
-  // the last forward was ComputeProb's: there is nothing to backpropagate
+  // the last forward was ComputeProb's or Compute's: there is nothing to
+  // backpropagate
   bool prob_forward_ = false;
+  // the last forward was Compute's: an activation is one chunk of utt_rows
+  bool whole_utts_ = false;
+  LabelStaging utts_;                   // Compute's utterance starts and prior offsets
+  CuMatrix<BaseFloat> padded_input_;    // Compute's clamped input frames, when laid out
+  CuMatrix<BaseFloat> loglikes_;        // Compute's result with apply_log
 };
 
 }  // namespace kcnn

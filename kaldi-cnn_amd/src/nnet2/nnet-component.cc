@@ -910,6 +910,26 @@ void SpliceComponent::Propagate(const ChunkInfo &in_info, const ChunkInfo &out_i
   CNSL_SAFE_CALL(kn_splice_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), g, NS()));
 }
 
+void SpliceComponent::PropagateRagged(const CuMatrixBase<BaseFloat> &in,
+                                      CuMatrixBase<BaseFloat> *out, const int32 *utt_start,
+                                      int32 num_utts, int32 total, int32 in_ext, int32 out_ext,
+                                      int32 pad_left) const {
+  KALDI_ASSERT(in.NumCols() == input_dim_ && out->NumCols() == OutputDim());
+  kn_ragged_splice_geom g;
+  g.num_utts = num_utts;
+  g.total = total;
+  g.in_ext = in_ext;
+  g.out_ext = out_ext;
+  g.shift = -context_.front() - pad_left;
+  g.const_shift = -pad_left;  // the input row with the output row's in-chunk index
+  g.const_dim = const_component_dim_;
+  g.dim = input_dim_ - const_component_dim_;
+  g.num_splice = (int)context_.size();
+  for (int c = 0; c < g.num_splice; c++) g.context[c] = context_[c];
+  CNSL_SAFE_CALL(
+      kn_splice_ragged_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), utt_start, g, NS()));
+}
+
 void SpliceComponent::Backprop(const ChunkInfo &in_info, const ChunkInfo &out_info,
                                const CuMatrixBase<BaseFloat> &,
                                const CuMatrixBase<BaseFloat> &,

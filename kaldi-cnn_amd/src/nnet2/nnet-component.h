@@ -313,6 +313,17 @@ class SpliceComponent : public Component {
                         const CuMatrixBase<BaseFloat> &out_deriv,
                         Component *to_update,
                         CuMatrix<BaseFloat> *in_deriv) const;
+  // Propagate on whole utterances of different lengths stacked row-wise, each
+  // one chunk (kn_splice_ragged_prop, nnet-kernels.h): utt_start is the
+  // DEVICE table of num_utts + 1 row starts of the final output frames
+  // (utt_start[num_utts] = total); `in` holds in_ext and *out out_ext more
+  // rows an utterance (out_ext = in_ext - (context.back() - context.front())
+  // unless padded).  pad_left > 0: `in` lacks the pad_left frames in front of
+  // each utterance and those behind it that the output rows ask for; a read
+  // of one repeats the utterance's first (last) frame.
+  void PropagateRagged(const CuMatrixBase<BaseFloat> &in, CuMatrixBase<BaseFloat> *out,
+                       const int32 *utt_start, int32 num_utts, int32 total, int32 in_ext,
+                       int32 out_ext, int32 pad_left) const;
   virtual bool BackpropNeedsInput() const { return false; }
   virtual bool BackpropNeedsOutput() const { return false; }
   virtual Component *Copy() const;

@@ -54,6 +54,30 @@ int kn_splice_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_
 int kn_splice_backprop(const float *out_deriv, MatrixDim od_dim, float *in_deriv,
                        MatrixDim id_dim, kn_splice_geom geom, kcnn_stream_t st);
 
+/* SpliceComponent::Propagate on whole utterances of different lengths stacked
+ * row-wise, each one chunk (upstream NnetComputer: Nnet::ComputeChunkInfo
+ * (num_rows, 1) per utterance).  utt_start (DEVICE, num_utts + 1 ascending
+ * entries from 0 to total) holds the row starts of the utterances' final
+ * output frames; an activation carries `ext` more rows per utterance, so
+ * utterance u has utt_start[u + 1] - utt_start[u] + ext rows from row
+ * utt_start[u] + u * ext (in_ext for `in`, out_ext for `out`).  Output row t
+ * of utterance u takes, for context slot c, the utterance's input row
+ * clamp(t + context[c] + shift, 0, its last row); the const_dim tail copies
+ * its input row clamp(t + const_shift, ...).  The clamp repeats the first and
+ * the last frame (NnetComputer's pad_input) where shift asks for rows the
+ * input does not hold; elsewhere it never acts.  A row's utterance is found
+ * by a search over utt_start: their number and lengths are bounded by the
+ * matrices alone (fewer than 2^31 rows, fewer than 2^31 elements a matrix). */
+typedef struct {
+  int num_utts, total;
+  int in_ext, out_ext;
+  int shift, const_shift;
+  int dim, const_dim, num_splice;
+  int context[KN_SPLICE_MAX_CONTEXT];
+} kn_ragged_splice_geom;
+int kn_splice_ragged_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                          const int *utt_start, kn_ragged_splice_geom geom, kcnn_stream_t st);
+
 /* fp64 stat vectors of NonlinearComponent (Scale/Add/UpdateStats):
  * y = beta * y + alpha * x  (x may be NULL: y = beta * y). */
 int kn_dvec_update(double *y, const double *x, double alpha, double beta, int n,
@@ -122,6 +146,20 @@ int kn_objf_accuracy(const float *probs, MatrixDim p_dim, const int *row_start,
 int kn_softmax_objf_accuracy(const float *logits, MatrixDim l_dim, const int *row_start,
                              const int *lab_col, const float *lab_w, double *tot, void *ws,
                              kcnn_stream_t st);
+
+/* The log-likelihoods of upstream nnet-am-compute --apply-log
+ * --divide-by-priors (DecodableAmNnet): out(r, c) = (float)(log((double)
+ * max(probs(r, c), 1e-20f)) - offset[c]), a NaN staying NaN (ApplyFloor).
+ * offset: DEVICE fp64, cols entries (prior_scale * log prior[c], formed on
+ * the host), or NULL for none.  One fp64 subtraction, one rounding. */
+int kn_loglikes(const float *probs, MatrixDim p_dim, float *out, MatrixDim out_dim,
+                const double *offset, kcnn_stream_t st);
+
+/* The same from the logits of a last SoftmaxComponent, each probability formed
+ * in registers as kn_softmax_objf_accuracy forms it and never stored: the bits
+ * of kn_softmax_prop into an output laid out as `out`, then kn_loglikes. */
+int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, MatrixDim out_dim,
+                        const double *offset, kcnn_stream_t st);
 
 /* DropoutComponent::Propagate (:3592-3625).  The uniform draw of element
  * (row, col) is output col % 4 of Philox4x32-10 with key = seed and counter =

@@ -4,6 +4,8 @@
 // ReLU statistics reduced in a fixed order (deterministic).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "nnet-kernels.h"
 #include "../cnslmat/hip-util.h"
 
@@ -153,6 +155,75 @@ __global__ __launch_bounds__(256) void splice_prop_kernel(const float *__restric
       icol = g.dim + ((int)col - g.num_splice * g.dim);
     }
     out[(int64_t)orow * os + col] = in[(int64_t)irow * is + icol];
+  }
+}
+
+// The whole-utterance form (kn_splice_ragged_prop): a block takes groups of
+// `rpb` consecutive output rows.  One thread per row finds the row's
+// utterance (a binary search over the num_utts + 1 starts, which stay in the
+// caches) and leaves the utterance's first input row, its last in-utterance
+// index and the row's own index in LDS; then all 256 threads copy the group's
+// V-float units, so narrow rows fill the lanes as wide ones do.  V = 4: 16-byte
+// accesses (dim, const_dim and both strides multiples of 4, bases aligned).
+constexpr int kRaggedMaxRows = 64;  // rows of a group
+struct RaggedArgs {
+  kn_ragged_splice_geom g;
+  int in_rows, out_rows, rpb;
+  FastDiv div_units, div_dim;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void splice_ragged_kernel(const float *__restrict__ in,
+                                                            int64_t is, float *__restrict__ out,
+                                                            int64_t os,
+                                                            const int *__restrict__ utt_start,
+                                                            RaggedArgs a) {
+  __shared__ int s_first[kRaggedMaxRows], s_last[kRaggedMaxRows], s_t[kRaggedMaxRows];
+  const kn_ragged_splice_geom &g = a.g;
+  const int units = (g.num_splice * g.dim + g.const_dim) / V;
+  const int ngroups = (a.out_rows + a.rpb - 1) / a.rpb;
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int r0 = grp * a.rpb;
+    const int nr = min(a.rpb, a.out_rows - r0);
+    __syncthreads();  // the last group's readers are done
+    if ((int)threadIdx.x < nr) {
+      const int r = r0 + (int)threadIdx.x;
+      int lo = 0, hi = g.num_utts;  // start(lo) <= r < start(hi)
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (utt_start[mid] + mid * g.out_ext <= r) lo = mid; else hi = mid;
+      }
+      const int s0 = utt_start[lo], frames = utt_start[lo + 1] - s0;
+      s_first[threadIdx.x] = s0 + lo * g.in_ext;
+      s_last[threadIdx.x] = frames + g.in_ext - 1;
+      s_t[threadIdx.x] = r - (s0 + lo * g.out_ext);
+    }
+    __syncthreads();
+    const int n = nr * units;
+    for (int e = threadIdx.x; e < n; e += 256) {
+      uint32_t lr, cu;
+      a.div_units.divmod((uint32_t)e, lr, cu);
+      const int col = (int)cu * V;
+      int idx, icol;
+      if (col < g.num_splice * g.dim) {
+        uint32_t c, d;
+        a.div_dim.divmod((uint32_t)col, c, d);
+        idx = s_t[lr] + g.context[c] + g.shift;
+        icol = (int)d;
+      } else {
+        idx = s_t[lr] + g.const_shift;
+        icol = g.dim + (col - g.num_splice * g.dim);
+      }
+      idx = max(0, min(idx, s_last[lr]));
+      // (a table that disagrees with the matrices still reads inside `in`)
+      const int irow = max(0, min(s_first[lr] + idx, a.in_rows - 1));
+      const float *src = in + (int64_t)irow * is + icol;
+      float *dst = out + (int64_t)(r0 + (int)lr) * os + col;
+      if constexpr (V == 4)
+        *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
+      else
+        *dst = *src;
+    }
   }
 }
 
@@ -308,6 +379,44 @@ int kn_splice_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_
   hipLaunchKernelGGL(splice_prop_kernel, dim3(kcnn::grid_for(total)), dim3(256), 0,
                      kcnn::as_stream(st), in, (int64_t)in_dim.stride, out,
                      (int64_t)out_dim.stride, splice_args(g, out_dim.cols), total);
+  return kcnn::launch_status();
+}
+
+int kn_splice_ragged_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
+                          const int *utt_start, kn_ragged_splice_geom g, kcnn_stream_t st) {
+  const int64_t in_rows = (int64_t)g.total + (int64_t)g.num_utts * g.in_ext;
+  const int64_t out_rows = (int64_t)g.total + (int64_t)g.num_utts * g.out_ext;
+  if (utt_start == nullptr || g.num_utts <= 0 || g.total < g.num_utts || g.in_ext < 0 ||
+      g.out_ext < 0 || g.dim <= 0 || g.const_dim < 0 || g.num_splice <= 0 ||
+      g.num_splice > KN_SPLICE_MAX_CONTEXT || in_rows != in_dim.rows ||
+      out_rows != out_dim.rows || in_dim.cols != g.dim + g.const_dim ||
+      out_dim.cols != g.num_splice * g.dim + g.const_dim || in_dim.stride < in_dim.cols ||
+      out_dim.stride < out_dim.cols)
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)out_dim.rows * out_dim.cols >= ((int64_t)1 << 31) ||
+      (int64_t)in_dim.rows * in_dim.cols >= ((int64_t)1 << 31))
+    return (int)hipErrorInvalidValue;
+  const bool vec4 = g.dim % 4 == 0 && g.const_dim % 4 == 0 && in_dim.stride % 4 == 0 &&
+                    out_dim.stride % 4 == 0 && (uintptr_t)in % 16 == 0 &&
+                    (uintptr_t)out % 16 == 0;
+  const int v = vec4 ? 4 : 1;
+  const int units = out_dim.cols / v;
+  RaggedArgs a;
+  a.g = g;
+  a.in_rows = in_dim.rows;
+  a.out_rows = out_dim.rows;
+  // about four units a thread and group
+  a.rpb = std::max(1, std::min(kRaggedMaxRows, 1024 / units));
+  a.div_units = FastDiv((uint32_t)units);
+  a.div_dim = FastDiv((uint32_t)g.dim);
+  const int ngroups = (out_dim.rows + a.rpb - 1) / a.rpb;
+  const dim3 grid((unsigned)std::min(ngroups, 256 * 32));
+  if (vec4)
+    hipLaunchKernelGGL(splice_ragged_kernel<4>, grid, dim3(256), 0, kcnn::as_stream(st), in,
+                       (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, utt_start, a);
+  else
+    hipLaunchKernelGGL(splice_ragged_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), in,
+                       (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, utt_start, a);
   return kcnn::launch_status();
 }
 

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "nnet-kernels.h"
@@ -550,6 +551,76 @@ __global__ __launch_bounds__(64) void prob_final_kernel(const double *__restrict
   }
 }
 
+// ---- log-likelihoods (nnet-am-compute --apply-log --divide-by-priors) ----------------------
+// ApplyFloor(1e-20) (NaN stays), the fp64 log of the fp32 probability, one
+// fp64 subtraction of the column's offset (prior_scale * log prior, formed
+// on the host; 0 without priors) and one rounding to fp32.
+__device__ __forceinline__ float loglike(float p, double offset) {
+  if (p < kSoftmaxFloor) p = kSoftmaxFloor;
+  return (float)(log((double)p) - offset);
+}
+
+// A stored P, element-wise: 256 consecutive columns x rows grid-strided.
+__global__ __launch_bounds__(256) void loglikes_kernel(const float *__restrict__ P, int64_t ps,
+                                                       float *__restrict__ out, int64_t os,
+                                                       int rows, int cols,
+                                                       const double *__restrict__ offset) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cols) return;
+  const double off = offset ? offset[c] : 0.0;
+  for (int r = blockIdx.y; r < rows; r += gridDim.y)
+    out[(int64_t)r * os + c] = loglike(P[(int64_t)r * ps + c], off);
+}
+
+// From the logits of a last SoftmaxComponent: P formed in registers as
+// softmax_prop_wave_kernel forms it, to the bit, and never stored.
+template <int V, int TOT>
+__global__ __launch_bounds__(256) void softmax_loglikes_wave_kernel(
+    const float *__restrict__ in, int64_t is, float *__restrict__ out, int64_t os, int rows,
+    int cols, const double *__restrict__ offset) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  float v[TOT];
+  load_row<V, TOT>(in + (int64_t)r * is, cols, lane, -INFINITY, v);
+  float m = v[0];
+#pragma unroll
+  for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
+  m = wave_max(m);
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TOT; j++) {
+    v[j] = expf(v[j] - m);
+    s += v[j];
+  }
+  s = wave_sum(s);
+#pragma unroll
+  for (int j = 0; j < TOT; j++) {
+    const int c = row_col<V, TOT>(lane, j);
+    if (c < cols) v[j] = loglike(v[j] / s, offset ? offset[c] : 0.0);
+  }
+  store_row<V, TOT>(out + (int64_t)r * os, cols, lane, v);
+}
+
+// The wide-row form, as softmax_prop_block_kernel.
+__global__ __launch_bounds__(256) void softmax_loglikes_block_kernel(
+    const float *__restrict__ in, int64_t is, float *__restrict__ out, int64_t os, int rows,
+    int cols, const double *__restrict__ offset) {
+  __shared__ float red[4];
+  for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float *x = in + (int64_t)r * is;
+    float *y = out + (int64_t)r * os;
+    float m = -INFINITY;
+    for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
+    m = block_max(m, red);
+    float s = 0.0f;
+    for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
+    s = block_sum(s, red);
+    for (int c = threadIdx.x; c < cols; c += 256)
+      y[c] = loglike(expf(x[c] - m) / s, offset ? offset[c] : 0.0);
+  }
+}
+
 // ---- Dropout -----------------------------------------------------------------------------
 struct Philox4 { uint32_t x, y, z, w; };
 
@@ -895,6 +966,41 @@ int kn_softmax_objf_accuracy(const float *logits, MatrixDim l_dim, const int *ro
                              const int *lab_col, const float *lab_w, double *tot, void *ws,
                              kcnn_stream_t st) {
   return launch_objf_accuracy<true>(logits, l_dim, row_start, lab_col, lab_w, tot, ws, st);
+}
+
+int kn_loglikes(const float *probs, MatrixDim p_dim, float *out, MatrixDim out_dim,
+                const double *offset, kcnn_stream_t st) {
+  if (!same_shape(p_dim, out_dim) || p_dim.stride < p_dim.cols || out_dim.stride < out_dim.cols)
+    return (int)hipErrorInvalidValue;
+  const int rows = p_dim.rows, cols = p_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  const unsigned cb = (unsigned)((cols + 255) / 256);
+  const unsigned rb = std::min(std::min((unsigned)rows, 8192u / cb + 1u), 65535u);
+  hipLaunchKernelGGL(loglikes_kernel, dim3(cb, rb), dim3(256), 0, kcnn::as_stream(st), probs,
+                     (int64_t)p_dim.stride, out, (int64_t)out_dim.stride, rows, cols, offset);
+  return kcnn::launch_status();
+}
+
+int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, MatrixDim out_dim,
+                        const double *offset, kcnn_stream_t st) {
+  if (!same_shape(l_dim, out_dim) || l_dim.stride < l_dim.cols || out_dim.stride < out_dim.cols)
+    return (int)hipErrorInvalidValue;
+  const int rows = l_dim.rows, cols = l_dim.cols;
+  if (rows == 0 || cols == 0) return 0;
+  hipStream_t s = kcnn::as_stream(st);
+  if (cols > kWaveRowMaxCols) {
+    hipLaunchKernelGGL(softmax_loglikes_block_kernel, dim3(row_blocks(rows)), dim3(256), 0, s,
+                       logits, (int64_t)l_dim.stride, out, (int64_t)out_dim.stride, rows, cols,
+                       offset);
+    return kcnn::launch_status();
+  }
+  const Operand ops[] = {{logits, l_dim.stride}, {out, out_dim.stride}};
+  dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+    hipLaunchKernelGGL((softmax_loglikes_wave_kernel<decltype(V)::value, decltype(TOT)::value>),
+                       dim3((rows + 3) / 4), dim3(256), 0, s, logits, (int64_t)l_dim.stride, out,
+                       (int64_t)out_dim.stride, rows, cols, offset);
+  });
+  return kcnn::launch_status();
 }
 
 int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
