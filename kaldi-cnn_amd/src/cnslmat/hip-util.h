@@ -1,9 +1,11 @@
-// cnslmat/hip-util.h -- small device helpers shared by the gfx950 kernels.
+// cnslmat/hip-util.h -- small device and launch helpers shared by the gfx950 kernels.
 #ifndef KCNN_CNSLMAT_HIP_UTIL_H_
 #define KCNN_CNSLMAT_HIP_UTIL_H_
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "cnsl-hip-kernels.h"
 #include "kaldi-lite/kcnn-knobs.h"
@@ -49,6 +51,28 @@ inline unsigned grid_for(int64_t n, int block = 256) {
   if (b < 1) b = 1;
   if (b > 256 * 32) b = 256 * 32;
   return (unsigned)b;
+}
+
+// The grid of an element-wise kernel whose block takes `cols_per_block`
+// consecutive columns and grid-strides the rows over blockIdx.y: ~8k blocks.
+inline dim3 elementwise_grid(int rows, int cols, int cols_per_block) {
+  const unsigned cb = (unsigned)((cols + cols_per_block - 1) / cols_per_block);
+  unsigned rb = (unsigned)rows;
+  if (rb > 8192u / cb + 1u) rb = 8192u / cb + 1u;
+  if (rb > 65535u) rb = 65535u;
+  return dim3(cb, rb);
+}
+
+// The argument checks of the extern "C" entry points.
+inline bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols == b.cols; }
+inline bool contiguous_enough(MatrixDim d) { return d.stride >= d.cols; }
+
+// f(std::true_type or std::false_type) for a runtime flag that is a kernel's
+// template parameter.
+template <typename F>
+void with_bool(bool flag, F f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 }  // namespace kcnn

@@ -287,17 +287,13 @@ int kn_relu_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_di
   const bool vec4 = in_dim.cols % 4 == 0 && in_dim.stride % 4 == 0 && out_dim.stride % 4 == 0 &&
                     (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
   const int cpb = vec4 ? 1024 : 256;  // columns per block
-  const unsigned cb = (unsigned)((in_dim.cols + cpb - 1) / cpb);
-  unsigned rb = (unsigned)in_dim.rows;
-  const unsigned cap = 8192u / cb + 1u;  // ~8k blocks, rows grid-strided
-  if (rb > cap) rb = cap;
-  if (rb > 65535u) rb = 65535u;
+  const dim3 grid = kcnn::elementwise_grid(in_dim.rows, in_dim.cols, cpb);
   if (vec4)
-    hipLaunchKernelGGL(relu_prop4_kernel, dim3(cb, rb), dim3(256), 0, kcnn::as_stream(st), in,
+    hipLaunchKernelGGL(relu_prop4_kernel, grid, dim3(256), 0, kcnn::as_stream(st), in,
                        (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, in_dim.rows,
                        in_dim.cols);
   else
-    hipLaunchKernelGGL(relu_prop_kernel, dim3(cb, rb), dim3(256), 0, kcnn::as_stream(st), in,
+    hipLaunchKernelGGL(relu_prop_kernel, grid, dim3(256), 0, kcnn::as_stream(st), in,
                        (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, in_dim.rows,
                        in_dim.cols);
   return kcnn::launch_status();

@@ -15,22 +15,21 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include <algorithm>
-#include <type_traits>
-
 #include "nnet-kernels.h"
 #include "row-regs.h"
 #include "../cnslmat/hip-util.h"
 
 using kcnn::FastDiv;
+using kcnn::contiguous_enough;
+using kcnn::same_shape;
 using namespace kcnn::rowregs;
 
 namespace {
 
-constexpr float kSoftmaxFloor = 1.0e-20f;
-
 // ---- Softmax Propagate ---------------------------------------------------------
-// One wave per row, four rows to a block.
+// One wave per row, four rows to a block.  Every kernel below that forms P
+// from logits forms it with the same softmax_row, or softmax_max_sum and
+// softmax_value (row-regs.h): the same bits as the P stored here.
 template <int V, int TOT>
 __global__ __launch_bounds__(256) void softmax_prop_wave_kernel(const float *__restrict__ in,
                                                                 int64_t is,
@@ -41,40 +40,8 @@ __global__ __launch_bounds__(256) void softmax_prop_wave_kernel(const float *__r
   if (r >= rows) return;
   float v[TOT];
   load_row<V, TOT>(in + (int64_t)r * is, cols, lane, -INFINITY, v);
-  float m = v[0];
-#pragma unroll
-  for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
-  m = wave_max(m);
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < TOT; j++) {
-    v[j] = expf(v[j] - m);  // the accurate exp: the 1e-5 bar holds down to x - m = -46
-    s += v[j];
-  }
-  s = wave_sum(s);
-#pragma unroll
-  for (int j = 0; j < TOT; j++) {
-    float y = v[j] / s;
-    if (y < kSoftmaxFloor) y = kSoftmaxFloor;  // ApplyFloor(1e-20); NaN stays
-    v[j] = y;
-  }
+  softmax_row<TOT>(v);
   store_row<V, TOT>(out + (int64_t)r * os, cols, lane, v);
-}
-
-// The four waves' values of a block reduction, combined in wave order.
-__device__ __forceinline__ float block_max(float v, float *red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float block_sum(float v, float *red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // Rows wider than a wave holds: a block per row, the row read three times.
@@ -86,17 +53,8 @@ __global__ __launch_bounds__(256) void softmax_prop_block_kernel(const float *__
   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
     const float *x = in + (int64_t)r * is;
     float *y = out + (int64_t)r * os;
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
-    m = block_max(m, red);
-    float s = 0.0f;
-    for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
-    s = block_sum(s, red);
-    for (int c = threadIdx.x; c < cols; c += 256) {
-      float v = expf(x[c] - m) / s;
-      if (v < kSoftmaxFloor) v = kSoftmaxFloor;
-      y[c] = v;
-    }
+    const RowMaxSum ms = softmax_max_sum(x, cols, red);
+    for (int c = threadIdx.x; c < cols; c += 256) y[c] = softmax_value(x[c], ms);
   }
 }
 
@@ -220,24 +178,51 @@ __global__ __launch_bounds__(256) void softmax_backprop_block_kernel(
   }
 }
 
-// ---- CompObjfAndDeriv ----------------------------------------------------------------
-// The objective terms of a block, reduced in a fixed order into its partial.
-__device__ __forceinline__ void block_objf_store(double objf, double wsum, double (*dred)[2],
-                                                 double *__restrict__ objf_part) {
-  objf = wave_sum(objf);
-  wsum = wave_sum(wsum);
+// ---- N totals in a fixed order ---------------------------------------------------------
+// {objective, weight} (N = 2) and {objective, weight, accuracy weight}
+// (N = 3).  Each wave's terms (lane 0's: the caller has summed over the lanes
+// where they differ) added in wave order into the block's partial.
+template <int N>
+__device__ __forceinline__ void block_terms_store(const double (&t)[N], double (*dred)[N],
+                                                  double *__restrict__ part) {
   if ((threadIdx.x & 63) == 0) {
-    dred[threadIdx.x >> 6][0] = objf;
-    dred[threadIdx.x >> 6][1] = wsum;
+#pragma unroll
+    for (int k = 0; k < N; k++) dred[threadIdx.x >> 6][k] = t[k];
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    objf_part[2 * (size_t)blockIdx.x] = ((dred[0][0] + dred[1][0]) + dred[2][0]) + dred[3][0];
-    objf_part[2 * (size_t)blockIdx.x + 1] =
-        ((dred[0][1] + dred[1][1]) + dred[2][1]) + dred[3][1];
-  }
+  if (threadIdx.x < N)
+    part[N * (size_t)blockIdx.x + threadIdx.x] =
+        ((dred[0][threadIdx.x] + dred[1][threadIdx.x]) + dred[2][threadIdx.x]) +
+        dred[3][threadIdx.x];
 }
 
+// tot[k] += the partials' term k: one wave, each lane its partials in order,
+// then the cross-lane sum.
+template <int N>
+__device__ __forceinline__ void terms_final(const double *__restrict__ part, int nparts,
+                                            double *__restrict__ tot) {
+  double t[N] = {};
+  for (int p = threadIdx.x; p < nparts; p += 64) {
+#pragma unroll
+    for (int k = 0; k < N; k++) t[k] += part[N * (size_t)p + k];
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) t[k] = wave_sum(t[k]);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < N; k++) tot[k] += t[k];
+  }
+}
+__global__ __launch_bounds__(64) void objf_final_kernel(const double *__restrict__ objf_part,
+                                                        int nparts, double *__restrict__ tot) {
+  terms_final<2>(objf_part, nparts, tot);
+}
+__global__ __launch_bounds__(64) void prob_final_kernel(const double *__restrict__ prob_part,
+                                                        int nparts, double *__restrict__ tot) {
+  terms_final<3>(prob_part, nparts, tot);
+}
+
+// ---- CompObjfAndDeriv ----------------------------------------------------------------
 // deriv(row, col) += weight / A(row, col); elements outside the matrix are
 // skipped (the hosts validate before they launch).
 __global__ __launch_bounds__(256) void comp_objf_kernel(
@@ -257,24 +242,7 @@ __global__ __launch_bounds__(256) void comp_objf_kernel(
       wsum = (double)w;
     }
   }
-  block_objf_store(objf, wsum, dred, objf_part);
-}
-
-// tot[0] += the partials' objective, tot[1] += their weight: one wave, each
-// lane its partials in order, then the cross-lane sum.
-__global__ __launch_bounds__(64) void objf_final_kernel(const double *__restrict__ objf_part,
-                                                        int nparts, double *__restrict__ tot) {
-  double objf = 0.0, wsum = 0.0;
-  for (int p = threadIdx.x; p < nparts; p += 64) {
-    objf += objf_part[2 * (size_t)p];
-    wsum += objf_part[2 * (size_t)p + 1];
-  }
-  objf = wave_sum(objf);
-  wsum = wave_sum(wsum);
-  if (threadIdx.x == 0) {
-    tot[0] += objf;
-    tot[1] += wsum;
-  }
+  block_terms_store<2>({wave_sum(objf), wave_sum(wsum)}, dred, objf_part);
 }
 
 // ---- Softmax + cross-entropy backward, fused -------------------------------------------
@@ -310,16 +278,14 @@ __global__ __launch_bounds__(256) void softmax_xent_wave_kernel(
       p[j] = -p[j] * S;
     }
     for (int l = lb; l < le; l++) {
-      // the label's column is value jl of lane `owner`: jl is wave-uniform,
+      // the label's column is value t.j of lane t.lane: t.j is wave-uniform,
       // so the search over the register file is scalar compares
-      const int c = __builtin_amdgcn_readfirstlane(lab_col[l]);
-      const float lw = lab_w[l];
-      const int q = c / V;
-      const int jl = (q >> 6) * V + (c % V);
-      const float add = (lane == (q & 63)) ? lw : 0.0f;
+      const RowSlot t = row_slot<V>(__builtin_amdgcn_readfirstlane(lab_col[l]));
+      const float lw = lab_w[l];  // every lane's load: not behind the one of lab_col
+      const float add = lane == t.lane ? lw : 0.0f;
 #pragma unroll
       for (int j = 0; j < TOT; j++)
-        if (j == jl) p[j] += add;
+        if (j == t.j) p[j] += add;
     }
     for (int l = lb + lane; l < le; l += 64) {
       const int c = lab_col[l];
@@ -333,7 +299,7 @@ __global__ __launch_bounds__(256) void softmax_xent_wave_kernel(
   }
   if constexpr (STATS)
     part_colsum_store<V, TOT>(cs, red, lane, w, part + (int64_t)blockIdx.x * cols, cols);
-  block_objf_store(objf, wsum, dred, objf_part);
+  block_terms_store<2>({wave_sum(objf), wave_sum(wsum)}, dred, objf_part);
 }
 
 // The wide-row form: a block per row; partial r is the row's objective.
@@ -360,7 +326,7 @@ __global__ __launch_bounds__(256) void softmax_xent_block_kernel(
       wsum += (double)lw;
     }
   }
-  block_objf_store(objf, wsum, dred, objf_part);
+  block_terms_store<2>({wave_sum(objf), wave_sum(wsum)}, dred, objf_part);
 }
 
 // ---- objective and frame accuracy, forward only (nnet-compute-prob) ----------------------
@@ -390,28 +356,11 @@ __device__ __forceinline__ RowBest wave_best(RowBest a) {
   return a;
 }
 
-// Each wave's {objective, weight, accuracy weight} (lane 0's), added in wave
-// order into the block's partial.
-__device__ __forceinline__ void block_prob_store(double objf, double wsum, double acc,
-                                                 double (*dred)[3],
-                                                 double *__restrict__ prob_part) {
-  if ((threadIdx.x & 63) == 0) {
-    dred[threadIdx.x >> 6][0] = objf;
-    dred[threadIdx.x >> 6][1] = wsum;
-    dred[threadIdx.x >> 6][2] = acc;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    prob_part[3 * (size_t)blockIdx.x + threadIdx.x] =
-        ((dred[0][threadIdx.x] + dred[1][threadIdx.x]) + dred[2][threadIdx.x]) +
-        dred[3][threadIdx.x];
-}
-
 // One wave per row, four rows to a block, the row in registers.  SOFTMAX: the
-// row holds logits and P is formed as softmax_prop_wave_kernel forms it, to
-// the bit, and never stored; else the row holds P.  Then the row's best
-// column, and per label w log P, w, and w where the label is the best column.
-// A row without labels is not read.  Every lane carries the same totals.
+// row holds logits and P is formed by softmax_row and never stored; else the
+// row holds P.  Then the row's best column, and per label w log P, w, and w
+// where the label is the best column.  A row without labels is not read.
+// Every lane carries the same totals.
 template <int V, int TOT, bool SOFTMAX>
 __global__ __launch_bounds__(256) void objf_accuracy_wave_kernel(
     const float *__restrict__ X, int64_t xs, int rows, int cols,
@@ -425,25 +374,7 @@ __global__ __launch_bounds__(256) void objf_accuracy_wave_kernel(
   if (lb < le) {
     float v[TOT];
     load_row<V, TOT>(X + (int64_t)r * xs, cols, lane, -INFINITY, v);
-    if constexpr (SOFTMAX) {
-      float m = v[0];
-#pragma unroll
-      for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
-      m = wave_max(m);
-      float s = 0.0f;
-#pragma unroll
-      for (int j = 0; j < TOT; j++) {
-        v[j] = expf(v[j] - m);
-        s += v[j];
-      }
-      s = wave_sum(s);
-#pragma unroll
-      for (int j = 0; j < TOT; j++) {
-        float y = v[j] / s;
-        if (y < kSoftmaxFloor) y = kSoftmaxFloor;  // NaN stays
-        v[j] = y;
-      }
-    }
+    if constexpr (SOFTMAX) softmax_row<TOT>(v);
     RowBest best{kRowMaxStart, kNoBest};
 #pragma unroll
     for (int j = 0; j < TOT; j++) {  // a lane's columns ascend with j
@@ -452,23 +383,15 @@ __global__ __launch_bounds__(256) void objf_accuracy_wave_kernel(
     }
     best = wave_best(best);
     for (int l = lb; l < le; l++) {
-      // the label's column is value jl of lane `owner`; jl is wave-uniform
       const int c = __builtin_amdgcn_readfirstlane(lab_col[l]);
       if (c < 0 || c >= cols) continue;  // (the hosts validate before they launch)
       const float lw = lab_w[l];
-      const int q = c / V;
-      const int jl = (q >> 6) * V + (c % V);
-      float pv = 0.0f;
-#pragma unroll
-      for (int j = 0; j < TOT; j++)
-        if (j == jl) pv = v[j];
-      pv = __shfl(pv, q & 63);
-      objf += (double)lw * log((double)pv);
+      objf += (double)lw * log((double)row_value_at<V, TOT>(v, c));
       wsum += (double)lw;
       if (c == best.c) acc += (double)lw;
     }
   }
-  block_prob_store(objf, wsum, acc, dred, prob_part);
+  block_terms_store<3>({objf, wsum, acc}, dred, prob_part);
 }
 
 // The four waves' best columns of a block, merged in wave order.
@@ -495,23 +418,11 @@ __global__ __launch_bounds__(256) void objf_accuracy_block_kernel(
   const int lb = row_start[r], le = row_start[r + 1];
   double objf = 0.0, wsum = 0.0, acc = 0.0;
   if (lb < le) {  // block-uniform
-    float m = 0.0f, s = 1.0f;
-    if constexpr (SOFTMAX) {
-      m = -INFINITY;
-      for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
-      m = block_max(m, red);
-      s = 0.0f;
-      for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
-      s = block_sum(s, red);
-    }
+    RowMaxSum ms{0.0f, 1.0f};
+    if constexpr (SOFTMAX) ms = softmax_max_sum(x, cols, red);
     auto prob = [&](int c) {
-      if constexpr (SOFTMAX) {
-        float y = expf(x[c] - m) / s;
-        if (y < kSoftmaxFloor) y = kSoftmaxFloor;
-        return y;
-      } else {
-        return x[c];
-      }
+      if constexpr (SOFTMAX) return softmax_value(x[c], ms);
+      else return x[c];
     };
     RowBest best{kRowMaxStart, kNoBest};
     for (int c = threadIdx.x; c < cols; c += 256) {
@@ -531,24 +442,7 @@ __global__ __launch_bounds__(256) void objf_accuracy_block_kernel(
     wsum = wave_sum(wsum);
     acc = wave_sum(acc);
   }
-  block_prob_store(objf, wsum, acc, dred, prob_part);
-}
-
-// tot[0..2] += the partials' objective, weight and accuracy weight: one wave,
-// each lane its partials in order, then the cross-lane sum.
-__global__ __launch_bounds__(64) void prob_final_kernel(const double *__restrict__ prob_part,
-                                                        int nparts, double *__restrict__ tot) {
-  double t[3] = {0.0, 0.0, 0.0};
-  for (int p = threadIdx.x; p < nparts; p += 64) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) t[k] += prob_part[3 * (size_t)p + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) t[k] = wave_sum(t[k]);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) tot[k] += t[k];
-  }
+  block_terms_store<3>({objf, wsum, acc}, dred, prob_part);
 }
 
 // ---- log-likelihoods (nnet-am-compute --apply-log --divide-by-priors) ----------------------
@@ -572,8 +466,9 @@ __global__ __launch_bounds__(256) void loglikes_kernel(const float *__restrict__
     out[(int64_t)r * os + c] = loglike(P[(int64_t)r * ps + c], off);
 }
 
-// From the logits of a last SoftmaxComponent: P formed in registers as
-// softmax_prop_wave_kernel forms it, to the bit, and never stored.
+// From the logits of a last SoftmaxComponent: P formed in registers by
+// softmax_row's two steps and never stored.  (loglike floors the floored P
+// again, which changes nothing.)
 template <int V, int TOT>
 __global__ __launch_bounds__(256) void softmax_loglikes_wave_kernel(
     const float *__restrict__ in, int64_t is, float *__restrict__ out, int64_t os, int rows,
@@ -583,21 +478,11 @@ __global__ __launch_bounds__(256) void softmax_loglikes_wave_kernel(
   if (r >= rows) return;
   float v[TOT];
   load_row<V, TOT>(in + (int64_t)r * is, cols, lane, -INFINITY, v);
-  float m = v[0];
-#pragma unroll
-  for (int j = 1; j < TOT; j++) m = fmaxf(m, v[j]);
-  m = wave_max(m);
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < TOT; j++) {
-    v[j] = expf(v[j] - m);
-    s += v[j];
-  }
-  s = wave_sum(s);
+  const float s = softmax_row_exp<TOT>(v);
 #pragma unroll
   for (int j = 0; j < TOT; j++) {
     const int c = row_col<V, TOT>(lane, j);
-    if (c < cols) v[j] = loglike(v[j] / s, offset ? offset[c] : 0.0);
+    if (c < cols) v[j] = loglike(softmax_quotient(v[j], s), offset ? offset[c] : 0.0);
   }
   store_row<V, TOT>(out + (int64_t)r * os, cols, lane, v);
 }
@@ -610,14 +495,9 @@ __global__ __launch_bounds__(256) void softmax_loglikes_block_kernel(
   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
     const float *x = in + (int64_t)r * is;
     float *y = out + (int64_t)r * os;
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < cols; c += 256) m = fmaxf(m, x[c]);
-    m = block_max(m, red);
-    float s = 0.0f;
-    for (int c = threadIdx.x; c < cols; c += 256) s += expf(x[c] - m);
-    s = block_sum(s, red);
+    const RowMaxSum ms = softmax_max_sum(x, cols, red);
     for (int c = threadIdx.x; c < cols; c += 256)
-      y[c] = loglike(expf(x[c] - m) / s, offset ? offset[c] : 0.0);
+      y[c] = loglike(softmax_value(x[c], ms), offset ? offset[c] : 0.0);
   }
 }
 
@@ -733,20 +613,6 @@ __global__ __launch_bounds__(256) void dropout_backprop4_kernel(
 // Values a lane holds (the kernels are built for 4, 16 and 64).
 int lane_values(int cols) { return cols <= 256 ? 4 : cols <= 1024 ? 16 : 64; }
 
-template <typename F>
-void dispatch_row_kernel(int v, int tot, F f) {
-  auto with_v = [&](auto vc) {
-    if (tot == 4) f(vc, std::integral_constant<int, 4>{});
-    else if (tot == 16) f(vc, std::integral_constant<int, 16>{});
-    else f(vc, std::integral_constant<int, 64>{});
-  };
-  if (v == 4) with_v(std::integral_constant<int, 4>{});
-  else if (v == 2) with_v(std::integral_constant<int, 2>{});
-  else with_v(std::integral_constant<int, 1>{});
-}
-
-bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols == b.cols; }
-
 int wave_parts(int rows) { return (rows + kSmRowsPerPart - 1) / kSmRowsPerPart; }
 
 }  // namespace
@@ -755,8 +621,8 @@ extern "C" {
 
 int kn_softmax_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                     kcnn_stream_t st) {
-  if (!same_shape(in_dim, out_dim) || in_dim.stride < in_dim.cols ||
-      out_dim.stride < out_dim.cols)
+  if (!same_shape(in_dim, out_dim) || !contiguous_enough(in_dim) ||
+      !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = in_dim.rows, cols = in_dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -767,7 +633,7 @@ int kn_softmax_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out
     return kcnn::launch_status();
   }
   const Operand ops[] = {{in, in_dim.stride}, {out, out_dim.stride}};
-  dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+  dispatch_kernel<4, 16, 64>(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
     hipLaunchKernelGGL((softmax_prop_wave_kernel<decltype(V)::value, decltype(TOT)::value>),
                        dim3((rows + 3) / 4), dim3(256), 0, s, in, (int64_t)in_dim.stride, out,
                        (int64_t)out_dim.stride, rows, cols);
@@ -807,7 +673,7 @@ int kn_softmax_backprop(const float *out_value, MatrixDim ov_dim, const float *o
                         MatrixDim od_dim, float *in_deriv, MatrixDim id_dim, double *value_sum,
                         void *ws, kcnn_stream_t st) {
   if (!same_shape(ov_dim, od_dim) || !same_shape(id_dim, od_dim) ||
-      ov_dim.stride < ov_dim.cols || od_dim.stride < od_dim.cols || id_dim.stride < id_dim.cols)
+      !contiguous_enough(ov_dim) || !contiguous_enough(od_dim) || !contiguous_enough(id_dim))
     return (int)hipErrorInvalidValue;
   const int rows = od_dim.rows, cols = od_dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -823,18 +689,14 @@ int kn_softmax_backprop(const float *out_value, MatrixDim ov_dim, const float *o
   } else {
     const Operand ops[] = {
         {out_value, ov_dim.stride}, {out_deriv, od_dim.stride}, {in_deriv, id_dim.stride}};
-    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
-      constexpr int v = decltype(V)::value, tot = decltype(TOT)::value;
-      if (stats)
-        hipLaunchKernelGGL((softmax_backprop_wave_kernel<v, tot, true>), dim3(wave_parts(rows)),
-                           dim3(256), 0, s, out_value, (int64_t)ov_dim.stride, out_deriv,
-                           (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols,
-                           part);
-      else
-        hipLaunchKernelGGL((softmax_backprop_wave_kernel<v, tot, false>), dim3(wave_parts(rows)),
-                           dim3(256), 0, s, out_value, (int64_t)ov_dim.stride, out_deriv,
-                           (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols,
-                           part);
+    dispatch_kernel<4, 16, 64>(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+      kcnn::with_bool(stats, [&](auto STATS) {
+        hipLaunchKernelGGL((softmax_backprop_wave_kernel<decltype(V)::value, decltype(TOT)::value,
+                                                         decltype(STATS)::value>),
+                           dim3(wave_parts(rows)), dim3(256), 0, s, out_value,
+                           (int64_t)ov_dim.stride, out_deriv, (int64_t)od_dim.stride, in_deriv,
+                           (int64_t)id_dim.stride, rows, cols, part);
+      });
     });
   }
   const int rc = kcnn::launch_status();
@@ -875,8 +737,8 @@ int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in
                              MatrixDim id_dim, const int *row_start, const int *lab_col,
                              const float *lab_w, double *value_sum, void *stats_ws, double *tot,
                              void *objf_ws, kcnn_stream_t st) {
-  if (!same_shape(ov_dim, id_dim) || ov_dim.stride < ov_dim.cols ||
-      id_dim.stride < id_dim.cols || tot == nullptr || objf_ws == nullptr ||
+  if (!same_shape(ov_dim, id_dim) || !contiguous_enough(ov_dim) ||
+      !contiguous_enough(id_dim) || tot == nullptr || objf_ws == nullptr ||
       row_start == nullptr)
     return (int)hipErrorInvalidValue;
   const int rows = ov_dim.rows, cols = ov_dim.cols;
@@ -894,16 +756,14 @@ int kn_softmax_xent_backprop(const float *out_value, MatrixDim ov_dim, float *in
                        row_start, lab_col, lab_w, objf_part);
   } else {
     const Operand ops[] = {{out_value, ov_dim.stride}, {in_deriv, id_dim.stride}};
-    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
-      constexpr int v = decltype(V)::value, tot_v = decltype(TOT)::value;
-      if (stats)
-        hipLaunchKernelGGL((softmax_xent_wave_kernel<v, tot_v, true>), dim3(nb), dim3(256), 0, s,
-                           out_value, (int64_t)ov_dim.stride, in_deriv, (int64_t)id_dim.stride,
-                           rows, cols, row_start, lab_col, lab_w, part, objf_part);
-      else
-        hipLaunchKernelGGL((softmax_xent_wave_kernel<v, tot_v, false>), dim3(nb), dim3(256), 0, s,
-                           out_value, (int64_t)ov_dim.stride, in_deriv, (int64_t)id_dim.stride,
-                           rows, cols, row_start, lab_col, lab_w, part, objf_part);
+    dispatch_kernel<4, 16, 64>(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+      kcnn::with_bool(stats, [&](auto STATS) {
+        hipLaunchKernelGGL((softmax_xent_wave_kernel<decltype(V)::value, decltype(TOT)::value,
+                                                     decltype(STATS)::value>),
+                           dim3(nb), dim3(256), 0, s, out_value, (int64_t)ov_dim.stride, in_deriv,
+                           (int64_t)id_dim.stride, rows, cols, row_start, lab_col, lab_w, part,
+                           objf_part);
+      });
     });
   }
   int rc = kcnn::launch_status();
@@ -920,7 +780,7 @@ namespace {
 template <bool SOFTMAX>
 int launch_objf_accuracy(const float *x, MatrixDim dim, const int *row_start, const int *lab_col,
                          const float *lab_w, double *tot, void *ws, kcnn_stream_t st) {
-  if (dim.stride < dim.cols || tot == nullptr || ws == nullptr || row_start == nullptr)
+  if (!contiguous_enough(dim) || tot == nullptr || ws == nullptr || row_start == nullptr)
     return (int)hipErrorInvalidValue;
   const int rows = dim.rows, cols = dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -932,7 +792,7 @@ int launch_objf_accuracy(const float *x, MatrixDim dim, const int *row_start, co
                        (int64_t)dim.stride, rows, cols, row_start, lab_col, lab_w, prob_part);
   } else {
     const Operand ops[] = {{x, dim.stride}};
-    dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+    dispatch_kernel<4, 16, 64>(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
       hipLaunchKernelGGL(
           (objf_accuracy_wave_kernel<decltype(V)::value, decltype(TOT)::value, SOFTMAX>),
           dim3(nb), dim3(256), 0, s, x, (int64_t)dim.stride, rows, cols, row_start, lab_col,
@@ -970,20 +830,19 @@ int kn_softmax_objf_accuracy(const float *logits, MatrixDim l_dim, const int *ro
 
 int kn_loglikes(const float *probs, MatrixDim p_dim, float *out, MatrixDim out_dim,
                 const double *offset, kcnn_stream_t st) {
-  if (!same_shape(p_dim, out_dim) || p_dim.stride < p_dim.cols || out_dim.stride < out_dim.cols)
+  if (!same_shape(p_dim, out_dim) || !contiguous_enough(p_dim) || !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = p_dim.rows, cols = p_dim.cols;
   if (rows == 0 || cols == 0) return 0;
-  const unsigned cb = (unsigned)((cols + 255) / 256);
-  const unsigned rb = std::min(std::min((unsigned)rows, 8192u / cb + 1u), 65535u);
-  hipLaunchKernelGGL(loglikes_kernel, dim3(cb, rb), dim3(256), 0, kcnn::as_stream(st), probs,
-                     (int64_t)p_dim.stride, out, (int64_t)out_dim.stride, rows, cols, offset);
+  hipLaunchKernelGGL(loglikes_kernel, kcnn::elementwise_grid(rows, cols, 256), dim3(256), 0,
+                     kcnn::as_stream(st), probs, (int64_t)p_dim.stride, out,
+                     (int64_t)out_dim.stride, rows, cols, offset);
   return kcnn::launch_status();
 }
 
 int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, MatrixDim out_dim,
                         const double *offset, kcnn_stream_t st) {
-  if (!same_shape(l_dim, out_dim) || l_dim.stride < l_dim.cols || out_dim.stride < out_dim.cols)
+  if (!same_shape(l_dim, out_dim) || !contiguous_enough(l_dim) || !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = l_dim.rows, cols = l_dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -995,7 +854,7 @@ int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, Matrix
     return kcnn::launch_status();
   }
   const Operand ops[] = {{logits, l_dim.stride}, {out, out_dim.stride}};
-  dispatch_row_kernel(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
+  dispatch_kernel<4, 16, 64>(lane_width(ops), lane_values(cols), [&](auto V, auto TOT) {
     hipLaunchKernelGGL((softmax_loglikes_wave_kernel<decltype(V)::value, decltype(TOT)::value>),
                        dim3((rows + 3) / 4), dim3(256), 0, s, logits, (int64_t)l_dim.stride, out,
                        (int64_t)out_dim.stride, rows, cols, offset);
@@ -1006,8 +865,8 @@ int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, Matrix
 int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                     float dropout_proportion, float high_minus_low, float low, uint64_t seed,
                     uint64_t call, kcnn_stream_t st) {
-  if (!same_shape(in_dim, out_dim) || in_dim.stride < in_dim.cols ||
-      out_dim.stride < out_dim.cols)
+  if (!same_shape(in_dim, out_dim) || !contiguous_enough(in_dim) ||
+      !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = in_dim.rows, cols = in_dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -1050,18 +909,14 @@ int kn_dropout_backprop(const float *in_value, MatrixDim iv_dim, const float *ou
                     (uintptr_t)in_value % 16 == 0 && (uintptr_t)out_value % 16 == 0 &&
                     (uintptr_t)out_deriv % 16 == 0 && (uintptr_t)in_deriv % 16 == 0;
   const int cpb = vec4 ? 1024 : 256;
-  const unsigned cb = (unsigned)((cols + cpb - 1) / cpb);
-  unsigned rb = (unsigned)rows;
-  const unsigned cap = 8192u / cb + 1u;
-  if (rb > cap) rb = cap;
-  if (rb > 65535u) rb = 65535u;
+  const dim3 grid = kcnn::elementwise_grid(rows, cols, cpb);
   hipStream_t s = kcnn::as_stream(st);
   if (vec4)
-    hipLaunchKernelGGL(dropout_backprop4_kernel, dim3(cb, rb), dim3(256), 0, s, in_value,
+    hipLaunchKernelGGL(dropout_backprop4_kernel, grid, dim3(256), 0, s, in_value,
                        (int64_t)iv_dim.stride, out_value, (int64_t)ov_dim.stride, out_deriv,
                        (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols);
   else
-    hipLaunchKernelGGL(dropout_backprop_kernel, dim3(cb, rb), dim3(256), 0, s, in_value,
+    hipLaunchKernelGGL(dropout_backprop_kernel, grid, dim3(256), 0, s, in_value,
                        (int64_t)iv_dim.stride, out_value, (int64_t)ov_dim.stride, out_deriv,
                        (int64_t)od_dim.stride, in_deriv, (int64_t)id_dim.stride, rows, cols);
   return kcnn::launch_status();

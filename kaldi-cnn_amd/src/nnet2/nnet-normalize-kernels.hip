@@ -19,18 +19,17 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include <type_traits>
-
 #include "nnet-kernels.h"
 #include "row-regs.h"
 #include "../cnslmat/hip-util.h"
 
+using kcnn::contiguous_enough;
+using kcnn::same_shape;
 using namespace kcnn::rowregs;
 
 namespace {
 
 constexpr int kBlockRowMaxCols = 16384;  // 256 threads x 64 values
-constexpr int kBlock = 256;
 
 // kNormFloor = 2^-66 (nnet-component.cc:576).
 constexpr float kNormFloor = 0x1.0p-66f;
@@ -67,15 +66,6 @@ __device__ __forceinline__ float sum_products(const float (&x)[TOT], const float
 #pragma unroll
   for (int j = 0; j < TOT; j++) a[j & 3] = fmaf(x[j], y[j], a[j & 3]);
   return (a[0] + a[1]) + (a[2] + a[3]);
-}
-
-// The four waves' sums of a block, combined in wave order.
-__device__ __forceinline__ float block_sum(float v, float *red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // ---- Propagate --------------------------------------------------------------------
@@ -198,8 +188,6 @@ __global__ __launch_bounds__(kBlock) void normalize_backprop_reread_kernel(
   }
 }
 
-bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols == b.cols; }
-
 // Values a thread holds: the wave kernels are built for 4, 16, 32 and 64 (a
 // lane of 64), the block kernels for 32 and 64 (a thread of 256).  32 for the
 // wave form, which Softmax does without: a 1152-column row in 64 registers a
@@ -207,25 +195,14 @@ bool same_shape(MatrixDim a, MatrixDim b) { return a.rows == b.rows && a.cols ==
 int wave_values(int cols) { return cols <= 256 ? 4 : cols <= 1024 ? 16 : cols <= 2048 ? 32 : 64; }
 int block_values(int cols) { return cols <= kBlock * 32 ? 32 : 64; }
 
-// f(V, TOT) as integral constants, for the one of TOTS that tot is.
-template <int... TOTS, typename F>
-void dispatch_kernel(int v, int tot, F f) {
-  auto with_v = [&](auto vc) {
-    (void)((tot == TOTS && (f(vc, std::integral_constant<int, TOTS>{}), true)) || ...);
-  };
-  if (v == 4) with_v(std::integral_constant<int, 4>{});
-  else if (v == 2) with_v(std::integral_constant<int, 2>{});
-  else with_v(std::integral_constant<int, 1>{});
-}
-
 }  // namespace
 
 extern "C" {
 
 int kn_normalize_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                       kcnn_stream_t st) {
-  if (!same_shape(in_dim, out_dim) || in_dim.stride < in_dim.cols ||
-      out_dim.stride < out_dim.cols)
+  if (!same_shape(in_dim, out_dim) || !contiguous_enough(in_dim) ||
+      !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = in_dim.rows, cols = in_dim.cols;
   if (rows == 0 || cols == 0) return 0;
@@ -256,7 +233,7 @@ int kn_normalize_backprop(const float *in_value, MatrixDim iv_dim, const float *
                           MatrixDim od_dim, float *in_deriv, MatrixDim id_dim,
                           kcnn_stream_t st) {
   if (!same_shape(iv_dim, od_dim) || !same_shape(id_dim, od_dim) ||
-      iv_dim.stride < iv_dim.cols || od_dim.stride < od_dim.cols || id_dim.stride < id_dim.cols)
+      !contiguous_enough(iv_dim) || !contiguous_enough(od_dim) || !contiguous_enough(id_dim))
     return (int)hipErrorInvalidValue;
   const int rows = od_dim.rows, cols = od_dim.cols;
   if (rows == 0 || cols == 0) return 0;
