@@ -85,9 +85,24 @@ int kcnn_set_fusion(int mode);
  *      touching a group with elements far under its max are checked and
  *      recomputed in fp32 where needed, so every element meets the 1e-5 * S
  *      bound at any fp32 range; IEEE Inf / NaN rows and columns; shapes past
- *      its 32-bit addressing run mode 1.
- * Env KCNN_GEMM (0/1/2) sets the initial mode. */
+ *      its 32-bit addressing run mode 1.  The tile of C per workgroup,
+ *      256 x 128 or 256 x 256, is chosen per call by a cost model of the
+ *      call's shape, transposes and alignment alone (same bits either way
+ *      where K is not split);
+ *   3: mode 2 with the 256 x 256 tile for every call that can take it (no
+ *      row-contiguous operand with an unaligned pitch);
+ *   4: mode 2 with the 256 x 128 tile for every call.
+ * Env KCNN_GEMM (0 to 4) sets the initial mode. */
 int kcnn_set_gemm_mode(int mode);
+/* The f16x3 GEMM's launches since the last reset: out[0] on the 256 x 128
+ * tile, out[1] on the 256 x 256 tile; reset != 0 zeroes them (a test and
+ * bench diagnostic, no reference counterpart). */
+int kcnn_gemm_tile_counts(unsigned long long *out, int reset);
+/* The plan the f16x3 GEMM would give a call under the current "gemm"
+ * selector, computed without a GPU: out[0] the tile's columns (128 or 256),
+ * out[1] the split-K count, out[2] the whole tiles in front of the split
+ * ones.  lda / ldb are the pitches of A and B (16-B aligned bases assumed). */
+int kcnn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int lda, int ldb, int *out);
 /* Kernel-family selectors (kaldi-lite/kcnn-knobs.h): each picks
  * one of the implementations of the same fp32 math: the split-operand
  * kernels on the f16 / bf16 matrix cores (f16x3: two f16 parts under a
@@ -100,7 +115,9 @@ int kcnn_set_gemm_mode(int mode);
  *              all) / 1 (bf16x6) / 0
  *   "wgrad_x6" long-kernel weight gradient      2 (default, wide bf16x6) / 3
  *              (wide f16x3) / 1 (128-wide bf16x6) / 0
- *   "gemm"     AddMatMat (= kcnn_set_gemm_mode) 2 (default, f16x3) / 1 / 0
+ *   "gemm"     AddMatMat (= kcnn_set_gemm_mode) 2 (default, f16x3, tile by
+ *              the cost model) / 3 (f16x3, 256 x 256 tile) / 4 (f16x3,
+ *              256 x 128 tile) / 1 / 0
  * The environment variables KCNN_FWD_X6, KCNN_BWD_X6, KCNN_IGEMM_X6,
  * KCNN_WGRAD_X6 and KCNN_GEMM set the initial values.  Returns nonzero for
  * an unknown name or value. */

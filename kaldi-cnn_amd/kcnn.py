@@ -171,14 +171,39 @@ def profile_string() -> str:
 
 def set_gemm_mode(mode: int):
     """AddMatMat's fp32 product: 0 = rocBLAS sgemm, 1 = bf16x6 split kernel,
-    2 = f16x3 split kernel (default)."""
+    2 = f16x3 split kernel, tile by its cost model (default), 3 = f16x3 on the
+    256 x 256 tile wherever a call can take it, 4 = f16x3 on the 256 x 128
+    tile."""
     check(lib().kcnn_set_gemm_mode(int(mode)))
+
+
+def gemm_tile_counts(reset=False):
+    """(f16x3 GEMM launches on the 256 x 128 tile, on the 256 x 256 tile)
+    since the last reset (kcnn_gemm_tile_counts)."""
+    out = (ctypes.c_ulonglong * 2)()
+    check(lib().kcnn_gemm_tile_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def gemm_plan(trans_a, trans_b, m, n, k, lda=None, ldb=None):
+    """(tile columns, ksplit, nwhole) the f16x3 GEMM would give the call under
+    the current "gemm" selector (kcnn_gemm_plan; no GPU needed).  lda / ldb
+    default to the operands' dense pitches."""
+    if lda is None:
+        lda = m if trans_a else k
+    if ldb is None:
+        ldb = k if trans_b else n
+    out = (ctypes.c_int * 3)()
+    check(lib().kcnn_gemm_plan(int(bool(trans_a)), int(bool(trans_b)), int(m), int(n), int(k),
+                               int(lda), int(ldb), out))
+    return tuple(int(v) for v in out)
 
 
 def set_kernel_family(name: str, value: int):
     """Kernel-family selector (kcnn.h): "fwd_x6" (2 f16x3 / 1 bf16x6 / 0),
     "bwd_x6", "igemm_x6", "wgrad_x6" (2 wide / 1 / 0) or "gemm" (2 f16x3 /
-    1 bf16x6 / 0 rocBLAS); 0 = the fp32-MFMA kernels."""
+    3 f16x3 wide tile / 4 f16x3 narrow tile / 1 bf16x6 / 0 rocBLAS); 0 = the
+    fp32-MFMA kernels."""
     check(lib().kcnn_set_kernel_family(name.encode(), int(value)))
 
 

@@ -181,8 +181,19 @@ int kcnn_set_fusion(int on) {
   return 0;
 }
 int kcnn_set_gemm_mode(int mode) {
-  if (mode < 0 || mode > 2) return fail("kcnn_set_gemm_mode: mode is 0, 1 or 2");
+  if (mode < 0 || mode > 4) return fail("kcnn_set_gemm_mode: mode is 0 to 4");
   CuDevice::Instantiate().SetGemmMode(mode);
+  return 0;
+}
+int kcnn_gemm_tile_counts(unsigned long long *out, int reset) {
+  if (!out) return fail("kcnn_gemm_tile_counts: out is NULL");
+  kl_gemm_f16x3_tile_counts(out, reset);
+  return 0;
+}
+int kcnn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int lda, int ldb, int *out) {
+  if (!out) return fail("kcnn_gemm_plan: out is NULL");
+  if (m <= 0 || n <= 0 || k <= 0) return fail("kcnn_gemm_plan: dimensions must be positive");
+  kl_gemm_f16x3_plan(trans_a, trans_b, m, n, k, lda, ldb, out);
   return 0;
 }
 int kcnn_set_kernel_family(const char *name, int value) {

@@ -80,7 +80,8 @@ class CuDevice {
   void ResetProfile() { profile_.clear(); }
 
   // AddMatMat's fp32 product: 0 = rocBLAS sgemm, 1 = bf16x6 split kernel,
-  // 2 = f16x3 split kernel (the "gemm" kernel family, kcnn-knobs.h)
+  // 2 = f16x3 split kernel with its tile chosen per call, 3 / 4 = f16x3 on
+  // the 256 x 256 / 256 x 128 tile (the "gemm" kernel family, kcnn-knobs.h)
   void SetGemmMode(int m) { kcnn::set_family(kcnn::kFamGemm, m); }
   int GemmMode() const { return kcnn::family(kcnn::kFamGemm); }
 

@@ -46,7 +46,9 @@
 // tile of C per workgroup (8 waves of 2 x 2 accumulators of 32 x 32), K steps
 // of 32, operands loaded as fp32 by branch-free buffer loads two steps ahead,
 // split in registers into two f16 planes of swizzled [row][k] LDS images
-// (double-buffered, 2 x 48 KB), one barrier per step.  Thin outputs split K
+// (double-buffered, 2 x 48 KB), one barrier per step; or, where the call's
+// plan says so (choose_plan), a 256 x 256 tile (8 waves of 4 x 2 accumulators,
+// 2 x 64 KB; gemm_f16x3_fast_kernel with BN_WIDE).  Thin outputs split K
 // over workgroups into partial slabs, which gemm_f16x3_reduce_kernel sums in
 // a fixed order.
 #include <atomic>
@@ -63,6 +65,7 @@
 #include "cnslmat/pool-stats-dev.h"
 #include "cnslmat/pool-stats.h"
 #include "kaldi-lite/cu-kernels-lite.h"
+#include "kaldi-lite/kcnn-knobs.h"
 
 namespace {
 
@@ -81,12 +84,25 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int BM = 256, BN = 128, BK = 32, NT = 512;
+constexpr int BM = 256, BK = 32, NT = 512;
 constexpr int ROWB = BK * 2;                  // bytes per LDS row of one plane
 constexpr int A_PLANE = BM * ROWB;            // 16 KB
-constexpr int B_PLANE = BN * ROWB;            // 8 KB
-constexpr int BUF = 2 * (A_PLANE + B_PLANE);  // 48 KB
-constexpr int LDS_BYTES = 2 * BUF + (BM + BN) * 8;  // + sexp, sw
+// The tile of C per workgroup is BM x BN: the narrow tile (BN 128, 8 waves
+// of 64 x 64, 2 x 2 accumulators each) or the wide one (BN 256, 8 waves of
+// 128 x 64, 4 x 2 accumulators: per MFMA two thirds of the narrow tile's
+// operand loads, split and LDS writes, three quarters of its fragment reads,
+// half its barriers and tiles).  Both hold the same 32 x 32 accumulator
+// blocks of C, each summed in the same order: the same bits.
+constexpr int BN_NARROW = 128, BN_WIDE = 256;
+template <int BN>
+struct Tile {
+  static constexpr int WN = BN / 64;             // waves along the columns
+  static constexpr int WR = BM / (8 / WN);       // rows per wave
+  static constexpr int MI = WR / 32;             // accumulator rows per wave
+  static constexpr int B_PLANE = BN * ROWB;      // 8 / 16 KB
+  static constexpr int BUF = 2 * (A_PLANE + B_PLANE);   // 48 / 64 KB
+  static constexpr int LDS_BYTES = 2 * BUF + (BM + BN) * 8;  // + sexp, sw
+};
 
 struct GemmF16Args {
   const float *A, *B;
@@ -104,6 +120,7 @@ struct GemmF16Args {
   int bvec;                      // bmax, bcnt 16-B aligned and N % 4 == 0 (the reduce's loads)
   MomentumEpi mom;               // mom.W: C is a weight gradient applied in the store (emit)
   int kps, ksplit, tiles_m, tiles_n;
+  int bn;                        // the tile's columns (BN_NARROW or BN_WIDE)
   int nwhole;                    // ksplit > 1: the first nwhole tiles (a multiple of 256) whole
   int fix_local;                 // ksplit > 1: no fix-up launch; the reduce recomputes every rejection
   uint32_t *fix_report;          // nullable (host memory): set to 1 when a group would be deferred
@@ -152,7 +169,7 @@ __device__ __forceinline__ bool block_tile(const GemmF16Args &p, int &split, int
 }
 // C element (r, c) is a split tile's (its value from the partial slabs)
 __device__ __forceinline__ bool in_split_tile(const GemmF16Args &p, int r, int c) {
-  return p.nwhole == 0 || tile_index(p, r / BM, c / BN) >= p.nwhole;
+  return p.nwhole == 0 || tile_index(p, r / BM, c / p.bn) >= p.nwhole;
 }
 
 __device__ __forceinline__ int swz(int r, int c) {
@@ -359,6 +376,34 @@ struct Loader {
       }
     }
   }
+  // The loads of load() in NPART parts, each the values of PPP consecutive
+  // pieces: the wide tile's loop holds one loader set per operand and issues
+  // part q of the next tile as soon as piece() has consumed part q of this one
+  static constexpr int NPART = MODE == LT ? KPT : UPT;
+  static constexpr int PPP = NPIECE / NPART;
+  __device__ __forceinline__ void load_part(__amdgpu_buffer_rsrc_t rs, int ld, int vrows, int kk,
+                                            int tid, int q) {
+    static_assert(MODE != LR, "the wide tile has no LR loader");
+    constexpr unsigned OOB = 0x80000000u;
+    if constexpr (MODE == LK) {
+      const int unit = tid + q * NT;
+      const int r = unit >> 2, k = kk + (unit & 3) * 8;
+      const unsigned off = r < vrows ? (unsigned)(r * ld + k) * 4u : OOB;
+      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+      const auto b = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16u, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[q][j] = __uint_as_float(a[j]);
+        v[q][4 + j] = __uint_as_float(b[j]);
+      }
+    } else {
+      const int rq = tid % (R / 4), k = kk + (tid / (R / 4)) * KPT;
+      const unsigned off = 4 * rq < vrows ? (unsigned)((k + q) * ld + 4 * rq) * 4u : OOB;
+      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[0][4 * q + i] = __uint_as_float(a[i]);
+    }
+  }
   // fragment reads per MFMA fragment (LT: two transposed 8-B reads)
   static constexpr int NRD = MODE == LT ? 2 : 1;
 
@@ -387,6 +432,7 @@ struct Loader {
 // threshold sum is then -inf, i.e. no check).  Returns bit 0: one of them is
 // an Inf / NaN row or column; bit 1: one of them is spread (both for the
 // whole block).
+template <int BN>
 __device__ __forceinline__ int tile_scales(const GemmF16Args &p, int *sexp, float *sw, int row0,
                                            int col0, int tid) {
   int skip = 0, spr = 0;
@@ -517,12 +563,14 @@ __device__ __forceinline__ void fix_rejected(const GemmF16Args &p, bool a_kc, bo
 //  - Elements of an Inf / NaN row or column are skipped above; split 0's
 //    workgroup computes them here as fp32 dot products in increasing k
 //    (IEEE Inf / NaN, the reference sgemm's pattern).
-template <bool A_KC, bool B_KC>
+template <bool A_KC, bool B_KC, int BN>
 __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *sexp,
-                                              const float *sw, const f32x16 (&acc)[2][2],
-                                              int split, bool whole, int row0, int col0,
-                                              int flags, int tid, char *lds) {
-  const int lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+                                              const float *sw,
+                                              const f32x16 (&acc)[Tile<BN>::MI][2], int split,
+                                              bool whole, int row0, int col0, int flags, int tid,
+                                              char *lds) {
+  constexpr int MI = Tile<BN>::MI, WR = Tile<BN>::WR, WN = Tile<BN>::WN;
+  const int lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN;
   const int half2 = lane >> 5;
   const bool partial = p.ksplit > 1 && !whole;
   const bool skip = flags & 1;
@@ -534,21 +582,26 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
   const int np4 = (p.N + 3) & ~3;  // partial slab pitch (16-B rows)
   float *slab = partial ? p.part + (int64_t)split * p.M * np4 : p.C;
   const int ldo = partial ? np4 : p.ldc;
-  uint64_t rej = 0;  // bit (2 i + j) * 16 + g: that element is rejected
+  // bit (2 (i & 1) + j) * 16 + g of word i >> 1: that element is rejected
+  uint64_t rej[MI / 2];
+#pragma unroll
+  for (int h = 0; h < MI / 2; ++h) rej[h] = 0;
   auto fix = [&]() {
-    fix_rejected(p, A_KC, B_KC, rej, lane, [&](int l, int n, int &row, int &col) {
-      const int i = n >> 5, j = (n >> 4) & 1, g = n & 15;
-      row = row0 + wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
-      col = col0 + wn * 64 + j * 32 + (l & 31);
-    });
+#pragma unroll
+    for (int h = 0; h < MI / 2; ++h)
+      fix_rejected(p, A_KC, B_KC, rej[h], lane, [&](int l, int n, int &row, int &col) {
+        const int i = 2 * h + (n >> 5), j = (n >> 4) & 1, g = n & 15;
+        row = row0 + wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
+        col = col0 + wn * 64 + j * 32 + (l & 31);
+      });
   };
   // A whole tile without Inf / NaN rows or columns (block-uniform): each
-  // wave's 64 x 64 block through LDS in two 32-row halves (the main loop's
+  // wave's WR x 64 block through LDS in 32-row passes (the main loop's
   // plane buffers, free after a barrier), then 16-B stores of whole rows:
   // a quarter of the store instructions of the per-register stores below
   // (c2's data gradient: 400 -> 388 us at K 1024).  An element the check
   // rejects is recomputed by its wave (fix_rejected) into its staging slot
-  // before the half is stored, so alpha, beta * C and the bias are applied
+  // before the pass is stored, so alpha, beta * C and the bias are applied
   // to it once, by the same 16-B store as its neighbours (a
   // second store_value after the staged store read back the new C).
   // (the momentum update's W and prev have 16-B aligned rows: host check)
@@ -559,36 +612,36 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
     constexpr int SR = 68;  // staging row pitch (floats): 16-B rows, rows 4 apart on other banks
     float *st = reinterpret_cast<float *>(lds) + wave * 32 * SR;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < MI; ++i) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int cl = wn * 64 + j * 32 + (lane & 31);
         const int ec = sexp[BM + cl];
         const float wc = check ? sw[BM + cl] : 0.0f;
         const bool bcheck =
-            check && (__ballot(wc > 0.0f || sw[wm * 64 + i * 32 + (lane & 31)] > 0.0f) != 0);
+            check && (__ballot(wc > 0.0f || sw[wm * WR + i * 32 + (lane & 31)] > 0.0f) != 0);
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
           const int rr = (g & 3) + 8 * (g >> 2) + 4 * half2;
-          const int rl = wm * 64 + i * 32 + rr;
+          const int rl = wm * WR + i * 32 + rr;
           if (bcheck) {
             const float thr = wc + sw[rl];
             if (thr != 0.0f && !(fabsf(acc[i][j][g]) >= thr))
-              rej |= (uint64_t)1 << ((2 * i + j) * 16 + g);
+              rej[i >> 1] |= (uint64_t)1 << ((2 * (i & 1) + j) * 16 + g);
           }
           st[rr * SR + j * 32 + (lane & 31)] =
               __builtin_amdgcn_ldexpf(acc[i][j][g], -(sexp[rl] + ec));
         }
       }
       if (check) {
-        // this half's rejections (bits 32 i .. 32 i + 31) into their slots
+        // this pass's rejections (bits 32 (i & 1) .. + 31 of its word) into their slots
         // (lane 0 writes after every lane's staging write: one wave, LDS in order)
-        const uint64_t mine = (rej >> (32 * i)) & 0xffffffffull;
+        const uint64_t mine = (rej[i >> 1] >> (32 * (i & 1))) & 0xffffffffull;
         fix_rejected(
             p, A_KC, B_KC, mine, lane,
             [&](int l, int n, int &row, int &col) {
               const int j = (n >> 4) & 1, g = n & 15;
-              row = row0 + wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
+              row = row0 + wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
               col = col0 + wn * 64 + j * 32 + (l & 31);
             },
             [&](int l, int n, int, int, float v) {
@@ -601,7 +654,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
       for (int k = 0; k < 8; ++k) {
         const int f = lane + 64 * k, rr = f >> 4, c4 = f & 15;
         const float4 v = *reinterpret_cast<const float4 *>(st + rr * SR + 4 * c4);
-        const int row = row0 + wm * 64 + i * 32 + rr, col = col0 + wn * 64 + 4 * c4;
+        const int row = row0 + wm * WR + i * 32 + rr, col = col0 + wn * 64 + 4 * c4;
         if (!partial && p.mom.W) {  // emit's momentum step, four elements per access
           float4 *wq = reinterpret_cast<float4 *>(p.mom.W + (int64_t)row * p.mom.ldw + col);
           float4 *pq = reinterpret_cast<float4 *>(p.mom.prev + (int64_t)row * p.mom.ldp + col);
@@ -638,7 +691,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
     return;
   }
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int cl = wn * 64 + j * 32 + (lane & 31);
@@ -649,17 +702,17 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
       // this 32 x 32 block's check: one of its columns or rows is spread
       // (wave-uniform; most blocks skip it)
       const bool bcheck =
-          check && (__ballot(wc > 0.0f || sw[wm * 64 + i * 32 + (lane & 31)] > 0.0f) != 0);
+          check && (__ballot(wc > 0.0f || sw[wm * WR + i * 32 + (lane & 31)] > 0.0f) != 0);
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int rl = wm * 64 + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * half2;
+        const int rl = wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * half2;
         const int row = row0 + rl;
         const int er = sexp[rl];
         if (row >= p.M || er == SKIP) continue;
         if (bcheck) {
           const float thr = wc + sw[rl];
           if (thr != 0.0f && !(fabsf(acc[i][j][g]) >= thr)) {
-            rej |= (uint64_t)1 << ((2 * i + j) * 16 + g);
+            rej[i >> 1] |= (uint64_t)1 << ((2 * (i & 1) + j) * 16 + g);
             continue;
           }
         }
@@ -689,6 +742,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
 template <int AM, int BMODE, bool RAG>
 __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
   constexpr bool A_KC = AM == LK, B_KC = BMODE == LK;
+  constexpr int BN = BN_NARROW, B_PLANE = Tile<BN>::B_PLANE, BUF = Tile<BN>::BUF;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int *sexp = reinterpret_cast<int *>(lds + 2 * BUF);  // [BM] rows, then [BN] columns
   float *sw = reinterpret_cast<float *>(sexp + BM + BN);  // spread weights, the same order
@@ -704,7 +758,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
   const int T = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
   const int klast = kend - kbeg - (T - 1) * BK;  // valid k of the last tile
 
-  const int flags = tile_scales(p, sexp, sw, row0, col0, tid);
+  const int flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
 
   // descriptors whose range ends at the operand's last element: a partial
   // last tile reads 0 past it (and the split zeroes the pitch's padding)
@@ -807,7 +861,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
     }
   }
 
-  tile_epilogue<A_KC, B_KC>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
+  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -828,16 +882,30 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
 // its power limit.  f16x3's three leave the clock up, and the MFMA pipe idles
 // on LDS latency instead (35-44 % busy at 2.1-2.3 GHz with the two-phase
 // loop).
-template <int AM, int BMODE, bool RAG>
+//
+// The wide tile (BN_WIDE) has 24 MFMAs in a phase and 128 accumulator
+// registers per lane, so it cannot hold two fragment sets and two loader
+// sets.  A half's MFMAs go accumulator row by accumulator row, and only two
+// rows' A fragments are held: row i + 1's are read beside row i's MFMAs, a
+// phase's last row reads the next phase's first, and the four B fragments
+// are re-read during the last row as each dies.  Reading a buffer in both of
+// a step's phases needs a second barrier, at the step's end (one barrier per
+// 24 MFMAs of a wave, the narrow tile's rate).  One loader set per operand:
+// phase A splits tile t+1 out of it piece by piece, and each part
+// (Loader::load_part) is loaded again with tile t+2 as soon as its last piece
+// is split, a whole K step (48 MFMAs, the narrow tile's two) before that
+// tile's split.
+template <int AM, int BMODE, bool RAG, int BN = BN_NARROW>
 __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
   constexpr bool A_KC = AM == LK, B_KC = BMODE == LK;
+  constexpr int B_PLANE = Tile<BN>::B_PLANE, BUF = Tile<BN>::BUF, MI = Tile<BN>::MI;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   int *sexp = reinterpret_cast<int *>(lds + 2 * BUF);
   float *sw = reinterpret_cast<float *>(sexp + BM + BN);
   const int tid = threadIdx.x;
   const float m1 = kcnn::f16x3::opaque_m1();
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
+  const int wm = wave / Tile<BN>::WN, wn = wave % Tile<BN>::WN;
   int split, tm, tn;
   const bool whole = block_tile(p, split, tm, tn);
   const int row0 = tm * BM, col0 = tn * BN;
@@ -861,116 +929,213 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
 
   using LA = Loader<BM, AM>;
   using LB = Loader<BN, BMODE>;
-  LA la[2];
-  LB lb[2];
-  f32x16 acc[2][2];
+  f32x16 acc[MI][2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.0f;
 
-  const int ar = wm * 64, br = wn * 64;
-  f16x8 fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
-  // r-th fragment of half s: A fragments (i, plane) first, then B
-  auto read_frag = [&](const char *buf, int s, int r, f16x8 (&fa)[2][2], f16x8 (&fb)[2][2]) {
-    if (r < 4) {
-      const int i = r >> 1, pl = r & 1;
-      fa[i][pl] = LA::frag(buf + pl * A_PLANE, ar + 32 * i, s, lane);
-    } else {
-      const int i = (r - 4) >> 1, pl = (r - 4) & 1;
-      fb[i][pl] = LB::frag(buf + 2 * A_PLANE + pl * B_PLANE, br + 32 * i, s, lane);
-    }
-  };
-  // n-th MFMA of a half: accumulator (n / 6, (n / 3) % 2), lo.hi, hi.lo, hi.hi
-  auto mfma_n = [&](int n, const f16x8 (&fa)[2][2], const f16x8 (&fb)[2][2]) {
-    const int i = n / 6, j = (n / 3) & 1, pr = n % 3;
-    constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
-    acc[i][j] = mfma(fa[i][PA[pr]], fb[j][PB[pr]], acc[i][j]);
-  };
-
+  const int ar = wm * Tile<BN>::WR, br = wn * 64;
   // waves 4-7 (each SIMD's second wave) at priority 1 for the whole kernel
   // (MI355X_MICROARCH.md, two waves per SIMD, item 4: the younger half loses
   // every VALU arbitration otherwise)
   constexpr int PRIO = 1;
   if (PRIO && wave >= 4) __builtin_amdgcn_s_setprio(1);
-  // the first two K tiles' loads go out before the tile's scales are read
-  // (the split needs both; the scales' loads and barriers then pass under
-  // the tiles' latency: c2's data gradient 400 -> 381 us at K 1024 without
-  // the scales at all)
-  if (T > 0) {
-    la[0].load(rsA, p.lda, vra, kk(0, A_KC), tid);
-    lb[0].load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
-    la[1].load(rsA, p.lda, vra, kk(1, A_KC), tid);
-    lb[1].load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  const int flags = tile_scales(p, sexp, sw, row0, col0, tid);
-  la[0].init_exp(sexp, tid);
-  la[1].init_exp(sexp, tid);
-  lb[0].init_exp(sexp + BM, tid);
-  lb[1].init_exp(sexp + BM, tid);
-  if (T > 0) {
-    la[0].template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
-    lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+  int flags = 0;
+  if constexpr (BN == BN_WIDE) {
+    LA la;
+    LB lb;
+    // two A rows and the four B fragments: row i's MFMAs run beside the reads
+    // of row i + 1 into the other slot
+    f16x8 fa[2][2], fb[2][2];
+    // n-th MFMA of a half: accumulator (n / 6, (n / 3) % 2), lo.hi, hi.lo, hi.hi
+    auto mfma_n = [&](int n) {
+      const int i = n / 6, j = (n / 3) & 1, pr = n % 3;
+      constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
+      acc[i][j] = mfma(fa[i & 1][PA[pr]], fb[j][PB[pr]], acc[i][j]);
+    };
+    // the fragment reads placed after MFMA n of the phase on half s of buf;
+    // (nb, ns) is the next phase's buffer and half.  Row i's first two MFMAs
+    // are followed by the reads of the next row (the next phase's row 0 after
+    // the last) into the slot row i - 1 left; B's four are re-read for the
+    // next phase during the last row, each after its last use (column block
+    // 0's lo, hi, then block 1's), three MFMAs or more before its first
+    auto reads_after = [&](int n, const char *buf, int s, const char *nb, int ns) {
+      constexpr int L = 6 * MI;
+      const int i = n / 6, r = (i + 1) % MI;
+      const char *src = i + 1 < MI ? buf : nb;
+      const int hs = i + 1 < MI ? s : ns;
+      if (n % 6 == 0) fa[r & 1][1] = LA::frag(src + A_PLANE, ar + 32 * r, hs, lane);
+      if (n % 6 == 1) fa[r & 1][0] = LA::frag(src, ar + 32 * r, hs, lane);
+      if (n == L - 5) fb[0][1] = LB::frag(nb + 2 * A_PLANE + B_PLANE, br, ns, lane);
+      if (n == L - 4) fb[0][0] = LB::frag(nb + 2 * A_PLANE, br, ns, lane);
+      if (n == L - 2) fb[1][1] = LB::frag(nb + 2 * A_PLANE + B_PLANE, br + 32, ns, lane);
+      if (n == L - 1) fb[1][0] = LB::frag(nb + 2 * A_PLANE, br + 32, ns, lane);
+    };
+    if (T > 0) {
+      la.load(rsA, p.lda, vra, kk(0, A_KC), tid);
+      lb.load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
+    }
     __builtin_amdgcn_sched_barrier(0);
-    la[0].load(rsA, p.lda, vra, kk(2, A_KC), tid);
-    lb[0].load(rsB, p.ldb, vrb, kk(2, B_KC), tid);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 8; ++r) read_frag(lds, 0, r, fa0, fb0);
-
-    // step t: tile t+1 is in set (t+1) & 1 (split in phase A), which then
-    // takes tile t+3 (phase B; a step past T issues its clamped loads too)
-    // (more_c: std::true_type where the step is known not to be the last,
-    // so its split and next-fragment reads carry no branch; std::false_type
-    // for the last step, which has neither)
-    auto step = [&](int t, LA &lan, LB &lbn, auto more_c) {
-      const char *buf = lds + (t & 1) * BUF;
-      char *nbuf = lds + ((t + 1) & 1) * BUF;
-      constexpr bool more = decltype(more_c)::value;
-      const int kv = t + 2 == T ? klast : BK;
-      uint32_t ph[4], pl[4];
-      // phase A
-#pragma unroll
-      for (int n = 0; n < 12; ++n) {
-        mfma_n(n, fa0, fb0);
-        if (more) {
-          if (n < LA::NPIECE)
-            lan.template piece<A_PLANE, RAG>(nbuf, tid, n, kv, ph, pl, m1);
-          else if (n - LA::NPIECE < LB::NPIECE)
-            lbn.template piece<B_PLANE, RAG>(nbuf + 2 * A_PLANE, tid, n - LA::NPIECE, kv, ph, pl, m1);
-        }
-        if (n >= 2 && n < 10) read_frag(buf, 1, n - 2, fa1, fb1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+    flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
+    la.init_exp(sexp, tid);
+    lb.init_exp(sexp + BM, tid);
+    if (T > 0) {
+      la.template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
+      lb.template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+      __builtin_amdgcn_sched_barrier(0);
+      la.load(rsA, p.lda, vra, kk(1, A_KC), tid);
+      lb.load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
       __syncthreads();
-      // phase B
 #pragma unroll
-      for (int n = 0; n < 12; ++n) {
-        mfma_n(n, fa1, fb1);
-        if (n == 1) lan.load(rsA, p.lda, vra, kk(t + 3, A_KC), tid);
-        if (n == 3) lbn.load(rsB, p.ldb, vrb, kk(t + 3, B_KC), tid);
-        if (more && n >= 2 && n < 10) read_frag(nbuf, 0, n - 2, fa0, fb0);
-        __builtin_amdgcn_sched_barrier(0);
+      for (int pl = 0; pl < 2; ++pl) fa[0][pl] = LA::frag(lds + pl * A_PLANE, ar, 0, lane);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+          fb[j][pl] = LB::frag(lds + 2 * A_PLANE + pl * B_PLANE, br + 32 * j, 0, lane);
+
+      // step t: the loader set holds tile t+1 (split in phase A) and takes
+      // tile t+2 part by part behind the split.  The last step does the same
+      // with the clamped tile (a re-read of tile T-1, split into the buffer
+      // no one reads again): one loop body, no peeled copy whose fragments
+      // would have to live beside the loop's at the join
+      auto step = [&](int t) {
+        const char *buf = lds + (t & 1) * BUF;
+        char *nbuf = lds + ((t + 1) & 1) * BUF;
+        const int kv = t + 2 == T ? klast : BK;
+        uint32_t ph[4], pl[4];
+        // phase A
+#pragma unroll
+        for (int n = 0; n < 6 * MI; ++n) {
+          mfma_n(n);
+          if (n < LA::NPIECE) {
+            la.template piece<A_PLANE, RAG>(nbuf, tid, n, kv, ph, pl, m1);
+            if ((n + 1) % LA::PPP == 0)
+              la.load_part(rsA, p.lda, vra, kk(t + 2, A_KC), tid, n / LA::PPP);
+          } else if (n - LA::NPIECE < LB::NPIECE) {
+            const int m = n - LA::NPIECE;
+            lb.template piece<B_PLANE, RAG>(nbuf + 2 * A_PLANE, tid, m, kv, ph, pl, m1);
+            if ((m + 1) % LB::PPP == 0)
+              lb.load_part(rsB, p.ldb, vrb, kk(t + 2, B_KC), tid, m / LB::PPP);
+          }
+          reads_after(n, buf, 0, buf, 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();  // tile t+1 written
+        // phase B
+#pragma unroll
+        for (int n = 0; n < 6 * MI; ++n) {
+          mfma_n(n);
+          reads_after(n, buf, 1, nbuf, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();  // buffer t & 1 read by every wave: step t+1 writes it
+      };
+      static_assert(LA::NPIECE + LB::NPIECE <= 6 * MI, "a piece per MFMA of phase A");
+#pragma unroll 1
+      for (int t = 0; t < T; ++t) step(t);
+    }
+  } else {
+    LA la[2];
+    LB lb[2];
+    f16x8 fa0[2][2], fb0[2][2], fa1[2][2], fb1[2][2];
+    // r-th fragment of half s: A fragments (i, plane) first, then B
+    auto read_frag = [&](const char *buf, int s, int r, f16x8 (&fa)[2][2], f16x8 (&fb)[2][2]) {
+      if (r < 4) {
+        const int i = r >> 1, pl = r & 1;
+        fa[i][pl] = LA::frag(buf + pl * A_PLANE, ar + 32 * i, s, lane);
+      } else {
+        const int i = (r - 4) >> 1, pl = (r - 4) & 1;
+        fb[i][pl] = LB::frag(buf + 2 * A_PLANE + pl * B_PLANE, br + 32 * i, s, lane);
       }
     };
-    int t = 0;
-    // every step of the loop has a successor; the last one or two after it
-    for (; t + 2 < T; t += 2) {
-      step(t, la[1], lb[1], std::true_type{});
-      step(t + 1, la[0], lb[0], std::true_type{});
+    // n-th MFMA of a half: accumulator (n / 6, (n / 3) % 2), lo.hi, hi.lo, hi.hi
+    auto mfma_n = [&](int n, const f16x8 (&fa)[2][2], const f16x8 (&fb)[2][2]) {
+      const int i = n / 6, j = (n / 3) & 1, pr = n % 3;
+      constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
+      acc[i][j] = mfma(fa[i][PA[pr]], fb[j][PB[pr]], acc[i][j]);
+    };
+
+    // the first two K tiles' loads go out before the tile's scales are read
+    // (the split needs both; the scales' loads and barriers then pass under
+    // the tiles' latency: c2's data gradient 400 -> 381 us at K 1024 without
+    // the scales at all)
+    if (T > 0) {
+      la[0].load(rsA, p.lda, vra, kk(0, A_KC), tid);
+      lb[0].load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
+      la[1].load(rsA, p.lda, vra, kk(1, A_KC), tid);
+      lb[1].load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
     }
-    if (t + 1 < T) {
-      step(t, la[1], lb[1], std::true_type{});
-      step(t + 1, la[0], lb[0], std::false_type{});
-    } else {
-      step(t, la[1], lb[1], std::false_type{});
+    __builtin_amdgcn_sched_barrier(0);
+    flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
+    la[0].init_exp(sexp, tid);
+    la[1].init_exp(sexp, tid);
+    lb[0].init_exp(sexp + BM, tid);
+    lb[1].init_exp(sexp + BM, tid);
+    if (T > 0) {
+      la[0].template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
+      lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+      __builtin_amdgcn_sched_barrier(0);
+      la[0].load(rsA, p.lda, vra, kk(2, A_KC), tid);
+      lb[0].load(rsB, p.ldb, vrb, kk(2, B_KC), tid);
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < 8; ++r) read_frag(lds, 0, r, fa0, fb0);
+
+      // step t: tile t+1 is in set (t+1) & 1 (split in phase A), which then
+      // takes tile t+3 (phase B; a step past T issues its clamped loads too)
+      // (more_c: std::true_type where the step is known not to be the last,
+      // so its split and next-fragment reads carry no branch; std::false_type
+      // for the last step, which has neither)
+      auto step = [&](int t, LA &lan, LB &lbn, auto more_c) {
+        const char *buf = lds + (t & 1) * BUF;
+        char *nbuf = lds + ((t + 1) & 1) * BUF;
+        constexpr bool more = decltype(more_c)::value;
+        const int kv = t + 2 == T ? klast : BK;
+        uint32_t ph[4], pl[4];
+        // phase A
+#pragma unroll
+        for (int n = 0; n < 12; ++n) {
+          mfma_n(n, fa0, fb0);
+          if (more) {
+            if (n < LA::NPIECE)
+              lan.template piece<A_PLANE, RAG>(nbuf, tid, n, kv, ph, pl, m1);
+            else if (n - LA::NPIECE < LB::NPIECE)
+              lbn.template piece<B_PLANE, RAG>(nbuf + 2 * A_PLANE, tid, n - LA::NPIECE, kv, ph, pl, m1);
+          }
+          if (n >= 2 && n < 10) read_frag(buf, 1, n - 2, fa1, fb1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+        // phase B
+#pragma unroll
+        for (int n = 0; n < 12; ++n) {
+          mfma_n(n, fa1, fb1);
+          if (n == 1) lan.load(rsA, p.lda, vra, kk(t + 3, A_KC), tid);
+          if (n == 3) lbn.load(rsB, p.ldb, vrb, kk(t + 3, B_KC), tid);
+          if (more && n >= 2 && n < 10) read_frag(nbuf, 0, n - 2, fa0, fb0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      int t = 0;
+      // every step of the loop has a successor; the last one or two after it
+      for (; t + 2 < T; t += 2) {
+        step(t, la[1], lb[1], std::true_type{});
+        step(t + 1, la[0], lb[0], std::true_type{});
+      }
+      if (t + 1 < T) {
+        step(t, la[1], lb[1], std::true_type{});
+        step(t + 1, la[0], lb[0], std::false_type{});
+      } else {
+        step(t, la[1], lb[1], std::false_type{});
+      }
     }
   }
 
-  tile_epilogue<A_KC, B_KC>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
+  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
 }
 
 // Max |x| and min nonzero |x| per row or per column of a pitched fp32 matrix,
@@ -1640,48 +1805,91 @@ __global__ __launch_bounds__(256) void gemm_f16x3_fixup_kernel(GemmF16Args p, in
   }
 }
 
-// The split-K count (and the whole tiles in front of the split ones,
-// block_tile) of least modelled time: the whole tiles in nwhole / 256 rounds
-// of one workgroup per CU, the split ones in ceil((tiles - nwhole) s / 256)
-// rounds, a round of k steps 0.0458 k + 11.1 us (the tile prologue and
-// epilogue; fitted to c2's three FC GEMMs on MI355X), and for s > 1 the
+// The plan of a call: the tile, the split-K count and the whole tiles in
+// front of the split ones (block_tile), of least modelled time.  Per tile:
+// the whole tiles in nwhole / 256 rounds of one workgroup per CU, the split
+// ones in ceil((tiles - nwhole) s / 256) rounds, a round of k steps
+// a k + b us (b: the tile prologue and epilogue), and for s > 1 the
 // reduce's (s + 1) fp32 reads and writes of the split tiles' share of M N
-// at 4 TB/s.  (The reduce was unpriced before r06: nnet.config's 4096 x 3454
+// at 4 TB/s.  Narrow tile: 0.0458 k + 11.1, fitted to c2's three FC GEMMs on
+// MI355X.  (The reduce was unpriced before r06: nnet.config's 4096 x 3454
 // x 4096 layers took 4 splits and an 86-92 us reduce, one split being 2.4 %
 // faster per step; c2's 364-tile weight gradient split all its tiles in 2.84
 // rounds, where 256 whole tiles and 108 split ones take 1 + 0.84.)
-int choose_ksplit(int64_t tiles, int M, int N, int K, int *nwhole = nullptr) {
-  auto round = [](int k) { return 0.0458 * k + 11.1; };
-  int best = 1, best_w = 0;
-  double best_t = (double)((tiles + 255) / 256) * round(K);
+// Wide tile: 0.0793 k + 21.4, fitted on MI355X to 4096 x 4096 x K calls (256
+// wide tiles, one round; 512 narrow ones, two) at K = 1024, 2016 and 4096
+// with each tile forced: 120.9 / 209.0 / 412.6 us wide against 134.3 / 235.1 /
+// 463.7 narrow, the narrow times less the narrow model being the statistics
+// launches both share (profiles/gemm_tiles.md, which also has c2's three
+// GEMMs: forward 353 -> 329 us, data gradient 377 -> 344, both as the model
+// picks; the weight gradient's 184 wide tiles measured 380 against the narrow
+// hybrid's 411, which the model, 346 against 314, does not see: it prices a
+// round of 184 workgroups as one of 256).
+// A pure function of the call's shape: no timing or history enters it.
+struct GemmPlan {
+  int bn, ksplit, nwhole;
+  double us;
+};
+constexpr double NARROW_A = 0.0458, NARROW_B = 11.1;
+constexpr double WIDE_A = 0.0793, WIDE_B = 21.4;
+GemmPlan plan_tile(int bn, int M, int N, int K) {
+  const int64_t tiles = (int64_t)((M + BM - 1) / BM) * ((N + bn - 1) / bn);
+  const double ca = bn == BN_WIDE ? WIDE_A : NARROW_A, cb = bn == BN_WIDE ? WIDE_B : NARROW_B;
+  auto round = [&](int k) { return ca * k + cb; };
+  GemmPlan best{bn, 1, 0, (double)((tiles + 255) / 256) * round(K)};
   for (int s = 2; s <= 4 && K / s >= 1024; ++s) {
     const int ks = (K + s - 1) / s;
     for (int64_t w = 0; w < tiles; w += 256) {
       const int64_t rest = tiles - w;
       const double t = (double)(w / 256) * round(K) + (double)((rest * s + 255) / 256) * round(ks) +
                        (double)(s + 1) * M * N * 4.0 / 4.0e6 * (double)rest / (double)tiles;
-      if (t < best_t) { best_t = t; best = s; best_w = (int)w; }
+      if (t < best.us) best = GemmPlan{bn, s, (int)w, t};
     }
   }
-  if (nwhole) *nwhole = best > 1 ? best_w : 0;
   return best;
 }
+// family: the "gemm" selector (kcnn-knobs.h): 3 the wide tile wherever the
+// call can take it (wide_ok: no LR operand), 4 the narrow tile, else the model
+GemmPlan choose_plan(int M, int N, int K, bool wide_ok, int family) {
+  const GemmPlan narrow = plan_tile(BN_NARROW, M, N, K);
+  if (!wide_ok || family == 4) return narrow;
+  const GemmPlan wide = plan_tile(BN_WIDE, M, N, K);
+  if (family == 3) return wide;
+  return wide.us < narrow.us ? wide : narrow;
+}
+// an operand's loader: K-contiguous, or row-contiguous with 16-B loads along
+// its rows when they are aligned (pitch % 4 == 0: a quad that starts inside
+// the row count M or N ends inside the pitch; its values past the count feed
+// only C rows or columns that are not stored, and the kernel's descriptors
+// end at the last row's padded quad), else one dword per lane
+int loader_mode(bool kc, const void *ptr, int ld) {
+  if (kc) return (int)LK;
+  return ld % 4 == 0 && (uintptr_t)ptr % 16 == 0 ? (int)LT : (int)LR;
+}
+std::atomic<unsigned long long> g_tile_calls[2];  // launches on the narrow, the wide tile
 
 // the one-barrier fast kernel where no operand is LR (an LR operand's 16
-// loaded values per thread and K step spill there), else the two-phase
-// kernel (bitwise the same C)
+// loaded values per thread and K step spill there), on the plan's tile, else
+// the two-phase kernel on the narrow tile (bitwise the same C)
+template <int AM, int BMODE, bool RAG, int BN>
+void launch_fast(const GemmF16Args &a, unsigned blocks, hipStream_t st) {
+  constexpr int LDS_BYTES = Tile<BN>::LDS_BYTES;
+  static bool attr = [] {
+    return hipFuncSetAttribute(
+               reinterpret_cast<const void *>(&gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN>),
+               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
+  }();
+  (void)attr;
+  hipLaunchKernelGGL((gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN>), dim3(blocks), dim3(NT),
+                     LDS_BYTES, st, a);
+}
 template <int AM, int BMODE, bool RAG>
 void launch_t(const GemmF16Args &a, unsigned blocks, hipStream_t st) {
   if constexpr (AM != LR && BMODE != LR) {
-    static bool attr = [] {
-      return hipFuncSetAttribute(
-                 reinterpret_cast<const void *>(&gemm_f16x3_fast_kernel<AM, BMODE, RAG>),
-                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-    }();
-    (void)attr;
-    hipLaunchKernelGGL((gemm_f16x3_fast_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT),
-                       LDS_BYTES, st, a);
+    if (a.bn == BN_WIDE) launch_fast<AM, BMODE, RAG, BN_WIDE>(a, blocks, st);
+    else launch_fast<AM, BMODE, RAG, BN_NARROW>(a, blocks, st);
   } else {
+    constexpr int LDS_BYTES = Tile<BN_NARROW>::LDS_BYTES;
     static bool attr = [] {
       return hipFuncSetAttribute(
                  reinterpret_cast<const void *>(&gemm_f16x3_kernel<AM, BMODE, RAG>),
@@ -1719,9 +1927,10 @@ size_t slab_bytes(int s, int M, int N) {
 size_t flag_bytes(int M, int N) {
   return align16(sizeof(uint32_t) * (((size_t)M * ((N + 3) / 4) + 63) / 64 + 1));
 }
+// (of the larger split count of the two tiles' plans: the workspace is sized
+// before the operands' alignment and the selector's value at the call are known)
 size_t partial_bytes(int M, int N, int K) {
-  const int64_t tiles = (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  const int s = choose_ksplit(tiles, M, N, K);
+  const int s = std::max(plan_tile(BN_NARROW, M, N, K).ksplit, plan_tile(BN_WIDE, M, N, K).ksplit);
   return s > 1 ? slab_bytes(s, M, N) + flag_bytes(M, N) : 0;
 }
 
@@ -1811,6 +2020,29 @@ extern "C" int kl_gemm_stats3(const float *X0, int rows0, int cols0, int ld0, in
 extern "C" size_t kl_gemm_f16x3_workspace_bytes(int M, int N, int K) {
   return partial_bytes(M, N, K);
 }
+// f16x3 launches on the narrow tile (out[0]) and on the wide tile (out[1])
+// since the last reset
+extern "C" void kl_gemm_f16x3_tile_counts(unsigned long long *out, int reset) {
+  for (int i = 0; i < 2; ++i) {
+    out[i] = g_tile_calls[i].load(std::memory_order_relaxed);
+    if (reset) g_tile_calls[i].store(0, std::memory_order_relaxed);
+  }
+}
+// The plan of a call under the current "gemm" selector, without a GPU:
+// out = {the tile's columns, ksplit, nwhole}; operand bases taken as 16-B
+// aligned, a workspace of kl_gemm_f16x3_workspace_bytes given.  Returns the
+// plan's workspace need (0 for one split).
+extern "C" size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K, int lda,
+                                     int ldb, int *out) {
+  out[0] = out[1] = out[2] = 0;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const int am = loader_mode(!transA, nullptr, lda), bm = loader_mode(transB != 0, nullptr, ldb);
+  const GemmPlan plan = choose_plan(M, N, K, am != LR && bm != LR, kcnn::family(kcnn::kFamGemm));
+  out[0] = plan.bn;
+  out[1] = plan.ksplit;
+  out[2] = plan.ksplit > 1 ? plan.nwhole : 0;
+  return plan.ksplit > 1 ? slab_bytes(plan.ksplit, M, N) + flag_bytes(M, N) : 0;
+}
 // The fix-up launch of a split-K call (an exit-at-once kernel of 4.4 us in
 // all but the rare calls with a spread group, FIX_GRID) is skipped for a call
 // site (shape, transposes, momentum or not) whose previous call deferred no
@@ -1880,11 +2112,16 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   a.bvec = N % 4 == 0 && (uintptr_t)a.bmax % 16 == 0 && (uintptr_t)a.bcnt % 16 == 0;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.alpha = alpha; a.beta = beta;
+  const int am = loader_mode(a_kc, A, lda), bm = loader_mode(b_kc, B, ldb);
+  const GemmPlan plan =
+      choose_plan(M, N, K, am != LR && bm != LR, kcnn::family(kcnn::kFamGemm));
+  const int BN = plan.bn;
+  a.bn = BN;
   a.tiles_m = (M + BM - 1) / BM;
   a.tiles_n = (N + BN - 1) / BN;
   const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-  int nwhole = 0;
-  int s = choose_ksplit(tiles, M, N, K, &nwhole);
+  int nwhole = plan.nwhole;
+  int s = plan.ksplit;
   const size_t need = s > 1 ? slab_bytes(s, M, N) + flag_bytes(M, N) : 0;
   if (need > ws_bytes || !ws) s = 1;
   if (s > 1) {
@@ -1907,15 +2144,6 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   a.nwhole = nwhole;
   const int64_t nb = nwhole + (tiles - nwhole) * s;
   if (nb >= ((int64_t)1 << 31)) return (int)hipErrorNotSupported;
-  // a row-contiguous operand takes 16-B loads along its rows when they are
-  // aligned (pitch % 4 == 0: a quad that starts inside the row count M or N
-  // ends inside the pitch; its values past the count feed only C rows or
-  // columns that are not stored, and the descriptors above end at the last
-  // row's padded quad)
-  auto mode = [](bool kc, const float *ptr, int ld) {
-    if (kc) return (int)LK;
-    return ld % 4 == 0 && (uintptr_t)ptr % 16 == 0 ? (int)LT : (int)LR;
-  };
   bool fix_launch = true;
   if (s > 1) {
     uint32_t *dev = nullptr;
@@ -1927,8 +2155,9 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
       a.fix_local = fix_launch ? 0 : 1;
     }
   }
-  launch(mode(a_kc, A, lda), mode(b_kc, B, ldb), a, (unsigned)nb, st);
+  launch(am, bm, a, (unsigned)nb, st);
   int rc = kcnn::launch_status();
+  if (!rc) g_tile_calls[BN == BN_WIDE ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   if (rc || s == 1) return rc;
   hipLaunchKernelGGL(gemm_f16x3_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * ((N + 3) / 4))),
                      dim3(256), 0, st, a, a_kc ? 1 : 0, b_kc ? 1 : 0);

@@ -60,6 +60,12 @@ int kl_gemm_stats3(const float *X0, int rows0, int cols0, int ld0, int mode0, ui
                    int ld2, int mode2, uint32_t *out2, uint32_t *part2, void *pool_cols,
                    kcnn_stream_t stream);
 size_t kl_gemm_f16x3_workspace_bytes(int M, int N, int K);
+/* launches on the narrow (out[0]) and the wide (out[1]) tile since the last
+   reset; the plan {tile columns, ksplit, nwhole} a call would get under the
+   current "gemm" selector (returns its split-K workspace need) */
+void kl_gemm_f16x3_tile_counts(unsigned long long *out, int reset);
+size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K, int lda, int ldb,
+                          int *out);
 int kl_gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alpha,
                      const float *A, int lda, const float *B, int ldb, float beta, float *C,
                      int ldc, const uint32_t *amax, const uint32_t *bmax, void *ws,

@@ -291,7 +291,7 @@ CuGemmBackpropStats::CuGemmBackpropStats(const CuMatrixBase<float> &dy,
                                          const CuMatrixBase<float> *in) {
   CuDevice &dev = CuDevice::Instantiate();
   const int N = dy.NumRows(), O = dy.NumCols(), I = W.NumCols();
-  if (dev.GemmMode() != 2 || N == 0 || O == 0 || I == 0 || W.NumRows() != O) return;
+  if (dev.GemmMode() < 2 || N == 0 || O == 0 || I == 0 || W.NumRows() != O) return;
   // an enclosing launch set already covers them (kcnn_nnet_backprop_split:
   // the gradient and the data gradient of one layer around the caller's
   // all-reduce, one statistics pass for both)
@@ -374,7 +374,7 @@ bool CuMatrixBase<Real>::AddMatMatMomentum(const CuMatrixBase<Real> &A,
   auto aligned = [](const CuMatrixBase<Real> &X) {
     return X.Stride() % 4 == 0 && reinterpret_cast<uintptr_t>(X.Data()) % 16 == 0;
   };
-  if (dev0.GemmMode() != 2 || m == 0 || n == 0 || k == 0 || !aligned(A) || !aligned(B) ||
+  if (dev0.GemmMode() < 2 || m == 0 || n == 0 || k == 0 || !aligned(A) || !aligned(B) ||
       !aligned(*this) || !aligned(*prev))
     return false;
   KALDI_ASSERT((transA == kNoTrans ? A.NumRows() : A.NumCols()) == m &&
@@ -411,7 +411,7 @@ void CuMatrixBase<Real>::AddMatMatBias(Real alpha, const CuMatrixBase<Real> &A,
   auto aligned = [](const CuMatrixBase<Real> &X) {
     return X.Stride() % 4 == 0 && reinterpret_cast<uintptr_t>(X.Data()) % 16 == 0;
   };
-  if (dev0.GemmMode() == 2 && num_rows_ > 0 && num_cols_ > 0 && k > 0 && aligned(A) &&
+  if (dev0.GemmMode() >= 2 && num_rows_ > 0 && num_cols_ > 0 && k > 0 && aligned(A) &&
       aligned(B)) {
     KALDI_ASSERT((transA == kNoTrans ? A.NumRows() : A.NumCols()) == num_rows_ &&
                  (transB == kNoTrans ? B.NumCols() : B.NumRows()) == num_cols_ &&
@@ -439,7 +439,7 @@ void CuMatrixBase<Real>::AddMatMat(Real alpha, const CuMatrixBase<Real> &A,
   CuDevice &dev0 = CuDevice::Instantiate();
   const int mode = dev0.GemmMode();
   if (mode >= 1) {
-    // fp32 product on the f16 (mode 2, cu-gemm-f16x3.hip) or bf16 (mode 1,
+    // fp32 product on the f16 (mode 2 and above, cu-gemm-f16x3.hip) or bf16 (mode 1,
     // cu-gemm-x6.hip) MFMAs from a split of each operand.  Their 16-B loads
     // need the K-contiguous operands (A untransposed, B transposed)
     // row-aligned; one that is not (a caller's matrix with an odd pitch,
@@ -453,9 +453,9 @@ void CuMatrixBase<Real>::AddMatMat(Real alpha, const CuMatrixBase<Real> &A,
     };
     CuMatrix<Real> Acopy, Bcopy;
     const CuMatrixBase<Real> *Ap = &A, *Bp = &B;
-    if ((transA == kNoTrans || mode == 2) && !aligned(A)) { Acopy = A; Ap = &Acopy; }
-    if ((transB == kTrans || mode == 2) && !aligned(B)) { Bcopy = B; Bp = &Bcopy; }
-    if (mode == 2 && GemmF16x3(alpha, A, *Ap, transA, B, *Bp, transB, beta, nullptr)) return;
+    if ((transA == kNoTrans || mode >= 2) && !aligned(A)) { Acopy = A; Ap = &Acopy; }
+    if ((transB == kTrans || mode >= 2) && !aligned(B)) { Bcopy = B; Bp = &Bcopy; }
+    if (mode >= 2 && GemmF16x3(alpha, A, *Ap, transA, B, *Bp, transB, beta, nullptr)) return;
     const size_t wsb = kl_gemm_x6_workspace_bytes(m, n, k);
     void *ws = wsb ? dev0.Malloc(wsb) : nullptr;
     const int rc = kl_gemm_x6(transA == kTrans, transB == kTrans, m, n, k, alpha,

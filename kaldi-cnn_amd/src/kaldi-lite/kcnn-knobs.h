@@ -14,7 +14,11 @@
 //                               below), 3 f16x3 for all, 1 bf16x6, 0 fp32 MFMA
 //   wgrad_x6   KCNN_WGRAD_X6    2 wide bf16x6, 3 wide f16x3 (slower on c5), 1 128-wide bf16x6,
 //                               0 fp32 MFMA
-//   gemm       KCNN_GEMM        2 f16x3 GEMM (AddMatMat), 1 bf16x6 GEMM, 0 rocBLAS sgemm
+//   gemm       KCNN_GEMM        2 f16x3 GEMM (AddMatMat), its tile (256 x 128 or 256 x 256)
+//                               chosen per call by the cost model (cu-gemm-f16x3.hip
+//                               choose_plan); 3 f16x3 with the 256 x 256 tile for every
+//                               call that can take it; 4 f16x3 with the 256 x 128 tile for
+//                               every call; 1 bf16x6 GEMM; 0 rocBLAS sgemm
 //
 // (KCNN_FUSE, KCNN_LITERAL and KCNN_PROFILE are kcnn_set_fusion,
 // kcnn_set_literal_path and kcnn_set_profiling.)
