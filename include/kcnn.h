@@ -103,6 +103,18 @@ int kcnn_gemm_tile_counts(unsigned long long *out, int reset);
  * out[1] the split-K count, out[2] the whole tiles in front of the split
  * ones.  lda / ldb are the pitches of A and B (16-B aligned bases assumed). */
 int kcnn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int lda, int ldb, int *out);
+/* The f16x3 GEMM's split-K calls since the last reset: out[0] those that
+ * launched the fix-up kernel after the reduce, out[1] those that skipped it
+ * (their reduce recomputes every rejected element itself); reset != 0 zeroes
+ * them.  A call launches the fix-up when its site (shape, transposes,
+ * momentum or not) is new, has no slot in the site table, or reported a
+ * deferred group in its previous call.  Host counters: no device call. */
+int kcnn_gemm_fixup_counts(unsigned long long *out, int reset);
+/* Forget every fix-up call site: the next split-K call at any key is a new
+ * site and launches the fix-up.  Host only, no device call; meant for a
+ * synchronised device (a reduce still in flight may set a reused word, which
+ * costs one fix-up launch, never a result).  A test diagnostic. */
+int kcnn_gemm_fixup_sites_reset(void);
 /* Kernel-family selectors (kaldi-lite/kcnn-knobs.h): each picks
  * one of the implementations of the same fp32 math: the split-operand
  * kernels on the f16 / bf16 matrix cores (f16x3: two f16 parts under a

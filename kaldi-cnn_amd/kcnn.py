@@ -199,6 +199,20 @@ def gemm_plan(trans_a, trans_b, m, n, k, lda=None, ldb=None):
     return tuple(int(v) for v in out)
 
 
+def gemm_fixup_counts(reset=False):
+    """(split-K f16x3 GEMM calls that launched the fix-up kernel, calls that
+    skipped it) since the last reset (kcnn_gemm_fixup_counts; no GPU needed)."""
+    out = (ctypes.c_ulonglong * 2)()
+    check(lib().kcnn_gemm_fixup_counts(out, int(bool(reset))))
+    return tuple(int(v) for v in out)
+
+
+def gemm_fixup_sites_reset():
+    """Forget every fix-up call site: the next split-K call at any key launches
+    the fix-up (kcnn_gemm_fixup_sites_reset; no GPU needed)."""
+    check(lib().kcnn_gemm_fixup_sites_reset())
+
+
 def set_kernel_family(name: str, value: int):
     """Kernel-family selector (kcnn.h): "fwd_x6" (2 f16x3 / 1 bf16x6 / 0),
     "bwd_x6", "igemm_x6", "wgrad_x6" (2 wide / 1 / 0) or "gemm" (2 f16x3 /

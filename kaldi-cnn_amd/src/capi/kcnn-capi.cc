@@ -196,6 +196,15 @@ int kcnn_gemm_plan(int trans_a, int trans_b, int m, int n, int k, int lda, int l
   kl_gemm_f16x3_plan(trans_a, trans_b, m, n, k, lda, ldb, out);
   return 0;
 }
+int kcnn_gemm_fixup_counts(unsigned long long *out, int reset) {
+  if (!out) return fail("kcnn_gemm_fixup_counts: out is NULL");
+  kl_gemm_f16x3_fixup_counts(out, reset);
+  return 0;
+}
+int kcnn_gemm_fixup_sites_reset(void) {
+  kl_gemm_f16x3_fixup_sites_reset();
+  return 0;
+}
 int kcnn_set_kernel_family(const char *name, int value) {
   const int f = kcnn::family_by_name(name);
   if (f < 0) return fail("kcnn_set_kernel_family: unknown family");

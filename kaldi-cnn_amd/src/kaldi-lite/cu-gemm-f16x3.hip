@@ -1542,6 +1542,12 @@ int stats_launch(const StatOp &a, const StatOp &b, hipStream_t st) {
 // gemm_f16x3_fixup_kernel, which spreads such groups over the whole GPU: a
 // spread row rejects hundreds of elements of one row, and one wave's
 // wave_dots in series took milliseconds (nnet.config's weight gradients).
+// A call launched without the fix-up (fix_local) recomputes such a group
+// itself, in the order the fix-up would have used: the quarter order
+// (quarter_sums) when the call's `rows` holds, wave_dot when not.  So a
+// rejected element's bits depend on the operands and on whether its group of
+// 64 quads exceeds REJ_LOCAL, never on which kernel recomputed it.  Every pass of a wave keeps all 64 lanes (a quad past the end rejects
+// nothing): wave_dot spreads K over the whole wave.
 constexpr int REJ_LOCAL = 4;
 __device__ __forceinline__ uint32_t reduce_quad(const GemmF16Args &p, int64_t e, int nq, int np4,
                                                 int64_t plane, int &r, int &c, bool store) {
@@ -1658,29 +1664,133 @@ __device__ __forceinline__ uint32_t reduce_quad(const GemmF16Args &p, int64_t e,
   return rej;
 }
 
+// A quarter of K (quarter q of 4: k in [q kq, min(K, (q + 1) kq)), kq = K / 4
+// rounded up) of the W sums of C[r][c .. c + W - 1], op(B) row-contiguous
+// (W = 4: a quad by 16-B loads of op(B)'s rows; W = 1: one element): for
+// each column, products k0 + 4 i + j go to accumulator j in increasing k
+// over the quarter's whole multiples of FIX_DEPTH, the rest to accumulator 0,
+// and the accumulators are added as (0 + 1) + (2 + 3).  A column's sum does
+// not depend on W, nor on DEPTH, which is only how many k steps are loaded at
+// once (the same products added in the same order).
+constexpr int FIX_DEPTH = 16;
+template <int W>
+__device__ __forceinline__ void load_cols(const float *q, float (&y)[W]) {
+  if constexpr (W == 4) {
+    const float4 t = *reinterpret_cast<const float4 *>(q);
+    y[0] = t.x; y[1] = t.y; y[2] = t.z; y[3] = t.w;
+  } else {
+    static_assert(W == 1, "a quad or one element");
+    y[0] = *q;
+  }
+}
+template <int DEPTH, int W>
+__device__ __forceinline__ void quarter_sums(const float *A, int lda, const float *B, int ldb,
+                                             int K, bool a_kc, int r, int c, int quarter,
+                                             float (&q)[W]) {
+  static_assert(DEPTH % 4 == 0 && FIX_DEPTH % DEPTH == 0, "accumulator j takes k = k0 + 4 i + j");
+  const int kq = (K + 3) >> 2;
+  const int k0 = quarter * kq, k1 = min(K, k0 + kq);
+  const int km = k0 + max(k1 - k0, 0) / FIX_DEPTH * FIX_DEPTH;
+  const int64_t sa = a_kc ? 1 : lda;
+  const float *qa = a_kc ? A + (int64_t)r * lda + k0 : A + (int64_t)k0 * lda + r;
+  const float *qb = B + (int64_t)k0 * ldb + c;
+  float acc[4][W];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < W; ++j) acc[i][j] = 0.0f;
+  int k = k0;
+#pragma unroll 1
+  for (; k < km; k += DEPTH) {
+    float x[DEPTH];
+    float y[DEPTH][W];
+#pragma unroll
+    for (int i = 0; i < DEPTH; ++i) {
+      x[i] = qa[i * sa];
+      load_cols<W>(qb + (int64_t)i * ldb, y[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < DEPTH; ++i)
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc[i & 3][j] = fmaf(x[i], y[i][j], acc[i & 3][j]);
+    qa += DEPTH * sa;
+    qb += (int64_t)DEPTH * ldb;
+  }
+#pragma unroll 1
+  for (; k < k1; ++k) {
+    const float x = *qa;
+    float y[W];
+    load_cols<W>(qb, y);
+#pragma unroll
+    for (int j = 0; j < W; ++j) acc[0][j] = fmaf(x, y[j], acc[0][j]);
+    qa += sa;
+    qb += ldb;
+  }
+#pragma unroll
+  for (int j = 0; j < W; ++j) q[j] = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
+}
+// loads in flight per lane in the reduce's own quarter sums (fix_local), which
+// take one element at a time: the kernel runs in every split-K call and is
+// bound by its slab reads, so the rarely taken path must not raise its
+// register count
+constexpr int LOCAL_DEPTH = 4;
+
 __global__ __launch_bounds__(256) void gemm_f16x3_reduce_kernel(GemmF16Args p, int a_kc,
-                                                                int b_kc) {
+                                                                int b_kc, int rows) {
   const int np4 = (p.N + 3) & ~3, nq = np4 >> 2;
   const int64_t total = (int64_t)p.M * nq;
   const int64_t plane = (int64_t)p.M * np4;
   const int lane = threadIdx.x & 63;
-  // e0 = the wave's first quad, a multiple of 64 below total: lane 0 is
-  // active in every pass, and every group of 64 quads gets its flag written
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    // (a whole tile's quads were stored by its workgroup: no slabs, no rejections)
+  // the bound is total rounded up to the wave's 64 quads, so a pass keeps or
+  // drops a whole wave (the last group's lanes past total stay, on quad 0
+  // with no rejection: wave_dot below needs all 64), and every group of 64
+  // quads gets its flag written
+  const int64_t padded = (total + 63) & ~(int64_t)63;
+  for (int64_t el = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; el < padded;
+       el += (int64_t)gridDim.x * blockDim.x) {
+    // (a whole tile's quads were stored by its workgroup: no slabs, no
+    // rejections.  One index for both uses below: the 64-bit division is
+    // then computed once)
+    const bool inside = el < total;
+    const int64_t e = inside ? el : 0;
     int r = (int)(e / nq), c = (int)(e - (int64_t)r * nq) * 4;
-    const uint32_t rej = in_split_tile(p, r, c) ? reduce_quad(p, e, nq, np4, plane, r, c, true) : 0u;
-    // the wave's rejections (ballots: only the active lanes)
+    const bool valid = inside && in_split_tile(p, r, c);
+    uint32_t rej = valid ? reduce_quad(p, e, nq, np4, plane, r, c, true) : 0u;
+    // the wave's rejections
     const int n = __builtin_popcountll(__ballot(rej & 1)) + __builtin_popcountll(__ballot(rej & 2)) +
                   __builtin_popcountll(__ballot(rej & 4)) + __builtin_popcountll(__ballot(rej & 8));
-    const bool defer = n > REJ_LOCAL && !p.fix_local;
+    const bool over = n > REJ_LOCAL;
+    const bool defer = over && !p.fix_local;
     if (lane == 0) {
-      p.rflag[e >> 6] = defer ? 1u : 0u;
+      p.rflag[el >> 6] = defer ? 1u : 0u;
       if (defer) p.rflag[(total + 63) >> 6] = p.gen;
-      if (n > REJ_LOCAL && p.fix_report) *p.fix_report = 1u;
+      if (over && p.fix_report) *p.fix_report = 1u;
     }
-    if (n == 0 || defer) continue;
+    // (expected: what follows is rare, and the register allocator should
+    // not spill the pass's own values for it)
+    if (__builtin_expect(n == 0 || defer, 1)) continue;
+    if (over && rows) {
+      // the fix-up's sums of this group, each lane its own quad's rejected
+      // elements in turn: the four quarters, added in quarter order (the
+      // fix-up's wave order, a left fold).  The shape enters through a
+      // barrier, so that this rare path's invariants are formed here and do
+      // not take scalar registers from every pass of every call.
+      int K = p.K, lda = p.lda, ldb = p.ldb, akc = a_kc;
+      asm volatile("" : "+s"(K), "+s"(lda), "+s"(ldb), "+s"(akc));
+#pragma unroll 1
+      for (; rej; rej &= rej - 1) {
+        const int col = c + __builtin_ctz(rej);
+        float s[1], t[1];
+        quarter_sums<LOCAL_DEPTH, 1>(p.A, lda, p.B, ldb, K, akc != 0, r, col, 0, s);
+#pragma unroll 1
+        for (int w = 1; w < 4; ++w) {
+          quarter_sums<LOCAL_DEPTH, 1>(p.A, lda, p.B, ldb, K, akc != 0, r, col, w, t);
+          s[0] += t[0];
+        }
+        emit(p, r, col, s[0]);
+      }
+      continue;
+    }
     fix_rejected(p, a_kc != 0, b_kc != 0, rej, lane, [&](int l, int bit, int &row, int &col) {
       row = __builtin_amdgcn_readlane(r, l);
       col = __builtin_amdgcn_readlane(c, l) + bit;
@@ -1693,13 +1803,15 @@ __global__ __launch_bounds__(256) void gemm_f16x3_reduce_kernel(GemmF16Args p, i
 // consecutive groups of one spread row go to different blocks.  A group's
 // rejections are found again (reduce_quad, not stored) and recomputed in fp32:
 //  - op(B) row-contiguous with 16-B rows (`rows`): every lane its quad's four sums, the
-//    block's four waves each over a quarter of K (16-B loads of op(B)'s rows,
-//    coalesced over the lanes; the lanes of one C row share op(A)'s element),
-//    the quarters added in wave order, the rejected elements stored;
+//    block's four waves each over a quarter of K (quarter_sums: 16-B loads of
+//    op(B)'s rows, coalesced over the lanes; the lanes of one C row share
+//    op(A)'s element), the quarters added in wave order, the rejected
+//    elements stored;
 //  - otherwise: wave_dot per rejected element, the quads dealt to
 //    the waves by lane & 3.
-// Deterministic: the group's results do not depend on the block or order.
-constexpr int FIX_DEPTH = 16;
+// Deterministic: the group's results do not depend on the block or order,
+// and they are the bits the reduce gives the group when the call runs
+// without this kernel (fix_local).
 // the fixup's grid: a flagged call's groups take the workgroups in turn
 // (c2's weight-gradient shape with 32 spread rows, 1452 groups: +925 us at
 // 128 workgroups, measured r05 by a one-off driver); an unflagged call exits at the
@@ -1743,52 +1855,9 @@ __global__ __launch_bounds__(256) void gemm_f16x3_fixup_kernel(GemmF16Args p, in
         continue;
       }
       // this wave's quarter of K for the lane's quad (r, c .. c + 3)
-      const int kq = (p.K + 3) >> 2;
-      const int k0 = wave * kq, k1 = min(p.K, k0 + kq);
-      const int64_t sa = a_kc ? 1 : p.lda;
-      const float *qa = a_kc ? p.A + (int64_t)r * p.lda + k0 : p.A + (int64_t)k0 * p.lda + r;
-      const float *qb = p.B + (int64_t)k0 * p.ldb + c;
-      float4 acc[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      int k = k0;
-#pragma unroll 1
-      for (; k + FIX_DEPTH <= k1; k += FIX_DEPTH) {
-        float x[FIX_DEPTH];
-        float4 y[FIX_DEPTH];
-#pragma unroll
-        for (int i = 0; i < FIX_DEPTH; ++i) {
-          x[i] = qa[i * sa];
-          y[i] = *reinterpret_cast<const float4 *>(qb + (int64_t)i * p.ldb);
-        }
-#pragma unroll
-        for (int i = 0; i < FIX_DEPTH; ++i) {
-          float4 &t = acc[i & 3];
-          t.x = fmaf(x[i], y[i].x, t.x);
-          t.y = fmaf(x[i], y[i].y, t.y);
-          t.z = fmaf(x[i], y[i].z, t.z);
-          t.w = fmaf(x[i], y[i].w, t.w);
-        }
-        qa += FIX_DEPTH * sa;
-        qb += (int64_t)FIX_DEPTH * p.ldb;
-      }
-#pragma unroll 1
-      for (; k < k1; ++k) {
-        const float x = *qa;
-        const float4 y = *reinterpret_cast<const float4 *>(qb);
-        acc[0].x = fmaf(x, y.x, acc[0].x);
-        acc[0].y = fmaf(x, y.y, acc[0].y);
-        acc[0].z = fmaf(x, y.z, acc[0].z);
-        acc[0].w = fmaf(x, y.w, acc[0].w);
-        qa += sa;
-        qb += p.ldb;
-      }
-      float4 q;
-      q.x = (acc[0].x + acc[1].x) + (acc[2].x + acc[3].x);
-      q.y = (acc[0].y + acc[1].y) + (acc[2].y + acc[3].y);
-      q.z = (acc[0].z + acc[1].z) + (acc[2].z + acc[3].z);
-      q.w = (acc[0].w + acc[1].w) + (acc[2].w + acc[3].w);
-      quarter[wave][lane] = q;
+      float q[4];
+      quarter_sums<FIX_DEPTH, 4>(p.A, p.lda, p.B, p.ldb, p.K, a_kc != 0, r, c, wave, q);
+      quarter[wave][lane] = make_float4(q[0], q[1], q[2], q[3]);
       __syncthreads();
       if (wave == 0 && rej) {
         const float4 q0 = quarter[0][lane], q1 = quarter[1][lane], q2 = quarter[2][lane],
@@ -2049,8 +2118,13 @@ extern "C" size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K
 // group: the site's word in host memory, cleared by the host at each launch
 // and set by the reduce when a group would have been deferred, is read at
 // the next launch.  A skipped call's reduce recomputes every rejection itself
-// (fix_local), so a stale or wrong guess costs time, never a result.  Up to
+// (fix_local), a group over REJ_LOCAL in the order the fix-up would have used
+// (gemm_f16x3_reduce_kernel), so the word, read without a synchronise, never
+// reaches a result: a stale or wrong guess costs time, not a bit of C
+// (tests/test_gpu_gemm_fixup.py runs every route in both states).  Up to
 // FIX_SITES sites; the others always launch the fix-up.
+// kl_gemm_f16x3_fixup_counts counts the calls either way and
+// kl_gemm_f16x3_fixup_sites_reset forgets the sites, for those tests.
 constexpr int FIX_SITES = 256;
 struct FixSites {
   std::mutex mu;
@@ -2060,9 +2134,28 @@ struct FixSites {
   int n = 0;
   bool failed = false;
 };
+static FixSites &fix_sites() {
+  static FixSites fs;
+  return fs;
+}
+// split-K calls that launched the fix-up, that skipped it
+static std::atomic<unsigned long long> g_fix_calls[2];
+extern "C" void kl_gemm_f16x3_fixup_counts(unsigned long long *out, int reset) {
+  for (int i = 0; i < 2; ++i) {
+    out[i] = g_fix_calls[i].load(std::memory_order_relaxed);
+    if (reset) g_fix_calls[i].store(0, std::memory_order_relaxed);
+  }
+}
+// every site forgotten: the next call at any key registers again, word 1 (the
+// pinned words stay allocated; no device call)
+extern "C" void kl_gemm_f16x3_fixup_sites_reset(void) {
+  FixSites &fs = fix_sites();
+  std::lock_guard<std::mutex> lk(fs.mu);
+  fs.n = 0;
+}
 // the word of this site, nullptr when there is none (table full, no host memory)
 static uint32_t *fix_site(int M, int N, int K, int ta, int tb, int mom, uint32_t **dev) {
-  static FixSites fs;
+  FixSites &fs = fix_sites();
   std::lock_guard<std::mutex> lk(fs.mu);
   if (!fs.flags && !fs.failed) {
     void *h = nullptr, *d = nullptr;
@@ -2159,12 +2252,14 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   int rc = kcnn::launch_status();
   if (!rc) g_tile_calls[BN == BN_WIDE ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   if (rc || s == 1) return rc;
-  hipLaunchKernelGGL(gemm_f16x3_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * ((N + 3) / 4))),
-                     dim3(256), 0, st, a, a_kc ? 1 : 0, b_kc ? 1 : 0);
-  rc = kcnn::launch_status();
-  if (rc || !fix_launch) return rc;
-  // op(B) row-contiguous: the fixup's 16-B loads along its rows
+  // op(B) row-contiguous: 16-B loads along its rows in the recomputation of
+  // a group over REJ_LOCAL, by the fix-up or (fix_local) by the reduce
   const int rows = !b_kc && ldb % 4 == 0 && (uintptr_t)B % 16 == 0 && N % 4 == 0;
+  hipLaunchKernelGGL(gemm_f16x3_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * ((N + 3) / 4))),
+                     dim3(256), 0, st, a, a_kc ? 1 : 0, b_kc ? 1 : 0, rows);
+  rc = kcnn::launch_status();
+  if (!rc) g_fix_calls[fix_launch ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+  if (rc || !fix_launch) return rc;
   const int64_t slots = ((int64_t)M * ((N + 3) / 4) + 63) / 64;
   hipLaunchKernelGGL(gemm_f16x3_fixup_kernel,
                      dim3((unsigned)std::min<int64_t>(FIX_GRID, (slots + 15) / 16)), dim3(256), 0, st,

@@ -66,6 +66,11 @@ size_t kl_gemm_f16x3_workspace_bytes(int M, int N, int K);
 void kl_gemm_f16x3_tile_counts(unsigned long long *out, int reset);
 size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K, int lda, int ldb,
                           int *out);
+/* split-K calls since the last reset that launched the fix-up kernel (out[0])
+   and that skipped it (out[1]); forget every fix-up call site (the next call
+   at any key is a fresh site, which launches the fix-up).  Host only. */
+void kl_gemm_f16x3_fixup_counts(unsigned long long *out, int reset);
+void kl_gemm_f16x3_fixup_sites_reset(void);
 int kl_gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alpha,
                      const float *A, int lda, const float *B, int ldb, float beta, float *C,
                      int ldc, const uint32_t *amax, const uint32_t *bmax, void *ws,

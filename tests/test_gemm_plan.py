@@ -100,6 +100,45 @@ def test_c2_plans(kc, name, m, n, k, ta, tb):
     assert kc.gemm_plan(ta, tb, m, n, k) == C2_PLANS[name]
 
 
+# tests/test_gpu_gemm_fixup.py's shapes: the smallest that split K (a split's
+# K / s >= 1024), with (tile, ksplit, nwhole) under selectors 2, 3 and 4.  If
+# the cost model stops splitting them that file checks nothing, so this goes
+# red first, without a GPU.
+FIXUP_PLANS = [((256, 256, 2048), {2: (NARROW, 2, 0), 3: (WIDE, 2, 0), 4: (NARROW, 2, 0)}),
+               ((260, 260, 3104), {2: (NARROW, 3, 0), 3: (WIDE, 3, 0), 4: (NARROW, 3, 0)}),
+               ((256, 258, 4133), {2: (NARROW, 4, 0), 3: (WIDE, 4, 0), 4: (NARROW, 4, 0)}),
+               ((260, 256, 2048), {2: (NARROW, 2, 0), 3: (WIDE, 2, 0), 4: (NARROW, 2, 0)}),
+               ((1024, 11616, 2048), {2: (NARROW, 2, 256), 3: (WIDE, 1, 0),
+                                      4: (NARROW, 2, 256)})]
+
+
+@pytest.mark.parametrize("mode", [2, 3, 4])
+@pytest.mark.parametrize("shape,plans", FIXUP_PLANS, ids=[str(p[0]) for p in FIXUP_PLANS])
+def test_fixup_test_shapes_split(kc, mode, shape, plans):
+    kc.set_kernel_family("gemm", mode)
+    m, n, k = shape
+    for ta in (False, True):
+        for tb in (False, True):
+            # 16-B pitches, as AddMatMat hands the operands to the kernel
+            lda = (m if ta else k) + 3 & ~3
+            ldb = (k if tb else n) + 3 & ~3
+            assert kc.gemm_plan(ta, tb, m, n, k, lda=lda, ldb=ldb) == plans[mode]
+    if mode == 2:   # the full-table case's 256 small keys
+        for mi in range(4, 1025, 4):
+            assert kc.gemm_plan(False, False, mi, 4, 2048) == (NARROW, 2, 0)
+
+
+def test_fixup_counters_and_site_reset_need_no_gpu(kc):
+    """kcnn_gemm_fixup_counts / kcnn_gemm_fixup_sites_reset are host-side: they
+    work without a device, and the counters read zero after a reset."""
+    kc.gemm_fixup_sites_reset()
+    kc.gemm_fixup_counts(reset=True)
+    assert kc.gemm_fixup_counts() == (0, 0)
+    assert kc.gemm_fixup_counts(reset=True) == (0, 0)
+    kc.gemm_fixup_sites_reset()
+    assert kc.gemm_fixup_counts() == (0, 0)
+
+
 def test_whole_plus_split_plans_on_the_wide_tile(kc):
     """The wide tile's hybrid grid (nwhole > 0) is reachable: forced on
     (1024, 20480, 2048), which tests/test_gpu_gemm_wide.py runs, and by the
