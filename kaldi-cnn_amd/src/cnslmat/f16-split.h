@@ -23,8 +23,9 @@
 // fp32) the products that touch them, which restores the 1e-5 * S parity
 // bar per element; the f16 MFMA runs at the bf16 rate, so this
 // is half the matrix-core work of bf16x6 (x6-util.h) for fewer split VALU.
-// Users: the FC GEMM (kaldi-lite/cu-gemm-f16x3.hip) and the frame-resident
-// conv forward (cnsl-conv-frame.hip).
+// Users: the FC GEMM (kaldi-lite/cu-gemm-f16x3.hip; its split-K finish,
+// cu-gemm-f16x3-reduce.hip; the statistics pass, cu-f16-stats.hip) and the
+// frame-resident conv forward (cnsl-conv-frame.hip).
 #ifndef KCNN_CNSLMAT_F16_SPLIT_H_
 #define KCNN_CNSLMAT_F16_SPLIT_H_
 

@@ -4,7 +4,7 @@
 // from the suspect frames.  Shared by the standalone kernels the forward
 // launches (cnsl-conv-frame.hip pool_colmax_kernel, pool_count_kernel) and
 // the FC backward's statistics launches, which take this work over when the
-// forward leaves it pending (kaldi-lite/cu-gemm-f16x3.hip kl_gemm_stats3).
+// forward leaves it pending (kaldi-lite/cu-f16-stats.hip kl_gemm_stats3).
 #ifndef KCNN_CNSLMAT_POOL_STATS_DEV_H_
 #define KCNN_CNSLMAT_POOL_STATS_DEV_H_
 

@@ -3,7 +3,7 @@
 //
 // The register-pooled frame forward (cnsl-conv-frame.hip) writes, besides the
 // pooled output and its routing mask, the pooled output's statistics blocks
-// (the GEMM's, cu-gemm-f16x3.hip: [max[n], min[n], cnt[n]]) per frame
+// (the GEMM's, cu-f16-stats.hip: [max[n], min[n], cnt[n]]) per frame
 // (rowmax[3R]: max |value| bits, exact; min nonzero |value| bits, 0 for
 // none) and per pooled column (colmax[3 npool]: the max's binade with every
 // mantissa bit set, which is all the GEMM's power-of-two scale reads; the

@@ -26,16 +26,16 @@
 // group's max, f16-split.h) every element is held to 2^-19, and a product is
 // within (2 * 2^-19 + 2^-22) S of exact; a product touching a spread group
 // is checked at its store against the count of the group's small elements
-// and recomputed in fp32 when the check cannot clear it (tile_epilogue,
-// gemm_f16x3_reduce_kernel).  So every finite C element meets the 1e-5 * S
-// parity bar whatever the operands' range; the scale puts a
+// and recomputed in fp32 when the check cannot clear it (tile_epilogue;
+// gemm_f16x3_reduce_kernel, cu-gemm-f16x3-reduce.hip).  So every finite C
+// element meets the 1e-5 * S parity bar whatever the operands' range; the scale puts a
 // whole row near FLT_MAX or of fp32 subnormals into f16's range like any
 // other (the bf16x6 split loses bits there).  The f16 MFMA runs at the bf16
 // rate: half the matrix-core work of bf16x6 for the same split VALU.
 //
-// The scales come from per-row / per-column max |x| (kl_absmax_rows /
-// kl_absmax_cols: the bit patterns of |x|, whose unsigned order is the
-// magnitude order).  A row of
+// The scales come from per-row / per-column max |x| (cu-f16-stats.hip,
+// kl_absmax_rows / kl_absmax_cols: the bit patterns of |x|, whose unsigned
+// order is the magnitude order).  A row of
 // op(A) or a column of op(B) holding Inf or NaN has no scale; every C
 // element in it is Inf or NaN in IEEE arithmetic.  The main loop leaves
 // those elements alone and the tile's split-0 workgroup computes them as
@@ -49,51 +49,34 @@
 // (double-buffered, 2 x 48 KB), one barrier per step; or, where the call's
 // plan says so (choose_plan), a 256 x 256 tile (8 waves of 4 x 2 accumulators,
 // 2 x 64 KB; gemm_f16x3_fast_kernel with BN_WIDE).  Thin outputs split K
-// over workgroups into partial slabs, which gemm_f16x3_reduce_kernel sums in
-// a fixed order.
+// over workgroups into partial slabs, which gemm_f16x3_reduce_kernel
+// (cu-gemm-f16x3-reduce.hip) sums in a fixed order.  What both files' kernels
+// use is in gemm-f16x3-dev.h.
 #include <atomic>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 
 #include "cnslmat/f16-split.h"
 #include "cnslmat/hip-util.h"
-#include "cnslmat/momentum-step.h"
-#include "cnslmat/pool-stats-dev.h"
-#include "cnslmat/pool-stats.h"
 #include "kaldi-lite/cu-kernels-lite.h"
+#include "kaldi-lite/f16-stats.h"
+#include "kaldi-lite/gemm-f16x3-dev.h"
 #include "kaldi-lite/kcnn-knobs.h"
+#include "kaldi-lite/launch-lds.h"
 
 namespace {
 
-using kcnn::COLMAX_ROWS;
-using kcnn::PoolCountSmem;
-using kcnn::pool_colmax_block;
-using kcnn::pool_count_block;
-using kcnn::f16x3::f16x8;
-using kcnn::f16x3::f32x16;
-using kcnn::f16x3::NONFINITE;
-using kcnn::f16x3::SKIP;
-using kcnn::f16x3::scale_exp;
-using kcnn::f16x3::split2h;
-using kcnn::f16x3::mfma;
+using namespace kcnn::f16x3;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int BM = 256, BK = 32, NT = 512;
+constexpr int NT = 512;
 constexpr int ROWB = BK * 2;                  // bytes per LDS row of one plane
 constexpr int A_PLANE = BM * ROWB;            // 16 KB
-// The tile of C per workgroup is BM x BN: the narrow tile (BN 128, 8 waves
-// of 64 x 64, 2 x 2 accumulators each) or the wide one (BN 256, 8 waves of
-// 128 x 64, 4 x 2 accumulators: per MFMA two thirds of the narrow tile's
-// operand loads, split and LDS writes, three quarters of its fragment reads,
-// half its barriers and tiles).  Both hold the same 32 x 32 accumulator
-// blocks of C, each summed in the same order: the same bits.
-constexpr int BN_NARROW = 128, BN_WIDE = 256;
 template <int BN>
 struct Tile {
   static constexpr int WN = BN / 64;             // waves along the columns
@@ -104,37 +87,13 @@ struct Tile {
   static constexpr int LDS_BYTES = 2 * BUF + (BM + BN) * 8;  // + sexp, sw
 };
 
-struct GemmF16Args {
-  const float *A, *B;
-  float *C;                      // the output
-  float *part;                   // ksplit > 1: the partial slabs [ksplit][M][N]
-  uint32_t *rflag;               // ksplit > 1: per 64 quads of C, 1 when the reduce left
-                                 // its rejections to gemm_f16x3_fixup_kernel; after
-                                 // them one word, gen when any group was flagged
-  uint32_t gen;                  // this call's number (host counter, never 0)
-  const uint32_t *amax, *bmax;   // max |x| bits per row of op(A), per column of op(B)
-  const uint32_t *amin, *bmin;   // min nonzero |x| bits (0: none), the same groups
-  const uint32_t *acnt, *bcnt;   // spread groups: their elements below 2^-3 after the scale
-  const float *bias;             // nullable: C += bias[col] on every row (after alpha, beta)
-  int M, N, K, lda, ldb, ldc;
-  int bvec;                      // bmax, bcnt 16-B aligned and N % 4 == 0 (the reduce's loads)
-  MomentumEpi mom;               // mom.W: C is a weight gradient applied in the store (emit)
-  int kps, ksplit, tiles_m, tiles_n;
-  int bn;                        // the tile's columns (BN_NARROW or BN_WIDE)
-  int nwhole;                    // ksplit > 1: the first nwhole tiles (a multiple of 256) whole
-  int fix_local;                 // ksplit > 1: no fix-up launch; the reduce recomputes every rejection
-  uint32_t *fix_report;          // nullable (host memory): set to 1 when a group would be deferred
-  float alpha, beta;
-};
-
 // Tile t of the order -> (tile row, tile column).  The tiles go in groups of
 // GM tile rows, column-major inside a group, so the 32 workgroups an XCD runs
 // at once (consecutive logical ids, block_tile) cover about 32 / GM tile
 // columns of GM tile rows, sharing GM row panels of op(A) and a few column
 // panels of op(B) in that XCD's L2, instead of one row panel and 32 column
 // panels (c2's data gradient: an XCD wave then reads 8 MB of operand panels
-// instead of 17)
-constexpr int GM = 4;
+// instead of 17).  (Back: tile_index, gemm-f16x3-dev.h.)
 __device__ __forceinline__ void tile_rc(const GemmF16Args &p, int t, int &tm, int &tn) {
   const int gsz = GM * p.tiles_n;
   const int g = t / gsz, r = t - g * gsz;
@@ -142,12 +101,6 @@ __device__ __forceinline__ void tile_rc(const GemmF16Args &p, int t, int &tm, in
   const int gm = min(p.tiles_m - m0, GM);
   tm = m0 + r % gm;
   tn = r / gm;
-}
-// ... and back: the order's index of tile (tm, tn)
-__device__ __forceinline__ int tile_index(const GemmF16Args &p, int tm, int tn) {
-  const int g = tm / GM, m0 = g * GM;
-  const int gm = min(p.tiles_m - m0, GM);
-  return g * GM * p.tiles_n + tn * gm + (tm - m0);
 }
 // This workgroup's (split, tile row, tile column); true for a whole tile.
 // Blocks [0, nwhole) take tiles [0, nwhole) over all of K, the others the
@@ -167,10 +120,48 @@ __device__ __forceinline__ bool block_tile(const GemmF16Args &p, int &split, int
   tile_rc(p, (whole ? 0 : p.nwhole) + lid / ks, tm, tn);
   return whole;
 }
-// C element (r, c) is a split tile's (its value from the partial slabs)
-__device__ __forceinline__ bool in_split_tile(const GemmF16Args &p, int r, int c) {
-  return p.nwhole == 0 || tile_index(p, r / BM, c / p.bn) >= p.nwhole;
-}
+
+// A workgroup's work: its tile (block_tile), its span of K in steps of BK,
+// and, once bound, the operands' buffer descriptors from the tile's first row
+// (K-contiguous) or the span's first k (row-contiguous)
+template <bool A_KC, bool B_KC, int BN>
+struct TileWork {
+  int split;
+  bool whole;           // the tile over all of K (block_tile)
+  int row0, col0;
+  int kbeg, T, klast;   // first k, K steps, valid k of the last step
+  int vra, vrb;         // the rows of op(A) and columns of op(B) from the tile's first on
+  __amdgpu_buffer_rsrc_t rsA, rsB;
+
+  __device__ __forceinline__ explicit TileWork(const GemmF16Args &p) {
+    int tm, tn;
+    whole = block_tile(p, split, tm, tn);
+    row0 = tm * BM; col0 = tn * BN;
+    vra = p.M - row0; vrb = p.N - col0;
+    kbeg = whole ? 0 : split * p.kps;
+    const int kend = whole ? p.K : min(p.K, kbeg + p.kps);
+    T = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+    klast = kend - kbeg - (T - 1) * BK;
+  }
+  // descriptors whose range ends at the operand's last element: a partial
+  // last tile reads 0 past it (and the split zeroes the pitch's padding)
+  __device__ __forceinline__ void bind(const GemmF16Args &p) {
+    const float *baseA = A_KC ? p.A + (int64_t)row0 * p.lda : p.A + (int64_t)kbeg * p.lda + row0;
+    const float *baseB = B_KC ? p.B + (int64_t)col0 * p.ldb : p.B + (int64_t)kbeg * p.ldb + col0;
+    const int64_t endA = A_KC ? ((int64_t)(vra - 1) * p.lda + p.K) * 4
+                              : ((int64_t)(p.K - 1 - kbeg) * p.lda + vra) * 4;
+    const int64_t endB = B_KC ? ((int64_t)(vrb - 1) * p.ldb + p.K) * 4
+                              : ((int64_t)(p.K - 1 - kbeg) * p.ldb + vrb) * 4;
+    rsA = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)baseA, (short)0, (int)(endA < 0x7fffffff ? endA : 0x7fffffff), 0x00020000);
+    rsB = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)baseB, (short)0, (int)(endB < 0x7fffffff ? endB : 0x7fffffff), 0x00020000);
+  }
+  // k of tile t relative to the base (clamped to the last tile: a re-read)
+  __device__ __forceinline__ int kk(int t, bool kc) const {
+    return (kc ? kbeg : 0) + min(t, T - 1) * BK;
+  }
+};
 
 __device__ __forceinline__ int swz(int r, int c) {
   return r * ROWB + ((c ^ ((r >> 2) & 3)) << 4);
@@ -263,6 +254,13 @@ struct Loader {
     }
   }
 
+  // a unit's row, first 16-B chunk and first k of the step (LK, LR)
+  __device__ static __forceinline__ void unit_pos(int unit, int &r, int &c0, int &kb) {
+    r = MODE == LK ? unit >> 2 : unit % R;
+    c0 = MODE == LK ? unit & 3 : (unit / R) * (KPT / 8);
+    kb = MODE == LK ? c0 * 8 : (unit / R) * KPT;
+  }
+
   // split and write the two planes (plane stride PL bytes); kv < BK: the
   // tile is the last, partial one and its k >= kv are zeroed (they are the
   // next row's values or a pitch's padding)
@@ -297,15 +295,7 @@ struct Loader {
         }
       } else {
         int r, c0, kb;
-        if constexpr (MODE == LK) {
-          r = unit >> 2;
-          c0 = unit & 3;
-          kb = c0 * 8;
-        } else {
-          r = unit % R;
-          c0 = (unit / R) * (KPT / 8);
-          kb = (unit / R) * KPT;
-        }
+        unit_pos(unit, r, c0, kb);
         if (RAG && kv < BK) {
 #pragma unroll
           for (int j = 0; j < KPT; ++j)
@@ -353,15 +343,7 @@ struct Loader {
       const int u = pc / PPU, q = pc % PPU;
       const int unit = tid + u * NT;
       int r, c0, kb;
-      if constexpr (MODE == LK) {
-        r = unit >> 2;
-        c0 = unit & 3;
-        kb = c0 * 8;
-      } else {
-        r = unit % R;
-        c0 = (unit / R) * (KPT / 8);
-        kb = (unit / R) * KPT;
-      }
+      unit_pos(unit, r, c0, kb);
       float x0 = v[u][2 * q], x1 = v[u][2 * q + 1];
       if (RAG && kv < BK) {
         asm volatile("");  // a branch: not per-element selects in every K step
@@ -459,99 +441,16 @@ __device__ __forceinline__ int tile_scales(const GemmF16Args &p, int *sexp, floa
   return any_skip | (__syncthreads_or(spr) != 0 ? 2 : 0);
 }
 
-// One C element by a whole wave, for the store's check (called with the same
-// row and column in every lane): fp32 products of op(A) row i and op(B)
-// column j in a fixed order per lane, then a butterfly over the lanes (every
-// lane ends with the same bits: deterministic)
-__device__ __forceinline__ float wave_dot(const GemmF16Args &p, bool a_kc, bool b_kc, int row,
-                                          int col, int lane) {
-  // element k of the row of op(A) / column of op(B): qa[k * sa], qb[k * sb]
-  // (wave-uniform strides; the pointers step, no per-load index products)
-  const int64_t sa = a_kc ? 1 : p.lda, sb = b_kc ? 1 : p.ldb;
-  const float *qa = (a_kc ? p.A + (int64_t)row * p.lda : p.A + row) + lane * sa;
-  const float *qb = (b_kc ? p.B + (int64_t)col * p.ldb : p.B + col) + lane * sb;
-  const int64_t da = 64 * sa, db = 64 * sb;
-  // four partial sums (k = lane + 64 (4 i + j) into sum j): eight loads in
-  // flight per lane instead of one
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  int k = lane;
-#pragma unroll 1
-  for (; k + 192 < p.K; k += 256) {
-    float x[4], y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[j] = qa[j * da];
-      y[j] = qb[j * db];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] = fmaf(x[j], y[j], s[j]);
-    qa += 4 * da;
-    qb += 4 * db;
-  }
-#pragma unroll 1
-  for (; k < p.K; k += 64) {
-    s[0] = fmaf(*qa, *qb, s[0]);
-    qa += da;
-    qb += db;
-  }
-  float t = (s[0] + s[1]) + (s[2] + s[3]);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d);
-  return t;
+// C/D map of 32x32x16: register g of lane l holds row (g & 3) + 8 (g >> 2) +
+// 4 (l >> 5), column l & 31 of its 32 x 32 block.  cd_row: that row from
+// `base` on (half: l >> 5); cd_col: that column of the wave's block j from
+// `base` on.  (The base is inside, so that the sums keep one association.)
+__device__ __forceinline__ int cd_row(int base, int g, int half) {
+  return base + (g & 3) + 8 * (g >> 2) + 4 * half;
 }
-__device__ __forceinline__ float store_value(const GemmF16Args &p, float v, float *o, int col) {
-  float r = p.beta == 0.0f ? p.alpha * v : p.alpha * v + p.beta * *o;
-  if (p.bias) r += p.bias[col];
-  return r;
-}
-// C[row][col] from the product's value v; with p.mom.W the element is instead
-// the gradient of the momentum update (momentum-step.h: alpha * v, beta 0, no
-// bias), applied to W and prev in place of storing C
-__device__ __forceinline__ void emit(const GemmF16Args &p, int row, int col, float v) {
-  if (p.mom.W) {
-    float *w = p.mom.W + (int64_t)row * p.mom.ldw + col;
-    float *q = p.mom.prev + (int64_t)row * p.mom.ldp + col;
-    float wv = *w, pv = *q;
-    kcnn::momentum_step(p.alpha * v, pv, wv, p.mom.momentum, p.mom.a_wd, p.mom.a_g);
-    *q = pv;
-    *w = wv;
-    return;
-  }
-  float *o = p.C + (int64_t)row * p.ldc + col;
-  *o = store_value(p, v, o, col);
-}
-// The elements a lane's check rejected (bit n of `mine` its n-th candidate,
-// decode(lane, n) -> (row, col)), each recomputed by the whole wave
-// (wave_dot) and handed to put(l, n, row, col, v) on lane 0: a wave-uniform
-// loop over the wave's rejections
-template <typename Decode, typename Put>
-__device__ __forceinline__ void fix_rejected(const GemmF16Args &p, bool a_kc, bool b_kc,
-                                             uint64_t mine, int lane, Decode decode, Put put) {
-  for (;;) {
-    const uint64_t who = __ballot(mine != 0);
-    if (who == 0) break;
-    const int l = __builtin_ctzll(who);
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)mine, l);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(mine >> 32), l);
-    const uint64_t bits = ((uint64_t)hi << 32) | lo;
-    const int n = __builtin_ctzll(bits);
-    int row, col;
-    decode(l, n, row, col);
-    const float v = wave_dot(p, a_kc, b_kc, row, col, lane);
-    if (lane == 0) put(l, n, row, col, v);
-    if (lane == l) mine &= mine - 1;
-  }
-}
-template <typename Decode>
-__device__ __forceinline__ void fix_rejected(const GemmF16Args &p, bool a_kc, bool b_kc,
-                                             uint64_t mine, int lane, Decode decode) {
-  fix_rejected(p, a_kc, b_kc, mine, lane, decode,
-               [&](int, int, int row, int col, float v) { emit(p, row, col, v); });
-}
+__device__ __forceinline__ int cd_col(int base, int j, int l) { return base + j * 32 + (l & 31); }
 
-// The tile's results.  C/D map of 32x32x16: register g of lane l holds row
-// (g & 3) + 8 (g >> 2) + 4 (l >> 5), column l & 31.  Each value is unscaled
-// by 2^-(s_row + s_col) (exact).
+// The tile's results.  Each value is unscaled by 2^-(s_row + s_col) (exact).
 //  - One split (or a whole tile of a split grid, block_tile): C = alpha * v
 //    + beta * C.
 //  - ksplit > 1: the split's values go to its partial slab, which
@@ -591,8 +490,8 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
     for (int h = 0; h < MI / 2; ++h)
       fix_rejected(p, A_KC, B_KC, rej[h], lane, [&](int l, int n, int &row, int &col) {
         const int i = 2 * h + (n >> 5), j = (n >> 4) & 1, g = n & 15;
-        row = row0 + wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
-        col = col0 + wn * 64 + j * 32 + (l & 31);
+        row = cd_row(row0 + wm * WR + i * 32, g, l >> 5);
+        col = cd_col(col0 + wn * 64, j, l);
       });
   };
   // A whole tile without Inf / NaN rows or columns (block-uniform): each
@@ -615,21 +514,21 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int cl = wn * 64 + j * 32 + (lane & 31);
+        const int cl = cd_col(wn * 64, j, lane);
         const int ec = sexp[BM + cl];
         const float wc = check ? sw[BM + cl] : 0.0f;
         const bool bcheck =
             check && (__ballot(wc > 0.0f || sw[wm * WR + i * 32 + (lane & 31)] > 0.0f) != 0);
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const int rr = (g & 3) + 8 * (g >> 2) + 4 * half2;
+          const int rr = cd_row(0, g, half2);
           const int rl = wm * WR + i * 32 + rr;
           if (bcheck) {
             const float thr = wc + sw[rl];
             if (thr != 0.0f && !(fabsf(acc[i][j][g]) >= thr))
               rej[i >> 1] |= (uint64_t)1 << ((2 * (i & 1) + j) * 16 + g);
           }
-          st[rr * SR + j * 32 + (lane & 31)] =
+          st[cd_col(rr * SR, j, lane)] =
               __builtin_amdgcn_ldexpf(acc[i][j][g], -(sexp[rl] + ec));
         }
       }
@@ -641,13 +540,12 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
             p, A_KC, B_KC, mine, lane,
             [&](int l, int n, int &row, int &col) {
               const int j = (n >> 4) & 1, g = n & 15;
-              row = row0 + wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
-              col = col0 + wn * 64 + j * 32 + (l & 31);
+              row = cd_row(row0 + wm * WR + i * 32, g, l >> 5);
+              col = cd_col(col0 + wn * 64, j, l);
             },
             [&](int l, int n, int, int, float v) {
               const int j = (n >> 4) & 1, g = n & 15;
-              const int rr = (g & 3) + 8 * (g >> 2) + 4 * (l >> 5);
-              st[rr * SR + j * 32 + (l & 31)] = v;
+              st[cd_col(cd_row(0, g, l >> 5) * SR, j, l)] = v;
             });
       }
 #pragma unroll
@@ -659,13 +557,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
           float4 *wq = reinterpret_cast<float4 *>(p.mom.W + (int64_t)row * p.mom.ldw + col);
           float4 *pq = reinterpret_cast<float4 *>(p.mom.prev + (int64_t)row * p.mom.ldp + col);
           float4 w4 = *wq, q4 = *pq;
-          const MomentumEpi &m = p.mom;
-          kcnn::momentum_step(p.alpha * v.x, q4.x, w4.x, m.momentum, m.a_wd, m.a_g);
-          kcnn::momentum_step(p.alpha * v.y, q4.y, w4.y, m.momentum, m.a_wd, m.a_g);
-          kcnn::momentum_step(p.alpha * v.z, q4.z, w4.z, m.momentum, m.a_wd, m.a_g);
-          kcnn::momentum_step(p.alpha * v.w, q4.w, w4.w, m.momentum, m.a_wd, m.a_g);
-          *pq = q4;
-          *wq = w4;
+          momentum_quad(p, v, w4, q4, wq, pq);
           continue;
         }
         float4 *o = reinterpret_cast<float4 *>(slab + (int64_t)row * ldo + col);
@@ -694,7 +586,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
   for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int cl = wn * 64 + j * 32 + (lane & 31);
+      const int cl = cd_col(wn * 64, j, lane);
       const int col = col0 + cl;
       const int ec = sexp[BM + cl];
       if (col >= p.N || ec == SKIP) continue;
@@ -705,7 +597,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmF16Args &p, const int *s
           check && (__ballot(wc > 0.0f || sw[wm * WR + i * 32 + (lane & 31)] > 0.0f) != 0);
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        const int rl = wm * WR + i * 32 + (g & 3) + 8 * (g >> 2) + 4 * half2;
+        const int rl = cd_row(wm * WR + i * 32, g, half2);
         const int row = row0 + rl;
         const int er = sexp[rl];
         if (row >= p.M || er == SKIP) continue;
@@ -750,31 +642,9 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
   const float m1 = kcnn::f16x3::opaque_m1();
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  int split, tm, tn;
-  const bool whole = block_tile(p, split, tm, tn);
-  const int row0 = tm * BM, col0 = tn * BN;
-  const int kbeg = whole ? 0 : split * p.kps;
-  const int kend = whole ? p.K : min(p.K, kbeg + p.kps);
-  const int T = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
-  const int klast = kend - kbeg - (T - 1) * BK;  // valid k of the last tile
-
-  const int flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
-
-  // descriptors whose range ends at the operand's last element: a partial
-  // last tile reads 0 past it (and the split zeroes the pitch's padding)
-  const float *baseA = A_KC ? p.A + (int64_t)row0 * p.lda : p.A + (int64_t)kbeg * p.lda + row0;
-  const float *baseB = B_KC ? p.B + (int64_t)col0 * p.ldb : p.B + (int64_t)kbeg * p.ldb + col0;
-  const int vra = p.M - row0, vrb = p.N - col0;
-  const int64_t endA = A_KC ? ((int64_t)(vra - 1) * p.lda + p.K) * 4
-                            : ((int64_t)(p.K - 1 - kbeg) * p.lda + vra) * 4;
-  const int64_t endB = B_KC ? ((int64_t)(vrb - 1) * p.ldb + p.K) * 4
-                            : ((int64_t)(p.K - 1 - kbeg) * p.ldb + vrb) * 4;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)baseA, (short)0, (int)(endA < 0x7fffffff ? endA : 0x7fffffff), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)baseB, (short)0, (int)(endB < 0x7fffffff ? endB : 0x7fffffff), 0x00020000);
-  // k of tile t relative to the base (clamped to the last tile: a re-read)
-  auto kk = [&](int t, bool kc) { return (kc ? kbeg : 0) + min(t, T - 1) * BK; };
+  TileWork<A_KC, B_KC, BN> tw(p);
+  const int flags = tile_scales<BN>(p, sexp, sw, tw.row0, tw.col0, tid);
+  tw.bind(p);
 
   using LA = Loader<BM, AM>;
   using LB = Loader<BN, BMODE>;
@@ -792,18 +662,18 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
   lb[0].init_exp(sexp + BM, tid);
   lb[1].init_exp(sexp + BM, tid);
 
-  if (T > 0) {
-    la[0].load(rsA, p.lda, vra, kk(0, A_KC), tid);
-    lb[0].load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
-    la[0].template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
-    lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+  if (tw.T > 0) {
+    la[0].load(tw.rsA, p.lda, tw.vra, tw.kk(0, A_KC), tid);
+    lb[0].load(tw.rsB, p.ldb, tw.vrb, tw.kk(0, B_KC), tid);
+    la[0].template store<A_PLANE, RAG>(lds, tid, tw.T == 1 ? tw.klast : BK, m1);
+    lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, tw.T == 1 ? tw.klast : BK, m1);
     // tiles 1, 2 into sets 1, 0 (as at every later loop entry)
     __builtin_amdgcn_sched_barrier(0);
-    la[1].load(rsA, p.lda, vra, kk(1, A_KC), tid);
-    lb[1].load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
+    la[1].load(tw.rsA, p.lda, tw.vra, tw.kk(1, A_KC), tid);
+    lb[1].load(tw.rsB, p.ldb, tw.vrb, tw.kk(1, B_KC), tid);
     __builtin_amdgcn_sched_barrier(0);
-    la[0].load(rsA, p.lda, vra, kk(2, A_KC), tid);
-    lb[0].load(rsB, p.ldb, vrb, kk(2, B_KC), tid);
+    la[0].load(tw.rsA, p.lda, tw.vra, tw.kk(2, A_KC), tid);
+    lb[0].load(tw.rsB, p.ldb, tw.vrb, tw.kk(2, B_KC), tid);
     __syncthreads();
 
     const int ar = wm * 64, br = wn * 64;
@@ -836,32 +706,33 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_kernel(GemmF16Args p) {
     // step past T issues its clamped loads too, so every path issues the
     // same loads and each split waits only for its own tile)
     auto step = [&](int t, LA &lan, LB &lbn) {
-      if (t < T) {
+      if (t < tw.T) {
         const char *buf = lds + (t & 1) * BUF;
         char *nA = lds + ((t + 1) & 1) * BUF;
-        const int kv = t + 2 == T ? klast : BK;
+        const int kv = t + 2 == tw.T ? tw.klast : BK;
         half_step(buf, 0);
-        if (!late && t + 1 < T) {
+        if (!late && t + 1 < tw.T) {
           lan.template store<A_PLANE, RAG>(nA, tid, kv, m1);
           lbn.template store<B_PLANE, RAG>(nA + 2 * A_PLANE, tid, kv, m1);
         }
         half_step(buf, 1);
-        if (late && t + 1 < T) {
+        if (late && t + 1 < tw.T) {
           lan.template store<A_PLANE, RAG>(nA, tid, kv, m1);
           lbn.template store<B_PLANE, RAG>(nA + 2 * A_PLANE, tid, kv, m1);
         }
       }
-      lan.load(rsA, p.lda, vra, kk(t + 3, A_KC), tid);
-      lbn.load(rsB, p.ldb, vrb, kk(t + 3, B_KC), tid);
+      lan.load(tw.rsA, p.lda, tw.vra, tw.kk(t + 3, A_KC), tid);
+      lbn.load(tw.rsB, p.ldb, tw.vrb, tw.kk(t + 3, B_KC), tid);
       __syncthreads();
     };
-    for (int t = 0; t < T; t += 2) {
+    for (int t = 0; t < tw.T; t += 2) {
       step(t, la[1], lb[1]);
       step(t + 1, la[0], lb[0]);
     }
   }
 
-  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
+  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, tw.split, tw.whole, tw.row0, tw.col0, flags, tid,
+                                lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -906,26 +777,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
   const float m1 = kcnn::f16x3::opaque_m1();
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / Tile<BN>::WN, wn = wave % Tile<BN>::WN;
-  int split, tm, tn;
-  const bool whole = block_tile(p, split, tm, tn);
-  const int row0 = tm * BM, col0 = tn * BN;
-  const int kbeg = whole ? 0 : split * p.kps;
-  const int kend = whole ? p.K : min(p.K, kbeg + p.kps);
-  const int T = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
-  const int klast = kend - kbeg - (T - 1) * BK;
-
-  const float *baseA = A_KC ? p.A + (int64_t)row0 * p.lda : p.A + (int64_t)kbeg * p.lda + row0;
-  const float *baseB = B_KC ? p.B + (int64_t)col0 * p.ldb : p.B + (int64_t)kbeg * p.ldb + col0;
-  const int vra = p.M - row0, vrb = p.N - col0;
-  const int64_t endA = A_KC ? ((int64_t)(vra - 1) * p.lda + p.K) * 4
-                            : ((int64_t)(p.K - 1 - kbeg) * p.lda + vra) * 4;
-  const int64_t endB = B_KC ? ((int64_t)(vrb - 1) * p.ldb + p.K) * 4
-                            : ((int64_t)(p.K - 1 - kbeg) * p.ldb + vrb) * 4;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)baseA, (short)0, (int)(endA < 0x7fffffff ? endA : 0x7fffffff), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)baseB, (short)0, (int)(endB < 0x7fffffff ? endB : 0x7fffffff), 0x00020000);
-  auto kk = [&](int t, bool kc) { return (kc ? kbeg : 0) + min(t, T - 1) * BK; };
+  TileWork<A_KC, B_KC, BN> tw(p);
+  tw.bind(p);
 
   using LA = Loader<BM, AM>;
   using LB = Loader<BN, BMODE>;
@@ -974,20 +827,20 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
       if (n == L - 2) fb[1][1] = LB::frag(nb + 2 * A_PLANE + B_PLANE, br + 32, ns, lane);
       if (n == L - 1) fb[1][0] = LB::frag(nb + 2 * A_PLANE, br + 32, ns, lane);
     };
-    if (T > 0) {
-      la.load(rsA, p.lda, vra, kk(0, A_KC), tid);
-      lb.load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
+    if (tw.T > 0) {
+      la.load(tw.rsA, p.lda, tw.vra, tw.kk(0, A_KC), tid);
+      lb.load(tw.rsB, p.ldb, tw.vrb, tw.kk(0, B_KC), tid);
     }
     __builtin_amdgcn_sched_barrier(0);
-    flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
+    flags = tile_scales<BN>(p, sexp, sw, tw.row0, tw.col0, tid);
     la.init_exp(sexp, tid);
     lb.init_exp(sexp + BM, tid);
-    if (T > 0) {
-      la.template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
-      lb.template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+    if (tw.T > 0) {
+      la.template store<A_PLANE, RAG>(lds, tid, tw.T == 1 ? tw.klast : BK, m1);
+      lb.template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, tw.T == 1 ? tw.klast : BK, m1);
       __builtin_amdgcn_sched_barrier(0);
-      la.load(rsA, p.lda, vra, kk(1, A_KC), tid);
-      lb.load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
+      la.load(tw.rsA, p.lda, tw.vra, tw.kk(1, A_KC), tid);
+      lb.load(tw.rsB, p.ldb, tw.vrb, tw.kk(1, B_KC), tid);
       __syncthreads();
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl) fa[0][pl] = LA::frag(lds + pl * A_PLANE, ar, 0, lane);
@@ -1005,7 +858,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
       auto step = [&](int t) {
         const char *buf = lds + (t & 1) * BUF;
         char *nbuf = lds + ((t + 1) & 1) * BUF;
-        const int kv = t + 2 == T ? klast : BK;
+        const int kv = t + 2 == tw.T ? tw.klast : BK;
         uint32_t ph[4], pl[4];
         // phase A
 #pragma unroll
@@ -1014,12 +867,12 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
           if (n < LA::NPIECE) {
             la.template piece<A_PLANE, RAG>(nbuf, tid, n, kv, ph, pl, m1);
             if ((n + 1) % LA::PPP == 0)
-              la.load_part(rsA, p.lda, vra, kk(t + 2, A_KC), tid, n / LA::PPP);
+              la.load_part(tw.rsA, p.lda, tw.vra, tw.kk(t + 2, A_KC), tid, n / LA::PPP);
           } else if (n - LA::NPIECE < LB::NPIECE) {
             const int m = n - LA::NPIECE;
             lb.template piece<B_PLANE, RAG>(nbuf + 2 * A_PLANE, tid, m, kv, ph, pl, m1);
             if ((m + 1) % LB::PPP == 0)
-              lb.load_part(rsB, p.ldb, vrb, kk(t + 2, B_KC), tid, m / LB::PPP);
+              lb.load_part(tw.rsB, p.ldb, tw.vrb, tw.kk(t + 2, B_KC), tid, m / LB::PPP);
           }
           reads_after(n, buf, 0, buf, 1);
           __builtin_amdgcn_sched_barrier(0);
@@ -1036,7 +889,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
       };
       static_assert(LA::NPIECE + LB::NPIECE <= 6 * MI, "a piece per MFMA of phase A");
 #pragma unroll 1
-      for (int t = 0; t < T; ++t) step(t);
+      for (int t = 0; t < tw.T; ++t) step(t);
     }
   } else {
     LA la[2];
@@ -1063,24 +916,24 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
     // (the split needs both; the scales' loads and barriers then pass under
     // the tiles' latency: c2's data gradient 400 -> 381 us at K 1024 without
     // the scales at all)
-    if (T > 0) {
-      la[0].load(rsA, p.lda, vra, kk(0, A_KC), tid);
-      lb[0].load(rsB, p.ldb, vrb, kk(0, B_KC), tid);
-      la[1].load(rsA, p.lda, vra, kk(1, A_KC), tid);
-      lb[1].load(rsB, p.ldb, vrb, kk(1, B_KC), tid);
+    if (tw.T > 0) {
+      la[0].load(tw.rsA, p.lda, tw.vra, tw.kk(0, A_KC), tid);
+      lb[0].load(tw.rsB, p.ldb, tw.vrb, tw.kk(0, B_KC), tid);
+      la[1].load(tw.rsA, p.lda, tw.vra, tw.kk(1, A_KC), tid);
+      lb[1].load(tw.rsB, p.ldb, tw.vrb, tw.kk(1, B_KC), tid);
     }
     __builtin_amdgcn_sched_barrier(0);
-    flags = tile_scales<BN>(p, sexp, sw, row0, col0, tid);
+    flags = tile_scales<BN>(p, sexp, sw, tw.row0, tw.col0, tid);
     la[0].init_exp(sexp, tid);
     la[1].init_exp(sexp, tid);
     lb[0].init_exp(sexp + BM, tid);
     lb[1].init_exp(sexp + BM, tid);
-    if (T > 0) {
-      la[0].template store<A_PLANE, RAG>(lds, tid, T == 1 ? klast : BK, m1);
-      lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, T == 1 ? klast : BK, m1);
+    if (tw.T > 0) {
+      la[0].template store<A_PLANE, RAG>(lds, tid, tw.T == 1 ? tw.klast : BK, m1);
+      lb[0].template store<B_PLANE, RAG>(lds + 2 * A_PLANE, tid, tw.T == 1 ? tw.klast : BK, m1);
       __builtin_amdgcn_sched_barrier(0);
-      la[0].load(rsA, p.lda, vra, kk(2, A_KC), tid);
-      lb[0].load(rsB, p.ldb, vrb, kk(2, B_KC), tid);
+      la[0].load(tw.rsA, p.lda, tw.vra, tw.kk(2, A_KC), tid);
+      lb[0].load(tw.rsB, p.ldb, tw.vrb, tw.kk(2, B_KC), tid);
       __syncthreads();
 #pragma unroll
       for (int r = 0; r < 8; ++r) read_frag(lds, 0, r, fa0, fb0);
@@ -1094,7 +947,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
         const char *buf = lds + (t & 1) * BUF;
         char *nbuf = lds + ((t + 1) & 1) * BUF;
         constexpr bool more = decltype(more_c)::value;
-        const int kv = t + 2 == T ? klast : BK;
+        const int kv = t + 2 == tw.T ? tw.klast : BK;
         uint32_t ph[4], pl[4];
         // phase A
 #pragma unroll
@@ -1114,19 +967,19 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
 #pragma unroll
         for (int n = 0; n < 12; ++n) {
           mfma_n(n, fa1, fb1);
-          if (n == 1) lan.load(rsA, p.lda, vra, kk(t + 3, A_KC), tid);
-          if (n == 3) lbn.load(rsB, p.ldb, vrb, kk(t + 3, B_KC), tid);
+          if (n == 1) lan.load(tw.rsA, p.lda, tw.vra, tw.kk(t + 3, A_KC), tid);
+          if (n == 3) lbn.load(tw.rsB, p.ldb, tw.vrb, tw.kk(t + 3, B_KC), tid);
           if (more && n >= 2 && n < 10) read_frag(nbuf, 0, n - 2, fa0, fb0);
           __builtin_amdgcn_sched_barrier(0);
         }
       };
       int t = 0;
       // every step of the loop has a successor; the last one or two after it
-      for (; t + 2 < T; t += 2) {
+      for (; t + 2 < tw.T; t += 2) {
         step(t, la[1], lb[1], std::true_type{});
         step(t + 1, la[0], lb[0], std::true_type{});
       }
-      if (t + 1 < T) {
+      if (t + 1 < tw.T) {
         step(t, la[1], lb[1], std::true_type{});
         step(t + 1, la[0], lb[0], std::false_type{});
       } else {
@@ -1135,743 +988,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_f16x3_fast_kernel(GemmF16Args p) {
     }
   }
 
-  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, split, whole, row0, col0, flags, tid, lds);
-}
-
-// Max |x| and min nonzero |x| per row or per column of a pitched fp32 matrix,
-// as the bit patterns of |x| (unsigned order = magnitude order, Inf / NaN
-// above every finite value; max and min are order-independent, so the
-// results are deterministic), and for a spread group (f16-split.h: an
-// element far enough below the max to lose low bits, which the GEMM's store
-// then checks, tile_epilogue) the count of its elements held only to 2^-25
-// (an integer: deterministic).  A group set's statistics block is
-// [max[n], min[n], cnt[n]] (n groups): max[i] sets the group's f16x3 scale,
-// min[i] (0: no nonzero element) says whether the group is spread, cnt[i]
-// (0 unless spread here) sizes its check.  The check is sound for any count
-// that covers the group's small elements (each is held to 2^-25, spread or
-// not), so a producer may also count them in a group that is not spread
-// (the pooled output's columns, pool-stats.h): that only adds checks.  The
-// min is taken as min(|x| - 1) in wrapping unsigned arithmetic, so a zero
-// (0 - 1 = 0xffffffff) never wins, then + 1.
-// A GEMM needs op(A)'s rows and op(B)'s columns; both operands' statistics
-// go in one launch (stats_kernel: blocks [0, a.blocks) for A, then B's) and
-// one more (stats_finalize_kernel) when either is per column:
-//  rows, cols >= 2048: a block per row (thread t reads float4 t + 256 i,
-//    four in flight), a wave reduction and an LDS step;
-//  rows, shorter rows: a wave per row;
-//  columns: block (cb, rc) covers 1024 columns (4 per thread) of a chunk of
-//    rows (8 in flight) and stores its column maxima and minima as partial
-//    rc; the finalize takes the maxima / minima over the chunks (64 columns
-//    x 4 chunk groups per block, combined through LDS).
-struct StatOp {
-  const float *X;
-  uint32_t *out;   // the statistics block [max, min, cnt], per row (mode 0) or column (1)
-  uint32_t *part;  // mode 1: [2][rbk][cols] partials (maxima, then minima - 1)
-  int rows, cols, ld, mode, vec;
-  int blocks;      // of stats_kernel
-  int rpb;         // mode 0: rows per block (4: a wave each; 1: a block)
-  int cb, rbk, rb; // mode 1: column blocks, row chunks, rows per chunk
-  int fblocks;     // mode 1: blocks of stats_finalize_kernel
-  uint32_t *clear; // nullable: two words stats_kernel sets to 0 (a consumer's counters)
-};
-__device__ __forceinline__ const float *X_row(const StatOp &o, int r) {
-  return o.X + (int64_t)r * o.ld;
-}
-
-// running max |x| (m) and min (|x| - 1) (n) over a float4
-__device__ __forceinline__ void mm4(uint32_t &m, uint32_t &n, float4 q) {
-  const uint32_t a = __float_as_uint(q.x) & 0x7fffffffu, b = __float_as_uint(q.y) & 0x7fffffffu,
-                 c = __float_as_uint(q.z) & 0x7fffffffu, d = __float_as_uint(q.w) & 0x7fffffffu;
-  m = max(max(m, a), max(max(b, c), d));
-  n = min(min(n, a - 1u), min(min(b - 1u, c - 1u), d - 1u));
-}
-__device__ __forceinline__ void mm1(uint32_t &m, uint32_t &n, float x) {
-  const uint32_t a = __float_as_uint(x) & 0x7fffffffu;
-  m = max(m, a);
-  n = min(n, a - 1u);
-}
-
-// the nonzero |x| of row r below bound (a spread row's count; sweep of
-// stats_rows' shape)
-__device__ __forceinline__ uint32_t count_small_row(const StatOp &o, const float *x, float bound,
-                                                    int c, int step) {
-  uint32_t n = 0;
-  for (; c < o.cols; c += step)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (c + i < o.cols) {
-        const float a = fabsf(x[c + i]);
-        n += (a < bound && a != 0.0f) ? 1u : 0u;
-      }
-  return n;
-}
-
-// A row held in registers by the sweep (RV float4 per thread: up to 18432
-// floats per block row, 4608 per wave row), so that a spread row counts its
-// small elements without a second read (c5's C3 input and output derivative
-// rows are 18432 floats, and the derivative's frames are all spread: a
-// second read doubled that pass, 83 us per call)
-constexpr int RV = 18;
-__device__ __forceinline__ void stats_rows(const StatOp &o, int blk, uint32_t *red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool wide = o.rpb == 1;
-  const int r = wide ? blk : blk * 4 + wave;
-  if (r >= o.rows) return;  // (wide: uniform over the block)
-  const float *x = X_row(o, r);
-  const int step = wide ? 1024 : 256;  // floats per sweep of the row
-  const int c0 = (wide ? threadIdx.x : lane) * 4;
-  const bool held = o.vec && o.cols <= RV * step;  // uniform
-  float4 q[RV];
-  uint32_t m = 0, n = 0xffffffffu;
-  if (held) {  // every load in flight at once; past the row: zeros (never max, min or small)
-#pragma unroll
-    for (int j = 0; j < RV; ++j) {
-      const int c = c0 + j * step;
-      if (c + 4 <= o.cols) {
-        q[j] = *reinterpret_cast<const float4 *>(x + c);
-      } else {
-        q[j].x = c < o.cols ? x[c] : 0.0f;
-        q[j].y = c + 1 < o.cols ? x[c + 1] : 0.0f;
-        q[j].z = c + 2 < o.cols ? x[c + 2] : 0.0f;
-        q[j].w = 0.0f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RV; ++j) mm4(m, n, q[j]);
-  } else {
-    int c = c0;
-    if (o.vec) {
-      for (; c + 3 * step + 4 <= o.cols; c += 4 * step) {
-        float4 v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float4 *>(x + c + j * step);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mm4(m, n, v[j]);
-      }
-      for (; c + 4 <= o.cols; c += step) mm4(m, n, *reinterpret_cast<const float4 *>(x + c));
-    }
-    for (; c < o.cols; c += step)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (c + i < o.cols) mm1(m, n, x[c + i]);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    m = max(m, (uint32_t)__shfl_xor((int)m, d));
-    n = min(n, (uint32_t)__shfl_xor((int)n, d));
-  }
-  if (wide) {  // the block's maxima / minima through LDS, to every thread
-    if (lane == 0) {
-      red[wave] = m;
-      red[4 + wave] = n;
-    }
-    __syncthreads();
-    m = max(max(red[0], red[1]), max(red[2], red[3]));
-    n = min(min(red[4], red[5]), min(red[6], red[7]));
-  }
-  // a spread row (f16-split.h) counts its small elements (from the registers,
-  // or a second sweep of the row from L2); every other row's count is 0
-  uint32_t cnt = 0;
-  if (kcnn::f16x3::spread(m, n + 1u)) {  // uniform over the wave (the block)
-    const float bound = kcnn::f16x3::small_bound(m);
-    if (held) {
-      auto small = [&](float v) { return (fabsf(v) < bound && v != 0.0f) ? 1u : 0u; };
-#pragma unroll
-      for (int j = 0; j < RV; ++j)
-        cnt += small(q[j].x) + small(q[j].y) + small(q[j].z) + small(q[j].w);
-    } else {
-      cnt = count_small_row(o, x, bound, c0, step);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d);
-    if (wide) {
-      __syncthreads();  // (red's maxima read above)
-      if (lane == 0) red[8 + wave] = cnt;
-      __syncthreads();
-      cnt = red[8] + red[9] + red[10] + red[11];
-    }
-  }
-  if (wide ? threadIdx.x == 0 : lane == 0) {
-    o.out[r] = m;
-    o.out[o.rows + r] = n + 1u;
-    o.out[2 * (size_t)o.rows + r] = cnt;
-  }
-}
-
-__device__ __forceinline__ void stats_cols(const StatOp &o, int blk) {
-  const int cbi = blk % o.cb, rci = blk / o.cb;
-  const int c0 = cbi * 1024 + threadIdx.x * 4;
-  const int r0 = rci * o.rb, rend = min(o.rows, r0 + o.rb);
-  if (c0 >= o.cols) return;
-  const bool v4 = o.vec && c0 + 4 <= o.cols;
-  uint32_t cm[4] = {0u, 0u, 0u, 0u};
-  uint32_t cn[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-  auto load = [&](int r) {
-    const float *x = X_row(o, r) + c0;
-    if (v4) return *reinterpret_cast<const float4 *>(x);
-    float4 q;
-    q.x = x[0];
-    q.y = c0 + 1 < o.cols ? x[1] : 0.0f;
-    q.z = c0 + 2 < o.cols ? x[2] : 0.0f;
-    q.w = c0 + 3 < o.cols ? x[3] : 0.0f;
-    return q;
-  };
-  auto take = [&](float4 q) {
-    mm1(cm[0], cn[0], q.x);
-    mm1(cm[1], cn[1], q.y);
-    mm1(cm[2], cn[2], q.z);
-    mm1(cm[3], cn[3], q.w);
-  };
-  int r = r0;
-  for (; r + 8 <= rend; r += 8) {
-    float4 q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = load(r + j);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) take(q[j]);
-  }
-  for (; r < rend; ++r) take(load(r));
-  uint32_t *dst = o.part + (size_t)rci * o.cols + c0;
-  uint32_t *dsn = dst + (size_t)o.rbk * o.cols;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (c0 + i < o.cols) {
-      dst[i] = cm[i];
-      dsn[i] = cn[i];
-    }
-}
-
-// Up to three statistics passes in one launch (their blocks in order): a
-// GEMM's two operands, or the FC backward's output derivative (rows and
-// columns) and weight columns (kl_gemm_stats3)
-struct StatOps {
-  StatOp o[3];
-  // a fused pool's pending column statistics (pool-stats-dev.h): pcx x pcy
-  // colmax blocks after the ops' blocks in stats_kernel, pcn count blocks
-  // after the finalize blocks in stats_finalize_kernel (0: none)
-  PoolColDeferred pc;
-  int pcx, pcy, pcn;
-};
-// the op of block `blk` among the ops' `count(o)` blocks, and its block index there
-template <typename Count>
-__device__ __forceinline__ int pick_op(const StatOps &s, int blk, Count count, int &local) {
-  const int n0 = count(s.o[0]), n1 = count(s.o[1]);
-  if (blk < n0) { local = blk; return 0; }
-  if (blk < n0 + n1) { local = blk - n0; return 1; }
-  local = blk - n0 - n1;
-  return 2;
-}
-__host__ __device__ inline int ncount_blocks(const StatOp &o);
-__host__ __device__ inline int nfinal_blocks(const StatOp &o) {
-  return o.mode == 1 && o.blocks ? o.fblocks : 0;
-}
-
-__global__ __launch_bounds__(256) void stats_kernel(StatOps s) {
-  __shared__ uint32_t red[12];
-  if (s.o[0].clear && blockIdx.x == 0 && threadIdx.x < 2) s.o[0].clear[threadIdx.x] = 0u;
-  const int nb3 = s.o[0].blocks + s.o[1].blocks + s.o[2].blocks;
-  if ((int)blockIdx.x >= nb3) {  // (uniform) a pool's column maxima
-    const int k = blockIdx.x - nb3;
-    pool_colmax_block(s.pc.pcol, s.pc.nblk, s.pc.npool, s.pc.colblk, k % s.pcx, k / s.pcx);
-    return;
-  }
-  int blk;
-  const int w = pick_op(s, blockIdx.x, [](const StatOp &o) { return o.blocks; }, blk);
-  const StatOp &o = s.o[w];  // (uniform)
-  if (o.mode == 0) stats_rows(o, blk, red);
-  else stats_cols(o, blk);
-}
-
-// The column maxima / minima over the partials (64 columns per block, 4
-// groups of partials through LDS); the counts zeroed for stats_count_kernel.
-__global__ __launch_bounds__(256) void stats_finalize_kernel(StatOps s) {
-  __shared__ uint32_t red[2][4][64];
-  __shared__ PoolCountSmem psm;
-  const int nf3 = nfinal_blocks(s.o[0]) + nfinal_blocks(s.o[1]) + nfinal_blocks(s.o[2]);
-  if ((int)blockIdx.x >= nf3) {  // (uniform) a pool's small elements, after its maxima
-    pool_count_block(s.pc.P, s.pc.ps, s.pc.R, s.pc.npool, s.pc.vec, s.pc.rowblk, s.pc.colblk,
-                     blockIdx.x - nf3, s.pcn, psm);
-    return;
-  }
-  int blk;
-  const StatOp &o = s.o[pick_op(s, blockIdx.x, [](const StatOp &q) { return nfinal_blocks(q); }, blk)];
-  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int c = blk * 64 + lane;
-  uint32_t m = 0, n = 0xffffffffu;
-  if (c < o.cols) {
-    const uint32_t *pm = o.part + c, *pn = o.part + (size_t)o.rbk * o.cols + c;
-    int q = grp;
-    for (; q + 28 < o.rbk; q += 32) {  // eight maxima and eight minima in flight
-      uint32_t a[8], b[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        a[j] = pm[(size_t)(q + 4 * j) * o.cols];
-        b[j] = pn[(size_t)(q + 4 * j) * o.cols];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        m = max(m, a[j]);
-        n = min(n, b[j]);
-      }
-    }
-    for (; q < o.rbk; q += 4) {
-      m = max(m, pm[(size_t)q * o.cols]);
-      n = min(n, pn[(size_t)q * o.cols]);
-    }
-  }
-  red[0][grp][lane] = m;
-  red[1][grp][lane] = n;
-  __syncthreads();
-  m = max(max(red[0][0][lane], red[0][1][lane]), max(red[0][2][lane], red[0][3][lane]));
-  n = min(min(red[1][0][lane], red[1][1][lane]), min(red[1][2][lane], red[1][3][lane]));
-  if (grp == 0 && c < o.cols) {
-    o.out[c] = m;
-    o.out[o.cols + c] = n + 1u;
-    o.out[2 * (size_t)o.cols + c] = 0;
-  }
-}
-
-// The spread columns' counts (f16-split.h) after the finalize: block (cb,
-// rc) takes 64 columns x a chunk of 64 rows, leaves at once unless one of
-// its columns is spread (rare), and otherwise reads its rows' 64-column
-// segments (one coalesced 256-B row piece per wave and row) and adds each
-// spread column's count of small elements by an integer atomic (exact and
-// order-independent).
-constexpr int CNT_ROWS = 64;
-__host__ __device__ inline int ncount_blocks(const StatOp &o) {
-  return o.mode == 1 && o.blocks ? ((o.cols + 63) / 64) * ((o.rows + CNT_ROWS - 1) / CNT_ROWS) : 0;
-}
-__global__ __launch_bounds__(256) void stats_count_kernel(StatOps s) {
-  int blk;
-  const StatOp &o = s.o[pick_op(s, blockIdx.x, [](const StatOp &q) { return ncount_blocks(q); }, blk)];
-  const int ncb = (o.cols + 63) / 64;
-  const int cb = blk % ncb, rc = blk / ncb;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = cb * 64 + lane;
-  bool spr = false;
-  float bound = 0.0f;
-  if (c < o.cols) {
-    const uint32_t mx = o.out[c];
-    spr = kcnn::f16x3::spread(mx, o.out[o.cols + c]);
-    if (spr) bound = kcnn::f16x3::small_bound(mx);
-  }
-  if (__ballot(spr) == 0) return;  // block-uniform (the same columns in every wave)
-  const int r0 = rc * CNT_ROWS, r1 = min(o.rows, r0 + CNT_ROWS);
-  uint32_t cnt = 0;
-  if (spr) {  // the wave's CNT_ROWS / 4 rows loaded together
-    float v[CNT_ROWS / 4];
-#pragma unroll
-    for (int i = 0; i < CNT_ROWS / 4; ++i) {
-      const int r = r0 + wave + 4 * i;
-      v[i] = r < r1 ? fabsf(X_row(o, r)[c]) : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < CNT_ROWS / 4; ++i) cnt += (v[i] < bound && v[i] != 0.0f) ? 1u : 0u;
-  }
-  if (cnt) atomicAdd(o.out + 2 * (size_t)o.cols + c, cnt);
-}
-
-// a statistics pass over X (rows x cols, pitch ld): mode 0 per row, 1 per
-// column (partials at part, stat_part_words of them)
-StatOp stat_op(const float *X, int rows, int cols, int ld, int mode, uint32_t *out,
-               uint32_t *part) {
-  StatOp o{};
-  o.X = X; o.out = out; o.part = part;
-  o.rows = rows; o.cols = cols; o.ld = ld; o.mode = mode;
-  o.vec = ld % 4 == 0 && (uintptr_t)X % 16 == 0;
-  if (rows <= 0 || cols <= 0) return o;  // blocks 0
-  if (mode == 0) {
-    o.rpb = cols >= 2048 ? 1 : 4;
-    o.blocks = (rows + o.rpb - 1) / o.rpb;
-  } else {
-    o.cb = (cols + 1023) / 1024;
-    // about 1024 blocks of at least 16 rows, at most 256 row chunks
-    o.rbk = std::max(1, std::min(256, std::min((rows + 15) / 16, (1024 + o.cb - 1) / o.cb)));
-    o.rb = (rows + o.rbk - 1) / o.rbk;
-    o.rbk = (rows + o.rb - 1) / o.rb;
-    o.blocks = o.cb * o.rbk;
-    o.fblocks = (cols + 63) / 64;
-  }
-  return o;
-}
-size_t stat_part_words(int rows, int cols, int mode) {
-  if (mode == 0) return 0;
-  const StatOp o = stat_op(nullptr, rows, cols, cols, 1, nullptr, nullptr);
-  return 2 * (size_t)o.rbk * cols;
-}
-int stats_launch3(const StatOps &ops, hipStream_t st) {
-  // empty operands: maxima 0 (no scale), minima 0 (no nonzero element)
-  for (const StatOp &o : ops.o)
-    if (o.blocks == 0 && o.out) {
-      const size_t n = o.mode == 0 ? (size_t)std::max(o.rows, 0) : (size_t)std::max(o.cols, 0);
-      if (n && hipMemsetAsync(o.out, 0, 3 * n * 4, st) != hipSuccess) return (int)hipGetLastError();
-    }
-  int nb = 0, nf = 0, nc = 0;
-  for (const StatOp &o : ops.o) {
-    nb += o.blocks;
-    nf += nfinal_blocks(o);
-    nc += ncount_blocks(o);
-  }
-  nb += ops.pcx * ops.pcy;
-  nf += ops.pcn;
-  if (nb == 0) return 0;
-  hipLaunchKernelGGL(stats_kernel, dim3(nb), dim3(256), 0, st, ops);
-  int rc = kcnn::launch_status();
-  if (rc || nf == 0) return rc;
-  hipLaunchKernelGGL(stats_finalize_kernel, dim3(nf), dim3(256), 0, st, ops);
-  rc = kcnn::launch_status();
-  if (rc || nc == 0) return rc;
-  hipLaunchKernelGGL(stats_count_kernel, dim3(nc), dim3(256), 0, st, ops);
-  return kcnn::launch_status();
-}
-int stats_launch(const StatOp &a, const StatOp &b, hipStream_t st) {
-  StatOps ops{};
-  ops.o[0] = a;
-  ops.o[1] = b;
-  ops.o[2] = StatOp{};
-  return stats_launch3(ops, st);
-}
-
-// C = alpha * sum_s part[s] + beta * C, the splits added in increasing s
-// (slab rows padded to np4 = N rounded up to 4: 16-B reads; a quad's columns
-// past N are not stored); elements of an Inf / NaN row or column are the
-// epilogue's (split 0).  The spread check of tile_epilogue on the summed
-// value (unscaled: the threshold times 2^-(s_row + s_col)); a rejected
-// element is not stored.  A wave with at most REJ_LOCAL of them recomputes
-// them itself (wave_dot); one with more flags its 64 quads (rflag) for
-// gemm_f16x3_fixup_kernel, which spreads such groups over the whole GPU: a
-// spread row rejects hundreds of elements of one row, and one wave's
-// wave_dots in series took milliseconds (nnet.config's weight gradients).
-// A call launched without the fix-up (fix_local) recomputes such a group
-// itself, in the order the fix-up would have used: the quarter order
-// (quarter_sums) when the call's `rows` holds, wave_dot when not.  So a
-// rejected element's bits depend on the operands and on whether its group of
-// 64 quads exceeds REJ_LOCAL, never on which kernel recomputed it.  Every pass of a wave keeps all 64 lanes (a quad past the end rejects
-// nothing): wave_dot spreads K over the whole wave.
-constexpr int REJ_LOCAL = 4;
-__device__ __forceinline__ uint32_t reduce_quad(const GemmF16Args &p, int64_t e, int nq, int np4,
-                                                int64_t plane, int &r, int &c, bool store) {
-  const int N = p.N;
-  r = (int)(e / nq);
-  c = (int)(e - (int64_t)r * nq) * 4;
-  // every load of the quad issued before the first test: the slabs, the
-  // row's statistics and the four columns' (one 16-B load each when the
-  // blocks allow; a column past N reads as non-finite, i.e. not stored)
-  const float *q = p.part + (int64_t)r * np4 + c;
-  float4 v = *reinterpret_cast<const float4 *>(q);
-  float4 w = p.ksplit > 1 ? *reinterpret_cast<const float4 *>(q + plane) : v;
-  const uint32_t ar = p.amax[r], cr = p.acnt[r];
-  uint32_t bm[4], cc[4];
-  if (p.bvec) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(p.bmax + c);
-    const uint4 y = *reinterpret_cast<const uint4 *>(p.bcnt + c);
-    bm[0] = x.x; bm[1] = x.y; bm[2] = x.z; bm[3] = x.w;
-    cc[0] = y.x; cc[1] = y.y; cc[2] = y.z; cc[3] = y.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      bm[i] = c + i < N ? p.bmax[c + i] : NONFINITE;
-      cc[i] = c + i < N ? p.bcnt[c + i] : 0u;
-    }
-  }
-  // the bias quad too, and the momentum update's W and prev quads (the 16-B
-  // paths' operands, loaded here, not after the tests: one memory round trip
-  // per quad instead of two; host: the update's rows 16-B aligned)
-  float4 w4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q4 = w4;
-  float4 *wp = nullptr, *qp = nullptr;
-  if (p.mom.W && store) {
-    wp = reinterpret_cast<float4 *>(p.mom.W + (int64_t)r * p.mom.ldw + c);
-    qp = reinterpret_cast<float4 *>(p.mom.prev + (int64_t)r * p.mom.ldp + c);
-    if (c + 4 <= N) {
-      w4 = *wp;
-      q4 = *qp;
-    }
-  }
-  float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (p.bias && store) {
-    if (c + 4 <= N && ((uintptr_t)p.bias & 15) == 0) {
-      const float4 b4 = *reinterpret_cast<const float4 *>(p.bias + c);
-      bv[0] = b4.x; bv[1] = b4.y; bv[2] = b4.z; bv[3] = b4.w;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) bv[i] = c + i < N ? p.bias[c + i] : 0.0f;
-    }
-  }
-  if (p.ksplit > 1) {
-    v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    for (int k = 2; k < p.ksplit; ++k) {
-      w = *reinterpret_cast<const float4 *>(q + k * plane);
-      v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    }
-  }
-  if (ar >= NONFINITE) return 0;
-  const float sv[4] = {v.x, v.y, v.z, v.w};
-  // the counts are 0 unless a group is spread, so one test skips the check
-  // (an all-zero row: its products are exactly 0, no check)
-  const bool any = (cr | cc[0] | cc[1] | cc[2] | cc[3]) != 0 && ar != 0;
-  float *o = p.C + (int64_t)r * p.ldc + c;
-  const bool fin = max(max(bm[0], bm[1]), max(bm[2], bm[3])) < NONFINITE;
-  if (p.mom.W && !any && fin) {  // the fused momentum update, 16-B (host: aligned)
-    if (store) {
-      const MomentumEpi &m = p.mom;
-      kcnn::momentum_step(p.alpha * sv[0], q4.x, w4.x, m.momentum, m.a_wd, m.a_g);
-      kcnn::momentum_step(p.alpha * sv[1], q4.y, w4.y, m.momentum, m.a_wd, m.a_g);
-      kcnn::momentum_step(p.alpha * sv[2], q4.z, w4.z, m.momentum, m.a_wd, m.a_g);
-      kcnn::momentum_step(p.alpha * sv[3], q4.w, w4.w, m.momentum, m.a_wd, m.a_g);
-      *qp = q4;
-      *wp = w4;
-    }
-    return 0;
-  }
-  if (!p.mom.W && !any && fin && ((p.ldc & 3) | ((uintptr_t)p.C & 15)) == 0) {
-    if (store) {  // one 16-B store (the same values)
-      float4 ov = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (p.beta != 0.0f) ov = *reinterpret_cast<const float4 *>(o);
-      const float oi[4] = {ov.x, ov.y, ov.z, ov.w};
-      float wv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        wv[i] = p.beta == 0.0f ? p.alpha * sv[i] : p.alpha * sv[i] + p.beta * oi[i];
-        if (p.bias) wv[i] += bv[i];
-      }
-      *reinterpret_cast<float4 *>(o) = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    }
-    return 0;
-  }
-  // the check's thresholds (0: no check) of the four columns
-  float thr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (any) {
-    const int er = scale_exp(ar);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      // (an all-zero column: exact, no check)
-      if (bm[i] >= NONFINITE || bm[i] == 0 || (cr | cc[i]) == 0) continue;
-      thr[i] = __builtin_amdgcn_ldexpf(
-          kcnn::f16x3::spread_weight(cr) + kcnn::f16x3::spread_weight(cc[i]),
-          -(er + scale_exp(bm[i])));
-    }
-  }
-  uint32_t rej = 0;  // bit i: column c + i is rejected
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (bm[i] >= NONFINITE) continue;  // (and columns past N)
-    if (thr[i] != 0.0f && !(fabsf(sv[i]) >= thr[i])) {
-      rej |= 1u << i;
-      continue;
-    }
-    if (store) emit(p, r, c + i, sv[i]);
-  }
-  return rej;
-}
-
-// A quarter of K (quarter q of 4: k in [q kq, min(K, (q + 1) kq)), kq = K / 4
-// rounded up) of the W sums of C[r][c .. c + W - 1], op(B) row-contiguous
-// (W = 4: a quad by 16-B loads of op(B)'s rows; W = 1: one element): for
-// each column, products k0 + 4 i + j go to accumulator j in increasing k
-// over the quarter's whole multiples of FIX_DEPTH, the rest to accumulator 0,
-// and the accumulators are added as (0 + 1) + (2 + 3).  A column's sum does
-// not depend on W, nor on DEPTH, which is only how many k steps are loaded at
-// once (the same products added in the same order).
-constexpr int FIX_DEPTH = 16;
-template <int W>
-__device__ __forceinline__ void load_cols(const float *q, float (&y)[W]) {
-  if constexpr (W == 4) {
-    const float4 t = *reinterpret_cast<const float4 *>(q);
-    y[0] = t.x; y[1] = t.y; y[2] = t.z; y[3] = t.w;
-  } else {
-    static_assert(W == 1, "a quad or one element");
-    y[0] = *q;
-  }
-}
-template <int DEPTH, int W>
-__device__ __forceinline__ void quarter_sums(const float *A, int lda, const float *B, int ldb,
-                                             int K, bool a_kc, int r, int c, int quarter,
-                                             float (&q)[W]) {
-  static_assert(DEPTH % 4 == 0 && FIX_DEPTH % DEPTH == 0, "accumulator j takes k = k0 + 4 i + j");
-  const int kq = (K + 3) >> 2;
-  const int k0 = quarter * kq, k1 = min(K, k0 + kq);
-  const int km = k0 + max(k1 - k0, 0) / FIX_DEPTH * FIX_DEPTH;
-  const int64_t sa = a_kc ? 1 : lda;
-  const float *qa = a_kc ? A + (int64_t)r * lda + k0 : A + (int64_t)k0 * lda + r;
-  const float *qb = B + (int64_t)k0 * ldb + c;
-  float acc[4][W];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[i][j] = 0.0f;
-  int k = k0;
-#pragma unroll 1
-  for (; k < km; k += DEPTH) {
-    float x[DEPTH];
-    float y[DEPTH][W];
-#pragma unroll
-    for (int i = 0; i < DEPTH; ++i) {
-      x[i] = qa[i * sa];
-      load_cols<W>(qb + (int64_t)i * ldb, y[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < DEPTH; ++i)
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[i & 3][j] = fmaf(x[i], y[i][j], acc[i & 3][j]);
-    qa += DEPTH * sa;
-    qb += (int64_t)DEPTH * ldb;
-  }
-#pragma unroll 1
-  for (; k < k1; ++k) {
-    const float x = *qa;
-    float y[W];
-    load_cols<W>(qb, y);
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[0][j] = fmaf(x, y[j], acc[0][j]);
-    qa += sa;
-    qb += ldb;
-  }
-#pragma unroll
-  for (int j = 0; j < W; ++j) q[j] = (acc[0][j] + acc[1][j]) + (acc[2][j] + acc[3][j]);
-}
-// loads in flight per lane in the reduce's own quarter sums (fix_local), which
-// take one element at a time: the kernel runs in every split-K call and is
-// bound by its slab reads, so the rarely taken path must not raise its
-// register count
-constexpr int LOCAL_DEPTH = 4;
-
-__global__ __launch_bounds__(256) void gemm_f16x3_reduce_kernel(GemmF16Args p, int a_kc,
-                                                                int b_kc, int rows) {
-  const int np4 = (p.N + 3) & ~3, nq = np4 >> 2;
-  const int64_t total = (int64_t)p.M * nq;
-  const int64_t plane = (int64_t)p.M * np4;
-  const int lane = threadIdx.x & 63;
-  // the bound is total rounded up to the wave's 64 quads, so a pass keeps or
-  // drops a whole wave (the last group's lanes past total stay, on quad 0
-  // with no rejection: wave_dot below needs all 64), and every group of 64
-  // quads gets its flag written
-  const int64_t padded = (total + 63) & ~(int64_t)63;
-  for (int64_t el = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; el < padded;
-       el += (int64_t)gridDim.x * blockDim.x) {
-    // (a whole tile's quads were stored by its workgroup: no slabs, no
-    // rejections.  One index for both uses below: the 64-bit division is
-    // then computed once)
-    const bool inside = el < total;
-    const int64_t e = inside ? el : 0;
-    int r = (int)(e / nq), c = (int)(e - (int64_t)r * nq) * 4;
-    const bool valid = inside && in_split_tile(p, r, c);
-    uint32_t rej = valid ? reduce_quad(p, e, nq, np4, plane, r, c, true) : 0u;
-    // the wave's rejections
-    const int n = __builtin_popcountll(__ballot(rej & 1)) + __builtin_popcountll(__ballot(rej & 2)) +
-                  __builtin_popcountll(__ballot(rej & 4)) + __builtin_popcountll(__ballot(rej & 8));
-    const bool over = n > REJ_LOCAL;
-    const bool defer = over && !p.fix_local;
-    if (lane == 0) {
-      p.rflag[el >> 6] = defer ? 1u : 0u;
-      if (defer) p.rflag[(total + 63) >> 6] = p.gen;
-      if (over && p.fix_report) *p.fix_report = 1u;
-    }
-    // (expected: what follows is rare, and the register allocator should
-    // not spill the pass's own values for it)
-    if (__builtin_expect(n == 0 || defer, 1)) continue;
-    if (over && rows) {
-      // the fix-up's sums of this group, each lane its own quad's rejected
-      // elements in turn: the four quarters, added in quarter order (the
-      // fix-up's wave order, a left fold).  The shape enters through a
-      // barrier, so that this rare path's invariants are formed here and do
-      // not take scalar registers from every pass of every call.
-      int K = p.K, lda = p.lda, ldb = p.ldb, akc = a_kc;
-      asm volatile("" : "+s"(K), "+s"(lda), "+s"(ldb), "+s"(akc));
-#pragma unroll 1
-      for (; rej; rej &= rej - 1) {
-        const int col = c + __builtin_ctz(rej);
-        float s[1], t[1];
-        quarter_sums<LOCAL_DEPTH, 1>(p.A, lda, p.B, ldb, K, akc != 0, r, col, 0, s);
-#pragma unroll 1
-        for (int w = 1; w < 4; ++w) {
-          quarter_sums<LOCAL_DEPTH, 1>(p.A, lda, p.B, ldb, K, akc != 0, r, col, w, t);
-          s[0] += t[0];
-        }
-        emit(p, r, col, s[0]);
-      }
-      continue;
-    }
-    fix_rejected(p, a_kc != 0, b_kc != 0, rej, lane, [&](int l, int bit, int &row, int &col) {
-      row = __builtin_amdgcn_readlane(r, l);
-      col = __builtin_amdgcn_readlane(c, l) + bit;
-    });
-  }
-}
-
-// The flagged groups of 64 quads (gemm_f16x3_reduce_kernel), one per block
-// at a time: slot s = t G + b for thread t of block b (G blocks), so the
-// consecutive groups of one spread row go to different blocks.  A group's
-// rejections are found again (reduce_quad, not stored) and recomputed in fp32:
-//  - op(B) row-contiguous with 16-B rows (`rows`): every lane its quad's four sums, the
-//    block's four waves each over a quarter of K (quarter_sums: 16-B loads of
-//    op(B)'s rows, coalesced over the lanes; the lanes of one C row share
-//    op(A)'s element), the quarters added in wave order, the rejected
-//    elements stored;
-//  - otherwise: wave_dot per rejected element, the quads dealt to
-//    the waves by lane & 3.
-// Deterministic: the group's results do not depend on the block or order,
-// and they are the bits the reduce gives the group when the call runs
-// without this kernel (fix_local).
-// the fixup's grid: a flagged call's groups take the workgroups in turn
-// (c2's weight-gradient shape with 32 spread rows, 1452 groups: +925 us at
-// 128 workgroups, measured r05 by a one-off driver); an unflagged call exits at the
-// first load, and the launch costs the same 4.4 us at 128 or 1024
-constexpr int FIX_GRID = 1024;
-__global__ __launch_bounds__(256) void gemm_f16x3_fixup_kernel(GemmF16Args p, int a_kc,
-                                                               int b_kc, int rows) {
-  __shared__ int list[256];
-  __shared__ int nlist;
-  __shared__ float4 quarter[4][64];
-  const int np4 = (p.N + 3) & ~3, nq = np4 >> 2;
-  const int64_t total = (int64_t)p.M * nq;
-  const int64_t plane = (int64_t)p.M * np4;
-  const int64_t nslots = (total + 63) >> 6;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // nothing flagged in this call (the word is another call's number, or
-  // anything the workspace held: a stale match only costs the scan below)
-  if (p.rflag[nslots] != p.gen) return;
-  for (int64_t base = 0; base < nslots; base += (int64_t)gridDim.x * blockDim.x) {
-    if (threadIdx.x == 0) nlist = 0;
-    __syncthreads();
-    const int64_t slot = base + (int64_t)threadIdx.x * gridDim.x + blockIdx.x;
-    if (slot < nslots && p.rflag[slot] != 0) list[atomicAdd(&nlist, 1)] = (int)threadIdx.x;
-    __syncthreads();
-    const int n = nlist;
-    for (int j = 0; j < n; ++j) {
-      const int64_t e0 = (base + (int64_t)list[j] * gridDim.x + blockIdx.x) << 6;
-      const int64_t e = e0 + lane;
-      // (past C: row and column 0, whose loads below stay in bounds)
-      int r = e < total ? (int)(e / nq) : 0;
-      int c = e < total ? (int)(e - (int64_t)r * nq) * 4 : 0;
-      const bool valid = e < total && in_split_tile(p, r, c);
-      const uint32_t rej = valid ? reduce_quad(p, e, nq, np4, plane, r, c, false) : 0u;
-      if (!rows) {
-        const uint64_t mine = (lane & 3) == wave ? rej : 0u;
-        fix_rejected(p, a_kc != 0, b_kc != 0, mine, lane, [&](int l, int bit, int &row, int &col) {
-          row = __builtin_amdgcn_readlane(r, l);
-          col = __builtin_amdgcn_readlane(c, l) + bit;
-        });
-        __syncthreads();
-        continue;
-      }
-      // this wave's quarter of K for the lane's quad (r, c .. c + 3)
-      float q[4];
-      quarter_sums<FIX_DEPTH, 4>(p.A, p.lda, p.B, p.ldb, p.K, a_kc != 0, r, c, wave, q);
-      quarter[wave][lane] = make_float4(q[0], q[1], q[2], q[3]);
-      __syncthreads();
-      if (wave == 0 && rej) {
-        const float4 q0 = quarter[0][lane], q1 = quarter[1][lane], q2 = quarter[2][lane],
-                     q3 = quarter[3][lane];
-        const float v[4] = {((q0.x + q1.x) + q2.x) + q3.x, ((q0.y + q1.y) + q2.y) + q3.y,
-                            ((q0.z + q1.z) + q2.z) + q3.z, ((q0.w + q1.w) + q2.w) + q3.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (rej >> i & 1) emit(p, r, c + i, v[i]);
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-  }
+  tile_epilogue<A_KC, B_KC, BN>(p, sexp, sw, acc, tw.split, tw.whole, tw.row0, tw.col0, flags, tid,
+                                lds);
 }
 
 // The plan of a call: the tile, the split-K count and the whole tiles in
@@ -1940,33 +1058,17 @@ std::atomic<unsigned long long> g_tile_calls[2];  // launches on the narrow, the
 // the one-barrier fast kernel where no operand is LR (an LR operand's 16
 // loaded values per thread and K step spill there), on the plan's tile, else
 // the two-phase kernel on the narrow tile (bitwise the same C)
-template <int AM, int BMODE, bool RAG, int BN>
-void launch_fast(const GemmF16Args &a, unsigned blocks, hipStream_t st) {
-  constexpr int LDS_BYTES = Tile<BN>::LDS_BYTES;
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN>), dim3(blocks), dim3(NT),
-                     LDS_BYTES, st, a);
-}
 template <int AM, int BMODE, bool RAG>
 void launch_t(const GemmF16Args &a, unsigned blocks, hipStream_t st) {
+  using kcnn::launch_lds;
+  constexpr int NARROW_LDS = Tile<BN_NARROW>::LDS_BYTES, WIDE_LDS = Tile<BN_WIDE>::LDS_BYTES;
   if constexpr (AM != LR && BMODE != LR) {
-    if (a.bn == BN_WIDE) launch_fast<AM, BMODE, RAG, BN_WIDE>(a, blocks, st);
-    else launch_fast<AM, BMODE, RAG, BN_NARROW>(a, blocks, st);
+    if (a.bn == BN_WIDE)
+      launch_lds<&gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN_WIDE>, WIDE_LDS>(a, blocks, NT, st);
+    else
+      launch_lds<&gemm_f16x3_fast_kernel<AM, BMODE, RAG, BN_NARROW>, NARROW_LDS>(a, blocks, NT, st);
   } else {
-    constexpr int LDS_BYTES = Tile<BN_NARROW>::LDS_BYTES;
-    static bool attr = [] {
-      return hipFuncSetAttribute(
-                 reinterpret_cast<const void *>(&gemm_f16x3_kernel<AM, BMODE, RAG>),
-                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-    }();
-    (void)attr;
-    hipLaunchKernelGGL((gemm_f16x3_kernel<AM, BMODE, RAG>), dim3(blocks), dim3(NT), LDS_BYTES,
-                       st, a);
+    launch_lds<&gemm_f16x3_kernel<AM, BMODE, RAG>, NARROW_LDS>(a, blocks, NT, st);
   }
 }
 template <bool RAG>
@@ -1987,15 +1089,6 @@ void launch(int am, int bm, const GemmF16Args &a, unsigned blocks, hipStream_t s
   else launch_r<false>(am, bm, a, blocks, st);
 }
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-// the split-K workspace: the slabs, then the reduce's flags (one word per
-// 64 quads of C)
-size_t slab_bytes(int s, int M, int N) {
-  return align16(sizeof(float) * (size_t)s * M * ((N + 3) & ~3));
-}
-size_t flag_bytes(int M, int N) {
-  return align16(sizeof(uint32_t) * (((size_t)M * ((N + 3) / 4) + 63) / 64 + 1));
-}
 // (of the larger split count of the two tiles' plans: the workspace is sized
 // before the operands' alignment and the selector's value at the call are known)
 size_t partial_bytes(int M, int N, int K) {
@@ -2005,87 +1098,6 @@ size_t partial_bytes(int M, int N, int K) {
 
 }  // namespace
 
-extern "C" int kl_absmax_rows(const float *X, int rows, int cols, int ld, uint32_t *rmax,
-                              kcnn_stream_t stream) {
-  if (rows < 0 || cols < 0 || ld < cols || !rmax) return (int)hipErrorInvalidValue;
-  return stats_launch(stat_op(X, rows, cols, ld, 0, rmax, nullptr), StatOp{},
-                      kcnn::as_stream(stream));
-}
-extern "C" size_t kl_absmax_cols_words(int rows, int cols) {
-  if (rows <= 0 || cols <= 0) return 0;
-  return stat_part_words(rows, cols, 1);
-}
-extern "C" int kl_absmax_cols(const float *X, int rows, int cols, int ld, uint32_t *cmax,
-                              uint32_t *part, kcnn_stream_t stream) {
-  if (rows < 0 || cols < 0 || ld < cols || !cmax) return (int)hipErrorInvalidValue;
-  if (rows > 0 && cols > 0 && !part) return (int)hipErrorInvalidValue;
-  return stats_launch(stat_op(X, rows, cols, ld, 1, cmax, part), StatOp{},
-                      kcnn::as_stream(stream));
-}
-
-// kl_absmax_rows of R (rows x cols, pitch ld) and kl_absmax_cols of Q
-// (qrows x qcols, pitch ldq; part: kl_absmax_cols_words) in one statistics
-// launch (and Q's finalize / count passes): the f16x3 implicit GEMM's frame
-// and filter statistics (cnsl-conv-igemm-x6.hip); clear (nullable): two
-// words set to 0 by the same launch (that kernel's list counters)
-extern "C" int kl_absmax_rows_cols(const float *R, int rows, int cols, int ld, uint32_t *rmax,
-                                   const float *Q, int qrows, int qcols, int ldq, uint32_t *cmax,
-                                   uint32_t *part, uint32_t *clear, kcnn_stream_t stream) {
-  if (rows < 0 || cols < 0 || ld < cols || !rmax || qrows < 0 || qcols < 0 || ldq < qcols ||
-      !cmax)
-    return (int)hipErrorInvalidValue;
-  if (qrows > 0 && qcols > 0 && !part) return (int)hipErrorInvalidValue;
-  StatOp q = stat_op(Q, qrows, qcols, ldq, 1, cmax, part);
-  q.clear = clear;
-  const StatOp r = stat_op(R, rows, cols, ld, 0, rmax, nullptr);
-  if (clear && q.blocks + r.blocks == 0) {  // no statistics launch to clear it
-    const hipError_t e = hipMemsetAsync(clear, 0, 8, kcnn::as_stream(stream));
-    if (e != hipSuccess) return (int)e;
-  }
-  return stats_launch(q, r, kcnn::as_stream(stream));
-}
-
-// Up to three statistics passes in one set of launches (stats, finalize,
-// count): op i over X_i (rows_i x cols_i, pitch ld_i), per row (mode_i 0)
-// or per column (1, part_i: kl_absmax_cols_words of scratch) into the block
-// out_i; X_i NULL skips op i.  The FC backward's output derivative (rows for
-// the data gradient, columns for the weight gradient) and weight columns in
-// one pass set instead of two (AffineComponent::Backprop).
-extern "C" int kl_gemm_stats3(const float *X0, int rows0, int cols0, int ld0, int mode0,
-                              uint32_t *out0, uint32_t *part0, const float *X1, int rows1,
-                              int cols1, int ld1, int mode1, uint32_t *out1, uint32_t *part1,
-                              const float *X2, int rows2, int cols2, int ld2, int mode2,
-                              uint32_t *out2, uint32_t *part2, void *pool_cols,
-                              kcnn_stream_t stream) {
-  StatOps ops{};
-  if (pool_cols) {  // the pool's column kernels' grids (cnsl-conv-frame.hip kcnn_pool_cols_complete)
-    ops.pc = *static_cast<const PoolColDeferred *>(pool_cols);
-    const int ncq = ops.pc.npool % 4 == 0 ? ops.pc.npool / 4 : ops.pc.npool;
-    ops.pcx = (ncq + 255) / 256;
-    ops.pcy = (ops.pc.nblk + COLMAX_ROWS - 1) / COLMAX_ROWS;
-    ops.pcn = std::min(ops.pc.R, 256);
-  }
-  const float *X[3] = {X0, X1, X2};
-  const int rows[3] = {rows0, rows1, rows2}, cols[3] = {cols0, cols1, cols2};
-  const int ld[3] = {ld0, ld1, ld2}, mode[3] = {mode0, mode1, mode2};
-  uint32_t *out[3] = {out0, out1, out2}, *part[3] = {part0, part1, part2};
-  for (int i = 0; i < 3; ++i) {
-    ops.o[i] = StatOp{};
-    if (!X[i]) continue;
-    if (rows[i] < 0 || cols[i] < 0 || ld[i] < cols[i] || !out[i] || (mode[i] != 0 && mode[i] != 1) ||
-        (mode[i] == 1 && rows[i] > 0 && cols[i] > 0 && !part[i]))
-      return (int)hipErrorInvalidValue;
-    ops.o[i] = stat_op(X[i], rows[i], cols[i], ld[i], mode[i], out[i], mode[i] ? part[i] : nullptr);
-  }
-  return stats_launch3(ops, kcnn::as_stream(stream));
-}
-
-// C[M x N] = alpha * op(A) op(B) + beta * C with the operands' max |x| given:
-// amax[i] for row i of op(A), bmax[j] for column j of op(B) (bit patterns of
-// max |x|, kl_absmax_rows / kl_absmax_cols).  Needs 16-B aligned
-// K-contiguous operands (A untransposed, B transposed) with pitches % 4 == 0
-// and every workgroup's buffer offsets below 2^31; returns
-// hipErrorNotSupported otherwise (the caller uses kl_gemm_x6).
 extern "C" size_t kl_gemm_f16x3_workspace_bytes(int M, int N, int K) {
   return partial_bytes(M, N, K);
 }
@@ -2112,100 +1124,90 @@ extern "C" size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K
   out[2] = plan.ksplit > 1 ? plan.nwhole : 0;
   return plan.ksplit > 1 ? slab_bytes(plan.ksplit, M, N) + flag_bytes(M, N) : 0;
 }
-// The fix-up launch of a split-K call (an exit-at-once kernel of 4.4 us in
-// all but the rare calls with a spread group, FIX_GRID) is skipped for a call
-// site (shape, transposes, momentum or not) whose previous call deferred no
-// group: the site's word in host memory, cleared by the host at each launch
-// and set by the reduce when a group would have been deferred, is read at
-// the next launch.  A skipped call's reduce recomputes every rejection itself
-// (fix_local), a group over REJ_LOCAL in the order the fix-up would have used
-// (gemm_f16x3_reduce_kernel), so the word, read without a synchronise, never
-// reaches a result: a stale or wrong guess costs time, not a bit of C
-// (tests/test_gpu_gemm_fixup.py runs every route in both states).  Up to
-// FIX_SITES sites; the others always launch the fix-up.
-// kl_gemm_f16x3_fixup_counts counts the calls either way and
-// kl_gemm_f16x3_fixup_sites_reset forgets the sites, for those tests.
-constexpr int FIX_SITES = 256;
-struct FixSites {
-  std::mutex mu;
-  uint32_t *flags = nullptr;  // pinned host words (1: the fix-up was needed or is unknown)
-  uint32_t *dflags = nullptr; // the same words' device address
-  int64_t key[FIX_SITES][6];
-  int n = 0;
-  bool failed = false;
+namespace {
+
+// One call, as its extern "C" entry fills it:
+// C[M x N] = alpha * op(A) op(B) + beta * C (+ bias[col] on every row), or
+// with mom.W the product applied as the momentum update instead of stored.
+struct GemmCall {
+  int transA, transB, M, N, K;
+  float alpha, beta;
+  const float *A, *B;
+  float *C;
+  int lda, ldb, ldc;
+  // the statistics blocks [max[n], min[n], cnt[n]] of op(A)'s rows and op(B)'s
+  // columns (kl_absmax_rows / kl_absmax_cols); nullable where the entry takes
+  // them from the caller: gemm_stats computes the missing ones
+  const uint32_t *amax, *bmax;
+  const float *bias;  // nullable
+  void *ws;           // kl_gemm_f16x3_full_workspace_bytes; after gemm_stats the split-K part
+  size_t ws_bytes;
+  kcnn_stream_t stream;
+  MomentumEpi mom;
 };
-static FixSites &fix_sites() {
-  static FixSites fs;
-  return fs;
-}
-// split-K calls that launched the fix-up, that skipped it
-static std::atomic<unsigned long long> g_fix_calls[2];
-extern "C" void kl_gemm_f16x3_fixup_counts(unsigned long long *out, int reset) {
-  for (int i = 0; i < 2; ++i) {
-    out[i] = g_fix_calls[i].load(std::memory_order_relaxed);
-    if (reset) g_fix_calls[i].store(0, std::memory_order_relaxed);
-  }
-}
-// every site forgotten: the next call at any key registers again, word 1 (the
-// pinned words stay allocated; no device call)
-extern "C" void kl_gemm_f16x3_fixup_sites_reset(void) {
-  FixSites &fs = fix_sites();
-  std::lock_guard<std::mutex> lk(fs.mu);
-  fs.n = 0;
-}
-// the word of this site, nullptr when there is none (table full, no host memory)
-static uint32_t *fix_site(int M, int N, int K, int ta, int tb, int mom, uint32_t **dev) {
-  FixSites &fs = fix_sites();
-  std::lock_guard<std::mutex> lk(fs.mu);
-  if (!fs.flags && !fs.failed) {
-    void *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, FIX_SITES * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) ==
-            hipSuccess &&
-        hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-      fs.flags = static_cast<uint32_t *>(h);
-      fs.dflags = static_cast<uint32_t *>(d);
-    } else {
-      (void)hipGetLastError();
-      fs.failed = true;
-    }
-  }
-  if (!fs.flags) return nullptr;
-  const int64_t k[6] = {M, N, K, ta, tb, mom};
-  int i = 0;
-  for (; i < fs.n; ++i)
-    if (std::equal(k, k + 6, fs.key[i])) break;
-  if (i == fs.n) {
-    if (fs.n == FIX_SITES) return nullptr;
-    std::copy(k, k + 6, fs.key[fs.n++]);
-    __atomic_store_n(fs.flags + i, 1u, __ATOMIC_RELAXED);
-  }
-  *dev = fs.dflags + i;
-  return fs.flags + i;
+
+size_t stats_ws_words(int M, int N, int K, int transA, int transB) {
+  const size_t pa = transA ? stat_part_words(K, M, 1) : 0;
+  const size_t pb = transB ? 0 : stat_part_words(K, N, 1);
+  return 3 * ((size_t)M + N) + 4 + pa + pb;
 }
 
-static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alpha,
-                         const float *A, int lda, const float *B, int ldb, float beta, float *C,
-                         int ldc, const uint32_t *amax, const uint32_t *bmax, const float *bias,
-                         void *ws, size_t ws_bytes, kcnn_stream_t stream,
-                         const MomentumEpi *mom = nullptr) {
+// The shape and workspace checks, then the operand statistics the caller did
+// not supply (op(A)'s rows: A's rows, or its columns when transposed; op(B)'s
+// columns: B's columns, or its rows when transposed; one read of that
+// operand), one launch for both (two with a per-column one), into the
+// workspace after the partial slabs.
+int gemm_stats(GemmCall &c) {
+  const int M = c.M, N = c.N, K = c.K;
   if (M < 0 || N < 0 || K < 0) return (int)hipErrorInvalidValue;
   if (M == 0 || N == 0 || K == 0) return (int)hipErrorNotSupported;
-  const bool a_kc = !transA, b_kc = transB != 0;
-  if ((a_kc && (lda % 4 || (uintptr_t)A % 16)) || (b_kc && (ldb % 4 || (uintptr_t)B % 16)))
+  const size_t pb = partial_bytes(M, N, K);
+  if (!c.ws || c.ws_bytes < kl_gemm_f16x3_full_workspace_bytes(M, N, K))
+    return (int)hipErrorInvalidValue;
+  uint32_t *amax = reinterpret_cast<uint32_t *>(static_cast<char *>(c.ws) + pb);
+  uint32_t *bmax = amax + 3 * (size_t)M;  // statistics blocks: [max, min, cnt] per group
+  uint32_t *parta = bmax + 3 * (size_t)N + 4;
+  uint32_t *partb = parta + (c.transA ? stat_part_words(K, M, 1) : 0);
+  const StatOp sa = c.amax     ? StatOp{}
+                    : c.transA ? stat_op(c.A, K, M, c.lda, 1, amax, parta)
+                               : stat_op(c.A, M, K, c.lda, 0, amax, nullptr);
+  const StatOp sb = c.bmax     ? StatOp{}
+                    : c.transB ? stat_op(c.B, N, K, c.ldb, 0, bmax, nullptr)
+                               : stat_op(c.B, K, N, c.ldb, 1, bmax, partb);
+  if (!c.amax || !c.bmax) {
+    const int rc = c.amax ? stats_launch(sb, StatOp{}, kcnn::as_stream(c.stream))
+                          : stats_launch(sa, sb, kcnn::as_stream(c.stream));
+    if (rc) return rc;
+  }
+  if (!c.amax) c.amax = amax;
+  if (!c.bmax) c.bmax = bmax;
+  c.ws = pb ? c.ws : nullptr;
+  c.ws_bytes = pb;
+  return 0;
+}
+
+// The call's plan and its launches, the statistics given.  Needs 16-B
+// aligned K-contiguous operands (A untransposed, B transposed) with pitches
+// % 4 == 0 and every workgroup's buffer offsets below 2^31; returns
+// hipErrorNotSupported otherwise (the caller uses kl_gemm_x6).
+int gemm_launch(const GemmCall &c) {
+  const int M = c.M, N = c.N, K = c.K;
+  const bool a_kc = !c.transA, b_kc = c.transB != 0;
+  if ((a_kc && (c.lda % 4 || (uintptr_t)c.A % 16)) || (b_kc && (c.ldb % 4 || (uintptr_t)c.B % 16)))
     return (int)hipErrorNotSupported;
-  hipStream_t st = kcnn::as_stream(stream);
+  hipStream_t st = kcnn::as_stream(c.stream);
   GemmF16Args a{};
-  a.A = A; a.B = B; a.C = C; a.amax = amax; a.bmax = bmax; a.bias = bias;
-  if (mom) a.mom = *mom;
+  a.A = c.A; a.B = c.B; a.C = c.C; a.amax = c.amax; a.bmax = c.bmax; a.bias = c.bias;
+  a.mom = c.mom;
   // statistics blocks [max[n], min[n], cnt[n]] (stats_rows, stats_finalize_kernel)
-  a.amin = amax + M;
-  a.acnt = amax + 2 * (size_t)M;
-  a.bmin = bmax + N;
-  a.bcnt = bmax + 2 * (size_t)N;
+  a.amin = a.amax + M;
+  a.acnt = a.amax + 2 * (size_t)M;
+  a.bmin = a.bmax + N;
+  a.bcnt = a.bmax + 2 * (size_t)N;
   a.bvec = N % 4 == 0 && (uintptr_t)a.bmax % 16 == 0 && (uintptr_t)a.bcnt % 16 == 0;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.alpha = alpha; a.beta = beta;
-  const int am = loader_mode(a_kc, A, lda), bm = loader_mode(b_kc, B, ldb);
+  a.M = M; a.N = N; a.K = K; a.lda = c.lda; a.ldb = c.ldb; a.ldc = c.ldc;
+  a.alpha = c.alpha; a.beta = c.beta;
+  const int am = loader_mode(a_kc, c.A, c.lda), bm = loader_mode(b_kc, c.B, c.ldb);
   const GemmPlan plan =
       choose_plan(M, N, K, am != LR && bm != LR, kcnn::family(kcnn::kFamGemm));
   const int BN = plan.bn;
@@ -2216,10 +1218,10 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
   int nwhole = plan.nwhole;
   int s = plan.ksplit;
   const size_t need = s > 1 ? slab_bytes(s, M, N) + flag_bytes(M, N) : 0;
-  if (need > ws_bytes || !ws) s = 1;
+  if (need > c.ws_bytes || !c.ws) s = 1;
   if (s > 1) {
-    a.part = static_cast<float *>(ws);
-    a.rflag = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + slab_bytes(s, M, N));
+    a.part = static_cast<float *>(c.ws);
+    a.rflag = reinterpret_cast<uint32_t *>(static_cast<char *>(c.ws) + slab_bytes(s, M, N));
     static std::atomic<uint32_t> calls{0};
     a.gen = ++calls;
     if (a.gen == 0) a.gen = ++calls;
@@ -2232,127 +1234,60 @@ static int gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alph
     if (kc) return (int64_t)R * ld * 4 + (int64_t)(K + 2 * BK) * 4 < ((int64_t)1 << 31);
     return (int64_t)(span + 2 * BK) * ld * 4 + (int64_t)R * 4 < ((int64_t)1 << 31);
   };
-  if (!fits(a_kc, lda, BM, a.kps) || !fits(b_kc, ldb, BN, a.kps)) return (int)hipErrorNotSupported;
-  if (s == 1 || !fits(a_kc, lda, BM, K) || !fits(b_kc, ldb, BN, K)) nwhole = 0;
+  if (!fits(a_kc, c.lda, BM, a.kps) || !fits(b_kc, c.ldb, BN, a.kps))
+    return (int)hipErrorNotSupported;
+  if (s == 1 || !fits(a_kc, c.lda, BM, K) || !fits(b_kc, c.ldb, BN, K)) nwhole = 0;
   a.nwhole = nwhole;
   const int64_t nb = nwhole + (tiles - nwhole) * s;
   if (nb >= ((int64_t)1 << 31)) return (int)hipErrorNotSupported;
-  bool fix_launch = true;
-  if (s > 1) {
-    uint32_t *dev = nullptr;
-    uint32_t *site = fix_site(M, N, K, transA != 0, transB != 0, a.mom.W != nullptr, &dev);
-    if (site) {
-      fix_launch = __atomic_load_n(site, __ATOMIC_RELAXED) != 0;
-      __atomic_store_n(site, 0u, __ATOMIC_RELAXED);
-      a.fix_report = dev;
-      a.fix_local = fix_launch ? 0 : 1;
-    }
-  }
+  // (the site's word is read and cleared before anything of the call is enqueued)
+  const FixupSite site = s > 1 ? split_k_site(a, a_kc, b_kc) : FixupSite{};
   launch(am, bm, a, (unsigned)nb, st);
-  int rc = kcnn::launch_status();
+  const int rc = kcnn::launch_status();
   if (!rc) g_tile_calls[BN == BN_WIDE ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
   if (rc || s == 1) return rc;
-  // op(B) row-contiguous: 16-B loads along its rows in the recomputation of
-  // a group over REJ_LOCAL, by the fix-up or (fix_local) by the reduce
-  const int rows = !b_kc && ldb % 4 == 0 && (uintptr_t)B % 16 == 0 && N % 4 == 0;
-  hipLaunchKernelGGL(gemm_f16x3_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * ((N + 3) / 4))),
-                     dim3(256), 0, st, a, a_kc ? 1 : 0, b_kc ? 1 : 0, rows);
-  rc = kcnn::launch_status();
-  if (!rc) g_fix_calls[fix_launch ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
-  if (rc || !fix_launch) return rc;
-  const int64_t slots = ((int64_t)M * ((N + 3) / 4) + 63) / 64;
-  hipLaunchKernelGGL(gemm_f16x3_fixup_kernel,
-                     dim3((unsigned)std::min<int64_t>(FIX_GRID, (slots + 15) / 16)), dim3(256), 0, st,
-                     a, a_kc ? 1 : 0, b_kc ? 1 : 0, rows);
-  return kcnn::launch_status();
-}
-extern "C" int kl_gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alpha,
-                                const float *A, int lda, const float *B, int ldb, float beta,
-                                float *C, int ldc, const uint32_t *amax, const uint32_t *bmax,
-                                void *ws, size_t ws_bytes, kcnn_stream_t stream) {
-  return gemm_f16x3_st(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, amax, bmax,
-                       nullptr, ws, ws_bytes, stream);
+  return split_k_finish(a, a_kc, b_kc, site, st);
 }
 
-// The same with the operand statistics computed here (op(A)'s rows: A's rows,
-// or its columns when transposed; op(B)'s columns: B's columns, or its rows
-// when transposed), one launch for both (two with a per-column one), into
-// the workspace after the partial slabs.
-namespace {
-size_t stats_ws_words(int M, int N, int K, int transA, int transB) {
-  const size_t pa = transA ? stat_part_words(K, M, 1) : 0;
-  const size_t pb = transB ? 0 : stat_part_words(K, N, 1);
-  return 3 * ((size_t)M + N) + 4 + pa + pb;
+int gemm_run(GemmCall c) {
+  const int rc = gemm_stats(c);
+  return rc ? rc : gemm_launch(c);
 }
+
 }  // namespace
+
 extern "C" size_t kl_gemm_f16x3_full_workspace_bytes(int M, int N, int K) {
   size_t w = 0;
   for (int ta = 0; ta < 2; ++ta)
     for (int tb = 0; tb < 2; ++tb) w = std::max(w, stats_ws_words(M, N, K, ta, tb));
   return partial_bytes(M, N, K) + align16(sizeof(uint32_t) * w);
 }
+// The operand statistics computed here, in the workspace
 extern "C" int kl_gemm_f16x3(int transA, int transB, int M, int N, int K, float alpha,
                              const float *A, int lda, const float *B, int ldb, float beta,
                              float *C, int ldc, void *ws, size_t ws_bytes,
                              kcnn_stream_t stream) {
-  return kl_gemm_f16x3_given(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                             nullptr, nullptr, ws, ws_bytes, stream);
+  return gemm_run({transA, transB, M, N, K, alpha, beta, A, B, C, lda, ldb, ldc, nullptr, nullptr,
+                   nullptr, ws, ws_bytes, stream, {}});
 }
-// ... with either operand's statistics supplied by its producer (nullable):
-// only the missing ones are computed (one read of that operand)
-extern "C" int kl_gemm_f16x3_given(int transA, int transB, int M, int N, int K, float alpha,
-                                   const float *A, int lda, const float *B, int ldb, float beta,
-                                   float *C, int ldc, const uint32_t *amax_given,
-                                   const uint32_t *bmax_given, void *ws, size_t ws_bytes,
-                                   kcnn_stream_t stream) {
-  return kl_gemm_f16x3_bias(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                            amax_given, bmax_given, nullptr, ws, ws_bytes, stream);
-}
-// ... and C += bias[col] on every row (bias nullable), in the same store: the
-// FC forward's out = bias; out += in W^T without the bias copy or C's re-read
-static int gemm_f16x3_full(int transA, int transB, int M, int N, int K, float alpha,
-                           const float *A, int lda, const float *B, int ldb, float beta,
-                           float *C, int ldc, const uint32_t *amax_given,
-                           const uint32_t *bmax_given, const float *bias, void *ws,
-                           size_t ws_bytes, kcnn_stream_t stream, const MomentumEpi *mom) {
-  if (M < 0 || N < 0 || K < 0) return (int)hipErrorInvalidValue;
-  if (M == 0 || N == 0 || K == 0) return (int)hipErrorNotSupported;
-  const size_t pb = partial_bytes(M, N, K);
-  if (!ws || ws_bytes < kl_gemm_f16x3_full_workspace_bytes(M, N, K))
-    return (int)hipErrorInvalidValue;
-  uint32_t *amax = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + pb);
-  uint32_t *bmax = amax + 3 * (size_t)M;  // statistics blocks: [max, min, cnt] per group
-  uint32_t *parta = bmax + 3 * (size_t)N + 4;
-  uint32_t *partb = parta + (transA ? stat_part_words(K, M, 1) : 0);
-  const StatOp sa = amax_given ? StatOp{}
-                    : transA   ? stat_op(A, K, M, lda, 1, amax, parta)
-                               : stat_op(A, M, K, lda, 0, amax, nullptr);
-  const StatOp sb = bmax_given ? StatOp{}
-                    : transB   ? stat_op(B, N, K, ldb, 0, bmax, nullptr)
-                               : stat_op(B, K, N, ldb, 1, bmax, partb);
-  if (!amax_given || !bmax_given) {
-    const int rc = amax_given ? stats_launch(sb, StatOp{}, kcnn::as_stream(stream))
-                              : stats_launch(sa, sb, kcnn::as_stream(stream));
-    if (rc) return rc;
-  }
-  return gemm_f16x3_st(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                       amax_given ? amax_given : amax, bmax_given ? bmax_given : bmax, bias,
-                       pb ? ws : nullptr, pb, stream, mom);
-}
+// ... with either operand's statistics supplied by its producer (nullable:
+// only the missing ones are computed), and C += bias[col] on every row (bias
+// nullable), in the same store: the FC forward's out = bias; out += in W^T
+// without the bias copy or C's re-read
 extern "C" int kl_gemm_f16x3_bias(int transA, int transB, int M, int N, int K, float alpha,
                                   const float *A, int lda, const float *B, int ldb, float beta,
                                   float *C, int ldc, const uint32_t *amax_given,
                                   const uint32_t *bmax_given, const float *bias, void *ws,
                                   size_t ws_bytes, kcnn_stream_t stream) {
-  return gemm_f16x3_full(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                         amax_given, bmax_given, bias, ws, ws_bytes, stream, nullptr);
+  return gemm_run({transA, transB, M, N, K, alpha, beta, A, B, C, lda, ldb, ldc, amax_given,
+                   bmax_given, bias, ws, ws_bytes, stream, {}});
 }
 // The weight-gradient product applied as the momentum update in its own
 // store (momentum-step.h): for every element g = (op(A) op(B))[i][j],
 // prev = momentum prev + a_wd W + a_g g, W += prev, the bits of
-// kl_gemm_f16x3_given(alpha 1, beta 0) into a gradient buffer followed by
-// hipF_momentum_update, without the buffer's write and read.  W and prev are
-// M x N with 16-B aligned rows (hipErrorNotSupported otherwise).
+// kl_gemm_f16x3_bias(alpha 1, beta 0, a null bias) into a gradient buffer
+// followed by hipF_momentum_update, without the buffer's write and read.  W
+// and prev are M x N with 16-B aligned rows (hipErrorNotSupported otherwise).
 extern "C" int kl_gemm_f16x3_momentum(int transA, int transB, int M, int N, int K,
                                       const float *A, int lda, const float *B, int ldb,
                                       const uint32_t *amax_given, const uint32_t *bmax_given,
@@ -2361,9 +1296,7 @@ extern "C" int kl_gemm_f16x3_momentum(int transA, int transB, int M, int N, int 
                                       kcnn_stream_t stream) {
   if (!W || !prev || ldw % 4 || ldp % 4 || (uintptr_t)W % 16 || (uintptr_t)prev % 16)
     return (int)hipErrorNotSupported;
-  MomentumEpi m;
-  m.W = W; m.prev = prev; m.ldw = ldw; m.ldp = ldp;
-  m.momentum = momentum; m.a_wd = a_wd; m.a_g = a_g;
-  return gemm_f16x3_full(transA, transB, M, N, K, 1.0f, A, lda, B, ldb, 0.0f, nullptr, ldw,
-                         amax_given, bmax_given, nullptr, ws, ws_bytes, stream, &m);
+  return gemm_run({transA, transB, M, N, K, 1.0f, 0.0f, A, B, nullptr, lda, ldb, ldw, amax_given,
+                   bmax_given, nullptr, ws, ws_bytes, stream,
+                   {W, prev, ldw, ldp, momentum, a_wd, a_g}});
 }

@@ -42,6 +42,7 @@
 #include "cnslmat/lds-dma.h"
 #include "cnslmat/hip-util.h"
 #include "kaldi-lite/cu-kernels-lite.h"
+#include "kaldi-lite/launch-lds.h"
 
 namespace {
 
@@ -752,18 +753,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_planes_kernel(GemmPlanesArgs p) {
     }
 }
 
-template <bool A_KC, bool B_KC>
-void launch_planes(const GemmPlanesArgs &a, unsigned blocks, hipStream_t st) {
-  static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<A_KC, B_KC>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_planes_kernel<A_KC, B_KC>), dim3(blocks), dim3(NT), LDS_BYTES, st,
-                     a);
-}
-
 // fp32 [rows x cols] (pitch ld) -> planes h, m, l [rows x cols] (pitch ldp,
 // plane stride ps elements); 4 columns per thread when aligned
 // vec: 16-B loads of 4 fp32 and 8-B stores of 4 bf16 per plane are aligned
@@ -798,26 +787,11 @@ __global__ void split_planes_kernel(const float *__restrict__ src, int rows, int
   }
 }
 
-template <bool A_KC, bool B_KC>
-void launch_x6(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_x6_kernel<A_KC, B_KC>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_x6_kernel<A_KC, B_KC>), dim3(blocks), dim3(NT), LDS_BYTES, st, a);
-}
-
-template <bool A_KC, bool B_KC>
-void launch_x6d(const GemmX6Args &a, unsigned blocks, hipStream_t st) {
-  static bool attr = [] {
-    return hipFuncSetAttribute(
-               reinterpret_cast<const void *>(&gemm_x6d_kernel<A_KC, B_KC>),
-               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((gemm_x6d_kernel<A_KC, B_KC>), dim3(blocks), dim3(NT), LDS_BYTES, st, a);
+// f(A_KC, B_KC) with the two layouts as std::true_type / std::false_type: a
+// kernel's template parameters from the call's transposes
+template <typename F>
+void with_layouts(bool a_kc, bool b_kc, F f) {
+  kcnn::with_bool(a_kc, [&](auto A) { kcnn::with_bool(b_kc, [&](auto B) { f(A, B); }); });
 }
 
 // K splits for a tile count: the fraction of the last wave of workgroups
@@ -833,6 +807,37 @@ int choose_ksplit(int64_t tiles, int K) {
     if (score > best_score + 1e-9) { best_score = score; best = s; }
   }
   return best;
+}
+
+// The tiles and the split-K set-up of a call (a: GemmX6Args or GemmPlanesArgs
+// with M, N and K set): the split count, cut to 1 without the workspace for
+// it, the K span per split, and the kernel's output, the partial slabs in the
+// workspace when split and the caller's C otherwise.  Returns the grid's
+// workgroups.
+template <typename Args>
+int64_t split_k_setup(Args &a, float *C, void *ws, size_t ws_bytes) {
+  a.tiles_m = (a.M + BM - 1) / BM;
+  a.tiles_n = (a.N + BN - 1) / BN;
+  const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
+  int s = choose_ksplit(tiles, a.K);
+  const size_t need = s > 1 ? sizeof(float) * (size_t)s * a.M * a.N : 0;
+  if (need > ws_bytes || !ws) s = 1;
+  a.ksplit = s;
+  a.kps = ((a.K + s - 1) / s + BK - 1) / BK * BK;
+  a.partial = s > 1;
+  a.C = s > 1 ? static_cast<float *>(ws) : C;
+  return tiles * s;
+}
+// C = alpha * (the sum of the s slabs at ws) + beta * C, by quads where C allows
+int reduce_launch(const void *ws, int s, int M, int N, float alpha, float beta, float *C, int ldc,
+                  hipStream_t st) {
+  if (N % 4 == 0 && ldc % 4 == 0 && (uintptr_t)C % 16 == 0)
+    hipLaunchKernelGGL(gemm_x6_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * (N / 4))),
+                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
+  else
+    hipLaunchKernelGGL(gemm_x6_reduce_scalar_kernel, dim3(kcnn::grid_for((int64_t)M * N)),
+                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
+  return kcnn::launch_status();
 }
 
 }  // namespace
@@ -858,43 +863,23 @@ extern "C" int kl_gemm_x6(int transA, int transB, int M, int N, int K, float alp
   hipStream_t st = kcnn::as_stream(stream);
   GemmX6Args a;
   a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb;
-  a.alpha = alpha; a.beta = beta;
-  a.tiles_m = (M + BM - 1) / BM;
-  a.tiles_n = (N + BN - 1) / BN;
-  const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-  int s = choose_ksplit(tiles, K);
-  const size_t need = s > 1 ? sizeof(float) * (size_t)s * M * N : 0;
-  if (need > ws_bytes || !ws) s = 1;
-  a.ksplit = s;
-  a.kps = ((K + s - 1) / s + BK - 1) / BK * BK;
-  a.partial = s > 1;
-  a.C = s > 1 ? static_cast<float *>(ws) : C;
-  a.ldc = ldc;
-  const int64_t nb = tiles * s;
+  a.alpha = alpha; a.beta = beta; a.ldc = ldc;
+  const int64_t nb = split_k_setup(a, C, ws, ws_bytes);
   if (nb >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
   // two-deep prefetch kernel: whole BK steps, the workgroup's offsets below 2^31
   auto deep_fits = [&](bool kc, int ld, int R) {
     if (kc) return (int64_t)R * ld * 4 + (int64_t)K * 4 < ((int64_t)1 << 31);
     return (int64_t)(a.kps + 1) * ld * 4 + (int64_t)R * 4 < ((int64_t)1 << 31);
   };
-  if (K % BK == 0 && deep_fits(a_kc, lda, BM) && deep_fits(b_kc, ldb, BN)) {
-    if (a_kc && b_kc) launch_x6d<true, true>(a, (unsigned)nb, st);
-    else if (a_kc) launch_x6d<true, false>(a, (unsigned)nb, st);
-    else if (b_kc) launch_x6d<false, true>(a, (unsigned)nb, st);
-    else launch_x6d<false, false>(a, (unsigned)nb, st);
-  } else if (a_kc && b_kc) launch_x6<true, true>(a, (unsigned)nb, st);
-  else if (a_kc) launch_x6<true, false>(a, (unsigned)nb, st);
-  else if (b_kc) launch_x6<false, true>(a, (unsigned)nb, st);
-  else launch_x6<false, false>(a, (unsigned)nb, st);
-  int rc = kcnn::launch_status();
-  if (rc || s == 1) return rc;
-  if (N % 4 == 0 && ldc % 4 == 0 && (uintptr_t)C % 16 == 0)
-    hipLaunchKernelGGL(gemm_x6_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * (N / 4))),
-                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
-  else
-    hipLaunchKernelGGL(gemm_x6_reduce_scalar_kernel, dim3(kcnn::grid_for((int64_t)M * N)),
-                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
-  return kcnn::launch_status();
+  const bool deep = K % BK == 0 && deep_fits(a_kc, lda, BM) && deep_fits(b_kc, ldb, BN);
+  with_layouts(a_kc, b_kc, [&](auto A, auto B) {
+    constexpr bool AKC = decltype(A)::value, BKC = decltype(B)::value;
+    if (deep) kcnn::launch_lds<&gemm_x6d_kernel<AKC, BKC>, LDS_BYTES>(a, (unsigned)nb, NT, st);
+    else kcnn::launch_lds<&gemm_x6_kernel<AKC, BKC>, LDS_BYTES>(a, (unsigned)nb, NT, st);
+  });
+  const int rc = kcnn::launch_status();
+  if (rc || a.ksplit == 1) return rc;
+  return reduce_launch(ws, a.ksplit, M, N, alpha, beta, C, ldc, st);
 }
 
 extern "C" int kl_split_planes(const float *src, int rows, int cols, int ld, uint16_t *dst,
@@ -936,29 +921,13 @@ extern "C" int kl_gemm_planes(int transA, int transB, int M, int N, int K, float
   GemmPlanesArgs a;
   a.A = A; a.B = B; a.aps = aps; a.bps = bps; a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.alpha = alpha; a.beta = beta;
-  a.tiles_m = (M + BM - 1) / BM;
-  a.tiles_n = (N + BN - 1) / BN;
-  const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-  int s = choose_ksplit(tiles, K);
-  const size_t need = s > 1 ? sizeof(float) * (size_t)s * M * N : 0;
-  if (need > ws_bytes || !ws) s = 1;
-  a.ksplit = s;
-  a.kps = ((K + s - 1) / s + BK - 1) / BK * BK;
-  a.partial = s > 1;
-  a.C = s > 1 ? static_cast<float *>(ws) : C;
-  const int64_t nb = tiles * s;
+  const int64_t nb = split_k_setup(a, C, ws, ws_bytes);
   if (nb >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-  if (a_kc && b_kc) launch_planes<true, true>(a, (unsigned)nb, st);
-  else if (a_kc) launch_planes<true, false>(a, (unsigned)nb, st);
-  else if (b_kc) launch_planes<false, true>(a, (unsigned)nb, st);
-  else launch_planes<false, false>(a, (unsigned)nb, st);
-  int rc = kcnn::launch_status();
-  if (rc || s == 1) return rc;
-  if (N % 4 == 0 && ldc % 4 == 0 && (uintptr_t)C % 16 == 0)
-    hipLaunchKernelGGL(gemm_x6_reduce_kernel, dim3(kcnn::grid_for((int64_t)M * (N / 4))),
-                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
-  else
-    hipLaunchKernelGGL(gemm_x6_reduce_scalar_kernel, dim3(kcnn::grid_for((int64_t)M * N)),
-                       dim3(256), 0, st, (const float *)ws, s, M, N, alpha, beta, C, ldc);
-  return kcnn::launch_status();
+  with_layouts(a_kc, b_kc, [&](auto A, auto B) {
+    kcnn::launch_lds<&gemm_planes_kernel<decltype(A)::value, decltype(B)::value>, LDS_BYTES>(
+        a, (unsigned)nb, NT, st);
+  });
+  const int rc = kcnn::launch_status();
+  if (rc || a.ksplit == 1) return rc;
+  return reduce_launch(ws, a.ksplit, M, N, alpha, beta, C, ldc, st);
 }

@@ -29,14 +29,16 @@ int kl_gemm_x6(int transA, int transB, int M, int N, int K, float alpha,
                const float *A, int lda, const float *B, int ldb, float beta,
                float *C, int ldc, void *ws, size_t ws_bytes, kcnn_stream_t st);
 /* fp32 GEMM on the f16 MFMAs: two-part f16 split under per-row / per-column
-   power-of-two scales (cu-gemm-f16x3.hip).  kl_absmax_rows / kl_absmax_cols
-   write a statistics block per row / column set: [max[n], min[n], cnt[n]],
+   power-of-two scales (cu-gemm-f16x3.hip; its split-K finish
+   cu-gemm-f16x3-reduce.hip, the statistics pass cu-f16-stats.hip).
+   kl_absmax_rows / kl_absmax_cols write a statistics block per row / column
+   set: [max[n], min[n], cnt[n]],
    the max |x| and the min nonzero |x| bit patterns (0: no nonzero element)
    and, for a spread group (cnslmat/f16-split.h), the count of its small
    elements (0 otherwise), 3 n words (the column form needs
    kl_absmax_cols_words of scratch);
-   kl_gemm_f16x3_st takes the blocks of op(A)'s rows and op(B)'s columns,
-   kl_gemm_f16x3 computes them in its workspace.
+   kl_gemm_f16x3 computes the blocks of op(A)'s rows and op(B)'s columns in
+   its workspace, kl_gemm_f16x3_bias takes either from the caller.
    Both return hipErrorNotSupported for shapes outside the kernel's
    addressing limits. */
 int kl_absmax_rows(const float *X, int rows, int cols, int ld, uint32_t *rmax,
@@ -71,28 +73,20 @@ size_t kl_gemm_f16x3_plan(int transA, int transB, int M, int N, int K, int lda, 
    at any key is a fresh site, which launches the fix-up).  Host only. */
 void kl_gemm_f16x3_fixup_counts(unsigned long long *out, int reset);
 void kl_gemm_f16x3_fixup_sites_reset(void);
-int kl_gemm_f16x3_st(int transA, int transB, int M, int N, int K, float alpha,
-                     const float *A, int lda, const float *B, int ldb, float beta, float *C,
-                     int ldc, const uint32_t *amax, const uint32_t *bmax, void *ws,
-                     size_t ws_bytes, kcnn_stream_t st);
 size_t kl_gemm_f16x3_full_workspace_bytes(int M, int N, int K);
 int kl_gemm_f16x3(int transA, int transB, int M, int N, int K, float alpha,
                   const float *A, int lda, const float *B, int ldb, float beta, float *C,
                   int ldc, void *ws, size_t ws_bytes, kcnn_stream_t st);
 /* kl_gemm_f16x3 with op(A)'s row and/or op(B)'s column statistics supplied
-   (nullable; e.g. from the fused conv + pool forward that wrote the operand) */
-int kl_gemm_f16x3_given(int transA, int transB, int M, int N, int K, float alpha,
-                        const float *A, int lda, const float *B, int ldb, float beta, float *C,
-                        int ldc, const uint32_t *amax, const uint32_t *bmax, void *ws,
-                        size_t ws_bytes, kcnn_stream_t st);
-/* kl_gemm_f16x3_given with C += bias[j] on every row (bias nullable; after
-   alpha and beta), in the kernel's own store. */
+   (nullable; e.g. from the fused conv + pool forward that wrote the operand)
+   and with C += bias[j] on every row (bias nullable; after alpha and beta),
+   in the kernel's own store. */
 int kl_gemm_f16x3_bias(int transA, int transB, int M, int N, int K, float alpha,
                        const float *A, int lda, const float *B, int ldb, float beta, float *C,
                        int ldc, const uint32_t *amax_given, const uint32_t *bmax_given,
                        const float *bias, void *ws, size_t ws_bytes, kcnn_stream_t stream);
-/* kl_gemm_f16x3_given(alpha 1, beta 0) of a weight gradient applied as the
-   momentum update in the GEMM's own store (cnslmat/momentum-step.h): W and
+/* kl_gemm_f16x3_bias(alpha 1, beta 0, a null bias) of a weight gradient
+   applied as the momentum update in the GEMM's own store (cnslmat/momentum-step.h): W and
    prev (M x N, 16-B aligned rows) get prev = momentum prev + a_wd W + a_g g,
    W += prev; the bits of the gradient buffer + hipF_momentum_update */
 int kl_gemm_f16x3_momentum(int transA, int transB, int M, int N, int K, const float *A,

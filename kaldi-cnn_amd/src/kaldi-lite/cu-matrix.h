@@ -317,7 +317,7 @@ Real VecVec(const CuVectorBase<Real> &a, const CuVectorBase<Real> &b);
 /// to AddMatMat while the object is in scope on this thread.  AddMatMat's
 /// f16x3 engine scales each operand row / column by them
 /// (kaldi-lite/cu-gemm-f16x3.hip) and would otherwise read the operand once
-/// more to compute them.  The owner keeps the matrix unmodified in scope.
+/// more to compute them (kaldi-lite/cu-f16-stats.hip).  The owner keeps the matrix unmodified in scope.
 }  // namespace kaldi
 struct PoolColDeferred;  // cnslmat/pool-stats.h
 namespace kaldi {

@@ -1,6 +1,6 @@
 """numpy restatement of an f16x3 statistics block (cnslmat/f16-split.h:
-ebits, spread, small_bound; kaldi-lite/cu-gemm-f16x3.hip: the comment above
-struct StatOp).
+ebits, spread, small_bound; kaldi-lite/cu-f16-stats.hip: the comment at
+its head; kaldi-lite/f16-stats.h: struct StatOp).
 
 A scale group is a row or a column of a float32 matrix.  Its block entry is
 [max, min, cnt], three uint32 words:

@@ -274,6 +274,53 @@ def test_gemm_f16x3_ragged_rows(kc, ta, tb, shape, pitch):
         _bound(torch, a, b, c0, c, ta, tb, alpha, beta)
 
 
+# (ta, tb, A's pitch padding, B's, K): a row-contiguous operand (A transposed,
+# B not) on an odd pitch takes the one-dword loader (LR), on a pitch that is
+# a multiple of 4 the 16-B transposed one (LT); a K-contiguous one (LK) needs
+# its pitch a multiple of 4.  K 64 is whole steps of 32, 77 is ragged.
+ONE_DWORD = [(False, False, 0, 3, 64),                            # LK, LR
+             (True, False, 4, 3, 64), (True, False, 4, 3, 77),    # LT, LR
+             (True, True, 3, 0, 64), (True, True, 3, 3, 77),      # LR, LK
+             (True, False, 3, 4, 64), (True, False, 3, 4, 77),    # LR, LT
+             (True, False, 3, 3, 64), (True, False, 3, 3, 77)]    # LR, LR
+
+
+@pytest.mark.parametrize("ta,tb,pa,pb,k", ONE_DWORD)
+def test_gemm_f16x3_one_dword_loader(kc, ta, tb, pa, pb, k):
+    """The two-phase kernel's instances with a one-dword (LR) operand, one
+    narrow tile each.  AddMatMat copies an operand with an unaligned pitch to
+    a padded one, so only kl_gemm_f16x3 called directly reaches them (as
+    test_gpu_gemm_wide.py test_unaligned_pitch_takes_the_narrow_tile reaches
+    LK, LR with a ragged K); the bound is this file's."""
+    import ctypes
+    import torch
+    m, n = 132, 68
+    g = torch.Generator(device="cuda")
+    g.manual_seed(17)
+
+    def mk(r, c, pitch, s):
+        return (torch.randn((r, c + pitch), generator=g, device="cuda") * s)[:, :c]
+    a = mk(k, m, pa, 1.0) if ta else mk(m, k, pa, 1.0)
+    b = mk(n, k, pb, 0.01) if tb else mk(k, n, pb, 0.01)
+    c0 = mk(m, n, 0, 1.0)
+    c = c0.clone()
+    L = kc.lib()
+    L.kl_gemm_f16x3_full_workspace_bytes.restype = ctypes.c_size_t
+    wsb = int(L.kl_gemm_f16x3_full_workspace_bytes(m, n, k))
+    ws = torch.empty(wsb // 4 + 4, dtype=torch.int32, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    kc.gemm_tile_counts(reset=True)
+    rc = L.kl_gemm_f16x3(int(ta), int(tb), m, n, k, ctypes.c_float(1.0),
+                         ctypes.c_void_p(a.data_ptr()), a.stride(0),
+                         ctypes.c_void_p(b.data_ptr()), b.stride(0), ctypes.c_float(0.5),
+                         ctypes.c_void_p(c.data_ptr()), c.stride(0),
+                         ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(wsb), stream)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert tuple(kc.gemm_tile_counts()) == (1, 0)
+    _bound(torch, a, b, c0, c, ta, tb, 1.0, 0.5)
+
+
 C2_FC = [("fc_fwd", 4096, 1024, 11616, False, True),
          ("fc_dgrad", 4096, 11616, 1024, False, False),
          ("fc_wgrad", 1024, 11616, 4096, True, False)]

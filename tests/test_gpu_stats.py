@@ -1,4 +1,4 @@
-"""The f16x3 GEMM's own operand statistics (kaldi-lite/cu-gemm-f16x3.hip:
+"""The f16x3 GEMM's own operand statistics (kaldi-lite/cu-f16-stats.hip:
 stats_kernel, stats_finalize_kernel, stats_count_kernel) through their four
 entry points kl_absmax_rows, kl_absmax_cols, kl_absmax_rows_cols and
 kl_gemm_stats3, bit for bit against the numpy definition of a statistics
