@@ -463,6 +463,51 @@ int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int
                       int num_utts, int pad_input, const float *priors, int num_priors,
                       float prior_scale, int apply_log, const float **data, MatrixDim *dim);
 
+/* ---- training from a corpus that stays on the device --------------------- */
+/* What nnet-get-egs and nnet-shuffle-egs do for nnet-train, without the
+ * window matrices: the corpus is the DEVICE matrix feats [sum of lengths x
+ * InputDim] of whole utterances stacked row-wise, lengths the HOST array of
+ * their num_utts >= 1 frame counts (each >= 1, summing to dim.rows).  The
+ * handle BORROWS feats, which must outlive it, and keeps the utterances' starts
+ * as a host prefix array, so a minibatch does no O(utterances) work.  NULL on
+ * error (bad lengths, an empty matrix or one of 2^31 elements), the message
+ * in kcnn_last_error(); nothing on the device is touched. */
+typedef struct kcnn_corpus kcnn_corpus;
+kcnn_corpus *kcnn_corpus_new(const float *feats, MatrixDim dim, const int32_t *lengths,
+                             int num_utts);
+void kcnn_corpus_free(kcnn_corpus *c);
+/* kcnn_nnet_propagate on a minibatch given as num_frames >= 1 HOST indices of
+ * corpus rows, in any order, repeats allowed.  Example n with row r =
+ * frames[n] in the utterance of rows [s, e) has the input chunk of rows
+ * clamp(r + o, s, e - 1) for the offsets o = -L .. R of the contexts above
+ * (what nnet-get-egs writes for frame r), and the pass computes what
+ * kcnn_nnet_propagate computes on the [(L + 1 + R) * num_frames x InputDim]
+ * matrix of those chunks, bit for bit; the rows of the output are the
+ * examples in order, and kcnn_nnet_backprop_xent / _backprop / _backprop_
+ * component follow as after kcnn_nnet_propagate.  The chunks are gathered on
+ * the device from {r, s, e - 1} triples staged by the host:
+ *   component 0 a SpliceComponent: its output is gathered straight from the
+ *     corpus and the chunk matrix is never stored.  kcnn_nnet_output(n, -1) is
+ *     the corpus.  The Splice's Backprop is then not run (it has no
+ *     parameters, and its input derivative would be a chunk matrix of rows
+ *     that examples share): kcnn_nnet_input_deriv(n, 0) is an error until the
+ *     next kcnn_nnet_propagate.
+ *   any other component 0: the same kernel lays the chunk matrix out in a
+ *     contiguous matrix of the network's, kcnn_nnet_output(n, -1), and
+ *     everything runs on it as after kcnn_nnet_propagate.
+ * Every check (no frames, an index outside the corpus, corpus columns other
+ * than InputDim, (L + 1 + R) * num_frames or any activation reaching 2^31 rows
+ * or elements) is made before anything is launched; a violation is an error
+ * that runs no kernel and changes nothing.  Does not synchronise. */
+int kcnn_nnet_propagate_frames(kcnn_nnet *n, const kcnn_corpus *corpus, const int32_t *frames,
+                               int num_frames);
+/* kcnn_nnet_compute_prob on such a minibatch: the labels' rows are 0 ..
+ * num_frames - 1, row n being example frames[n].  Same checks, then those of
+ * the labels; the state kcnn_nnet_compute_prob leaves. */
+int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
+                                  const int32_t *frames, int num_frames, const int32_t *rows,
+                                  const int32_t *cols, const float *weights, int num);
+
 #ifdef __cplusplus
 }
 #endif

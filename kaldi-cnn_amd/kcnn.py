@@ -10,6 +10,8 @@ Mirrors the reference's interfaces with the same names and argument meaning:
     nnet0 components implement them (nnet0/nnet-component-nnet0.h:23-232),
     created with ``Component.NewFromString`` (nnet2/nnet-component.cc:124-136)
   * ``Nnet``            = a component stack run NnetUpdater-style.
+  * ``Corpus`` / ``train_epoch`` = training minibatches as rows of a corpus
+    that stays on the device (nnet-get-egs + nnet-shuffle-egs + nnet-train).
 
 Matrices are 2-D float32 CUDA tensors with unit column stride (any row
 stride); they are handed to the C++ library as raw device pointers + MatrixDim
@@ -77,6 +79,16 @@ def lib():
             L.kcnn_nnet_copy.restype = ctypes.c_void_p
             L.kcnn_nnet_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_int]
+        if hasattr(L, "kcnn_corpus_new"):  # (absent from builds before the frame-index calls)
+            L.kcnn_corpus_new.restype = ctypes.c_void_p
+            L.kcnn_corpus_new.argtypes = [ctypes.c_void_p, MatrixDim, ctypes.c_void_p,
+                                          ctypes.c_int]
+            L.kcnn_corpus_free.argtypes = [ctypes.c_void_p]
+            L.kcnn_nnet_propagate_frames.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int]
+            L.kcnn_nnet_compute_prob_frames.argtypes = [
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.kcnn_nnet_free.argtypes = [ctypes.c_void_p]
         L.kcnn_nnet_component.restype = ctypes.c_void_p
         L.kcnn_nnet_component.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -878,6 +890,95 @@ class Nnet:
             int(bool(pad_input)), pp, np_, ctypes.c_float(prior_scale), int(bool(apply_log)),
             ctypes.byref(p), ctypes.byref(d)))
         return _device_view(p.value, d)
+
+    def PropagateFrames(self, corpus: "Corpus", frames):
+        """Propagate on a minibatch given as rows of a device-resident corpus
+        (kcnn_nnet_propagate_frames).  `frames`: host int32 indices of corpus
+        rows, any order, repeats allowed; example n is frames[n], and its
+        context window (clamped at its utterance's ends) is gathered on the
+        device.  Output row n, and the labels' rows of a following
+        BackpropXent, are example n.  Does not synchronise."""
+        fr = _frame_array(frames)
+        self._input = corpus  # the library borrows its matrix until Backprop
+        check(lib().kcnn_nnet_propagate_frames(
+            self._h, corpus._h, fr.ctypes.data_as(ctypes.c_void_p), len(fr)))
+
+    def ComputeProbFrames(self, corpus: "Corpus", frames, labels):
+        """ComputeProb on such a minibatch (kcnn_nnet_compute_prob_frames);
+        the labels' rows are 0 .. len(frames) - 1."""
+        fr = _frame_array(frames)
+        rows, cols, weights = _label_arrays(labels)
+        self._input = corpus
+        check(lib().kcnn_nnet_compute_prob_frames(
+            self._h, corpus._h, fr.ctypes.data_as(ctypes.c_void_p), len(fr),
+            rows.ctypes.data_as(ctypes.c_void_p), cols.ctypes.data_as(ctypes.c_void_p),
+            weights.ctypes.data_as(ctypes.c_void_p), len(rows)))
+
+
+def _frame_array(frames):
+    import numpy as np
+    try:
+        return np.ascontiguousarray(frames, np.int32).ravel()
+    except (OverflowError, ValueError) as e:
+        raise KcnnError(f"bad frame indices: {e}") from None
+
+
+class Corpus:
+    """A training corpus that stays on the device (kcnn_corpus): `feats`, the
+    [sum(lengths) x InputDim] device matrix of whole utterances stacked
+    row-wise (borrowed by the library, kept alive here), and `lengths`, their
+    frame counts (host ints).  Nnet.PropagateFrames / ComputeProbFrames take
+    minibatches of its rows."""
+
+    def __init__(self, feats, lengths):
+        import numpy as np
+        _ensure_init()
+        self._h = None
+        try:
+            lens = np.ascontiguousarray(lengths, np.int32).ravel()
+        except (OverflowError, ValueError) as e:
+            raise KcnnError(f"Corpus: bad lengths: {e}") from None
+        self.feats = feats
+        self.lengths = lens
+        h = lib().kcnn_corpus_new(ptr(feats), dim(feats),
+                                  lens.ctypes.data_as(ctypes.c_void_p), len(lens))
+        if not h:
+            raise KcnnError(lib().kcnn_last_error().decode(errors="replace"))
+        self._h = ctypes.c_void_p(h)
+
+    def NumRows(self) -> int:
+        return int(self.feats.shape[0])
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().kcnn_corpus_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def train_epoch(net: Nnet, corpus: Corpus, pdfs, minibatch_size: int, srand: int = 0):
+    """One epoch over the corpus, as nnet-shuffle-egs --srand followed by the
+    nnet-train loop: one numpy permutation of all corpus rows seeded by
+    `srand`, minibatches of `minibatch_size` (the remainder trained as a last,
+    smaller one), labels (n, pdfs[frames[n]], 1.0).  `pdfs`: one class per
+    corpus row (host).  Returns (objf, frames) of ObjfTotal(reset=True), which
+    synchronises; totals accumulated before the call are included."""
+    import numpy as np
+    pdfs = np.ascontiguousarray(pdfs, np.int32).ravel()
+    rows = corpus.NumRows()
+    if len(pdfs) != rows:
+        raise KcnnError(f"train_epoch: {len(pdfs)} pdfs for a corpus of {rows} rows")
+    if minibatch_size < 1:
+        raise KcnnError(f"train_epoch: minibatch_size {minibatch_size}")
+    order = np.random.default_rng(srand).permutation(rows).astype(np.int32)
+    for at in range(0, rows, minibatch_size):
+        frames = order[at:at + minibatch_size]
+        n = len(frames)
+        net.PropagateFrames(corpus, frames)
+        net.BackpropXent((np.arange(n, dtype=np.int32), pdfs[frames], np.ones(n, np.float32)))
+    return net.ObjfTotal(reset=True)
 
 
 def _device_view(addr, d: MatrixDim):

@@ -35,6 +35,14 @@ struct kcnn_nnet {
   explicit kcnn_nnet(Args &&...args) : stack(std::forward<Args>(args)...) {}
 };
 
+// A corpus that stays on the device: the caller's feature matrix (borrowed)
+// and its utterances' starts (frame-index.h).
+struct kcnn_corpus {
+  const float *feats = nullptr;
+  MatrixDim dim = {0, 0, 0};
+  kcnn::CorpusIndex index;
+};
+
 namespace {
 thread_local std::string g_err;
 
@@ -776,6 +784,44 @@ int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int
     matrix_out(n->stack.Compute(in, in_dim, lengths, num_utts, pad_input != 0, priors,
                                 num_priors, prior_scale, apply_log != 0),
                data, dim);
+  });
+}
+
+// ---- training from a device-resident corpus ----------------------------------------
+kcnn_corpus *kcnn_corpus_new(const float *feats, MatrixDim dim, const int32_t *lengths,
+                             int num_utts) {
+  kcnn_corpus *c = nullptr;
+  guard([&] {
+    std::unique_ptr<kcnn_corpus> made(new kcnn_corpus);
+    const std::string bad =
+        kcnn::build_corpus_index(lengths, num_utts, dim.rows, dim.cols, &made->index);
+    if (!bad.empty()) KALDI_ERR << "kcnn_corpus_new: " << bad;
+    if (feats == nullptr) KALDI_ERR << "kcnn_corpus_new: no feature matrix";
+    if (dim.stride < dim.cols)
+      KALDI_ERR << "kcnn_corpus_new: a row stride of " << dim.stride << " for " << dim.cols
+                << " columns";
+    made->feats = feats;
+    made->dim = dim;
+    c = made.release();
+  });
+  return c;
+}
+void kcnn_corpus_free(kcnn_corpus *c) { delete c; }
+
+int kcnn_nnet_propagate_frames(kcnn_nnet *n, const kcnn_corpus *corpus, const int32_t *frames,
+                               int num_frames) {
+  return guard([&] {
+    if (corpus == nullptr) KALDI_ERR << "kcnn_nnet_propagate_frames: no corpus";
+    n->stack.PropagateFrames(corpus->feats, corpus->dim, corpus->index, frames, num_frames);
+  });
+}
+int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
+                                  const int32_t *frames, int num_frames, const int32_t *rows,
+                                  const int32_t *cols, const float *weights, int num) {
+  return guard([&] {
+    if (corpus == nullptr) KALDI_ERR << "kcnn_nnet_compute_prob_frames: no corpus";
+    n->stack.ComputeProbFrames(corpus->feats, corpus->dim, corpus->index, frames, num_frames,
+                               rows, cols, weights, num);
   });
 }
 

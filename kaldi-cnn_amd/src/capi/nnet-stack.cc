@@ -283,13 +283,43 @@ static int checked_num_chunks(MatrixDim in_dim, int input_dim, int in_cs) {
   return in_dim.rows / in_cs;
 }
 
-void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count) {
-  num_chunks_ =
-      checked_num_chunks(in_dim, comps_[0].c->InputDim(), (int)acts_[0].offsets.size());
+void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count,
+                               const FrameList *fl) {
+  const int in_cs = (int)acts_[0].offsets.size();
+  num_chunks_ = fl ? fl->num : checked_num_chunks(in_dim, comps_[0].c->InputDim(), in_cs);
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   ForgetMinibatch();
-  prob_forward_ = whole_utts_ = false;
-  for (int i = 0; i < count; i++) {
+  prob_forward_ = whole_utts_ = frames_fused_ = false;
+  int first = 0;  // the component the loop starts at
+  if (fl != nullptr) {
+    // the offset of the input chunk's first frame from an example's own
+    const int in_first = -LeftContext();
+    if (const SpliceComponent *splice = comps_[0].splice) {
+      // the Splice reads the corpus itself: its output rows' offsets from the
+      // example's frame are the chunk offsets less the shift Init gave them
+      std::vector<int32> out_offsets(out(0).offsets);
+      for (int32 &o : out_offsets) o += in_first;
+      size_output(&out(0).value, num_chunks_ * (int)out_offsets.size(), splice->OutputDim());
+      CuProfileScope prof("kn_splice_frames_prop");
+      splice->PropagateFrames(acts_[0].value, &out(0).value, fl->examples, num_chunks_,
+                              out_offsets, in_first);
+      frames_fused_ = true;
+      first = 1;
+    } else {
+      // the window matrix, laid out as a caller's contiguous one would be
+      const int rows = num_chunks_ * in_cs, cols = in_dim.cols;
+      float *win = static_cast<float *>(
+          frames_input_.reserve(sizeof(float) * (size_t)rows * cols));
+      CuSubMatrix<BaseFloat> laid(win, rows, cols, cols);
+      {
+        CuProfileScope prof("kn_splice_frames_prop");
+        SpliceComponent::LayOutFrames(acts_[0].value, &laid, fl->examples, num_chunks_, in_cs,
+                                      in_first);
+      }
+      acts_[0].value.Borrow(win, rows, cols, cols);
+    }
+  }
+  for (int i = first; i < count; i++) {
     if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
     ChunkInfo ii = in_info(i), oi = out_info(i);
     auto hint = input_stats(i);
@@ -299,6 +329,58 @@ void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count) 
 
 void NnetStack::Propagate(const float *input, MatrixDim in_dim) {
   PropagateFirst(input, in_dim, NumComponents());
+}
+
+int NnetStack::CheckFrames(const FrameList &fl, const char *who) const {
+  if (fl.corpus == nullptr || fl.feats == nullptr) KALDI_ERR << who << ": no corpus";
+  if (fl.dim.cols != comps_[0].c->InputDim())
+    KALDI_ERR << who << ": a corpus of " << fl.dim.cols << " columns for a network of "
+              << comps_[0].c->InputDim();
+  if (fl.dim.rows != fl.corpus->rows())
+    KALDI_ERR << who << ": the corpus index covers " << fl.corpus->rows() << " rows, the matrix "
+              << "has " << fl.dim.rows;
+  std::string bad =
+      check_frames(*fl.corpus, fl.frames, fl.num, (int)acts_[0].offsets.size());
+  // every activation of the pass, the window matrix among them
+  for (size_t k = 0; bad.empty() && k < acts_.size(); k++)
+    bad = check_frames_matrix(k == 0 ? "the input" : "an activation",
+                              (int64_t)fl.num * (int64_t)acts_[k].offsets.size(),
+                              k == 0 ? comps_[0].c->InputDim() : comps_[k - 1].c->OutputDim());
+  if (!bad.empty()) KALDI_ERR << who << ": " << bad;
+  if (comps_[0].splice != nullptr) {
+    // gapped output offsets travel in the kernel's table of shorts
+    const std::vector<int32> &o = acts_[1].offsets;
+    if (o.back() - o.front() + 1 != (int32)o.size() &&
+        (o.size() > KN_SPLICE_MAX_TAB || acts_[0].offsets.back() > 32767))
+      KALDI_ERR << who << ": " << o.size() << " gapped output rows per example in a context of "
+                << acts_[0].offsets.back() << " frames exceed the first Splice's offset table";
+  }
+  return fl.num;
+}
+
+// The examples' triples -> pinned staging buffer -> device, on the library's
+// stream (before the labels and the forward, as ComputeProb stages its labels).
+void NnetStack::StageFrames(FrameList *fl) {
+  const size_t bytes = frame_triples_bytes(fl->num);
+  stage_frames(*fl->corpus, fl->frames, fl->num, frames_.Begin(bytes));
+  fl->examples = reinterpret_cast<const int32_t *>(
+      frames_.Commit(bytes, CuDevice::Instantiate().Stream()));
+}
+
+void NnetStack::PropagateFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
+                                const int32_t *frames, int num) {
+  FrameList fl = {feats, dim, &corpus, frames, num, nullptr};
+  CheckFrames(fl, "kcnn_nnet_propagate_frames");  // every check before any launch
+  StageFrames(&fl);
+  PropagateFirst(feats, dim, NumComponents(), &fl);
+}
+
+void NnetStack::ComputeProbFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
+                                  const int32_t *frames, int num, const int32_t *rows,
+                                  const int32_t *cols, const float *weights, int num_labels) {
+  FrameList fl = {feats, dim, &corpus, frames, num, nullptr};
+  ComputeProbOn(feats, dim, &fl, rows, cols, weights, num_labels,
+                "kcnn_nnet_compute_prob_frames");
 }
 
 const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
@@ -328,6 +410,10 @@ void NnetStack::MaterialisePoolDeriv(int i) {
 
 const CuMatrix<BaseFloat> &NnetStack::InputDeriv(int i) {
   KALDI_ASSERT(i >= 0 && i < NumComponents());
+  if (i == 0 && frames_fused_)
+    KALDI_ERR << "input derivative of component 0: after kcnn_nnet_propagate_frames a first "
+              << "SpliceComponent reads the corpus itself and its Backprop is not run (it has "
+              << "no parameters, and examples share corpus rows)";
   if (comps_[i].deriv_deferred) MaterialisePoolDeriv(i);
   return comps_[i].deriv;
 }
@@ -337,6 +423,9 @@ void NnetStack::BackpropComponent(int i, const float *out_deriv, MatrixDim od_di
   const int nc = NumComponents();
   KALDI_ASSERT(i >= 0 && i < nc);
   RequireTrainingForward("kcnn_nnet_backprop_component");
+  // a first Splice that gathered from the corpus: nothing to update, and its
+  // input derivative would be a window matrix of rows that examples share
+  if (i == 0 && frames_fused_) return;
   Comp &c = comps_[i];
   auto hint = input_stats(i);
   if (out(i).stale == kRecomputable) out(i).stale = kGone;
@@ -507,21 +596,29 @@ double *NnetStack::prob_totals() {
 
 void NnetStack::ComputeProb(const float *input, MatrixDim in_dim, const int32_t *rows,
                             const int32_t *cols, const float *weights, int num) {
+  ComputeProbOn(input, in_dim, nullptr, rows, cols, weights, num, "kcnn_nnet_compute_prob");
+}
+
+void NnetStack::ComputeProbOn(const float *input, MatrixDim in_dim, FrameList *fl,
+                              const int32_t *rows, const int32_t *cols, const float *weights,
+                              int num, const char *who) {
   const int nc = NumComponents();
   const Comp &last = comps_[nc - 1];
   // every check before any launch
-  const int N =
-      checked_num_chunks(in_dim, comps_[0].c->InputDim(), (int)acts_[0].offsets.size());
+  const int N = fl ? CheckFrames(*fl, who)
+                   : checked_num_chunks(in_dim, comps_[0].c->InputDim(),
+                                        (int)acts_[0].offsets.size());
   const int dim = last.c->OutputDim();
-  if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_nnet_compute_prob: bad label arrays";
+  if (num > 0 && weights == nullptr) KALDI_ERR << who << ": bad label arrays";
   const std::string bad = check_labels(rows, cols, num, N, dim, true);
-  if (!bad.empty()) KALDI_ERR << "kcnn_nnet_compute_prob: " << bad;
+  if (!bad.empty()) KALDI_ERR << who << ": " << bad;
   const bool fused = last.softmax != nullptr && !cnsl::nnet0::LiteralPath();
   // The labels go first: staging waits for the last call's copy to have left
   // the pinned buffer, and behind the forward pass that wait would be for the
-  // whole of the last call, every call.
+  // whole of the last call, every call.  (The examples before them.)
+  if (fl) StageFrames(fl);
   const DeviceLabels lab = StageLabels(rows, cols, weights, num, N);
-  PropagateFirst(input, in_dim, fused ? nc - 1 : nc);
+  PropagateFirst(input, in_dim, fused ? nc - 1 : nc, fl);
   prob_forward_ = true;
   if (fused) out(nc - 1).stale = kRecomputable;  // the Softmax did not run
   // the matrix the sums are taken from: the Softmax's input, or the last output
@@ -572,6 +669,7 @@ void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
   if (clamp_in_splice) acts_[0].utt_rows = in_dim.rows;
   ForgetMinibatch();
   prob_forward_ = whole_utts_ = true;
+  frames_fused_ = false;
   if (pad_input && ext > 0 && !clamp_in_splice) {
     // component 0 is row-wise: the clamped frames laid out by a one-slot Splice
     size_output(&padded_input_, acts_[0].utt_rows, in_dim.cols);

@@ -6,7 +6,9 @@
 // and what follows a training iteration: the <Nnet> file (Nnet::Read / Write),
 // the scaled, Dropout-free copy (nnet-am-copy), ComputeProb
 // (nnet-compute-prob) and Compute, the whole-utterance forward pass of
-// upstream NnetComputer (nnet-am-compute, the decodable).
+// upstream NnetComputer (nnet-am-compute, the decodable); and what comes
+// before one: PropagateFrames, a minibatch as rows of a corpus that stays on
+// the device (nnet-get-egs and nnet-shuffle-egs without the window matrices).
 // Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
 // error codes.
 #ifndef KCNN_CAPI_NNET_STACK_H_
@@ -23,6 +25,7 @@
 #include "../kaldi-lite/cu-matrix.h"
 #include "../nnet0/nnet-component-nnet0.h"
 #include "../nnet2/nnet-component.h"
+#include "frame-index.h"
 
 struct kcnn_component {
   kaldi::nnet2::Component *c;
@@ -149,6 +152,26 @@ class NnetStack {
                                      int num_utts, bool pad_input, const float *priors,
                                      int num_priors, float prior_scale, bool apply_log);
 
+  // Propagate on a minibatch given as `num` rows (HOST indices, any order,
+  // repeats allowed) of a corpus that stays on the device: `feats` holds whole
+  // utterances stacked row-wise, `corpus` their starts (frame-index.h).
+  // Example n, corpus row r in utterance rows [s, e), has the input chunk
+  // clamp(r + o, s, e - 1) for the input chunk's offsets o = -L .. R: the
+  // window matrix Propagate would be given.  From component 0's output upwards
+  // the pass is Propagate's, num chunks.  A first SpliceComponent gathers its
+  // output straight from the corpus (the window matrix is never stored;
+  // Output(-1) is the borrowed corpus) and its Backprop is then skipped: it has
+  // no parameters, and InputDeriv(0) throws.  Any other component 0 gets the
+  // window matrix laid out by the same kernel into a matrix of the stack's
+  // (Output(-1)) and runs as after Propagate.  Every check (frames, indices,
+  // columns, sizes) precedes every launch; the examples are staged first.
+  void PropagateFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
+                       const int32_t *frames, int num);
+  // ComputeProb on such a minibatch; leaves the state ComputeProb leaves.
+  void ComputeProbFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
+                         const int32_t *frames, int num, const int32_t *rows,
+                         const int32_t *cols, const float *weights, int num_labels);
+
  private:
   struct Comp {
     std::unique_ptr<kaldi::nnet2::Component> c;
@@ -203,7 +226,8 @@ class NnetStack {
   // BackpropXent: the label list's pinned staging buffer and its device image
   // (xent-labels.h), the event after which the staging buffer may be
   // rewritten, and the fp64 {objective, weight} totals on the device.
-  // Compute stages its utterance starts and prior offsets through another.
+  // Compute stages its utterance starts and prior offsets through another,
+  // PropagateFrames its example triples (frame-index.h) through a third.
   struct LabelStaging {
     void *host = nullptr;
     size_t host_bytes = 0;
@@ -224,8 +248,26 @@ class NnetStack {
 
   // the constructors' shared tail: the checks, the kinds, the chunk offsets
   void Init(std::vector<std::unique_ptr<kaldi::nnet2::Component>> parsed);
-  // Propagate's checks and its first `count` components
-  void PropagateFirst(const float *in, MatrixDim in_dim, int count);
+  // A minibatch of corpus rows (PropagateFrames): the caller's arguments, and
+  // `examples`, their staged triples on the device once StageFrames has run.
+  struct FrameList {
+    const float *feats;
+    MatrixDim dim;
+    const CorpusIndex *corpus;
+    const int32_t *frames;
+    int num;
+    const int32_t *examples;
+  };
+  // Propagate's checks and its first `count` components; with `fl` (checked
+  // and staged) the input is its minibatch and (in, in_dim) the corpus matrix
+  void PropagateFirst(const float *in, MatrixDim in_dim, int count,
+                      const FrameList *fl = nullptr);
+  // PropagateFrames' checks; returns the number of examples
+  int CheckFrames(const FrameList &fl, const char *who) const;
+  void StageFrames(FrameList *fl);
+  // ComputeProb and ComputeProbFrames (fl != NULL)
+  void ComputeProbOn(const float *in, MatrixDim in_dim, FrameList *fl, const int32_t *rows,
+                     const int32_t *cols, const float *weights, int num, const char *who);
   void RequireTrainingForward(const char *who) const;
   // the checked labels staged on the device (xent-labels.h)
   struct DeviceLabels {
@@ -266,6 +308,12 @@ class NnetStack {
   LabelStaging utts_;                   // Compute's utterance starts and prior offsets
   CuMatrix<BaseFloat> padded_input_;    // Compute's clamped input frames, when laid out
   CuMatrix<BaseFloat> loglikes_;        // Compute's result with apply_log
+  // the last forward was PropagateFrames' through a first Splice: component
+  // 0's input is the corpus, not a window matrix, and it has no Backprop
+  bool frames_fused_ = false;
+  LabelStaging frames_;                 // PropagateFrames' example triples
+  // its window matrix when laid out, contiguous as a caller's would be
+  kaldi::CuBuffer frames_input_;
 };
 
 }  // namespace kcnn

@@ -930,6 +930,53 @@ void SpliceComponent::PropagateRagged(const CuMatrixBase<BaseFloat> &in,
       kn_splice_ragged_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), utt_start, g, NS()));
 }
 
+void SpliceComponent::PropagateFrames(const CuMatrixBase<BaseFloat> &corpus,
+                                      CuMatrixBase<BaseFloat> *out, const int32 *examples,
+                                      int32 num, const std::vector<int32> &out_offsets,
+                                      int32 in_first) const {
+  KALDI_ASSERT(corpus.NumCols() == input_dim_ && out->NumCols() == OutputDim());
+  const int32 out_cs = (int32)out_offsets.size();
+  KALDI_ASSERT(out_cs > 0);
+  kn_frames_splice_geom g;
+  g.num_examples = num;
+  g.out_cs = out_cs;
+  g.const_dim = const_component_dim_;
+  g.dim = input_dim_ - const_component_dim_;
+  g.num_splice = (int)context_.size();
+  for (int c = 0; c < g.num_splice; c++) g.context[c] = context_[c];
+  g.const_first = in_first;
+  g.out_first = out_offsets.front();
+  g.table = out_offsets.back() - out_offsets.front() + 1 == out_cs ? 0 : 1;
+  if (g.table) {
+    if (out_cs > KN_SPLICE_MAX_TAB)
+      KALDI_ERR << "SpliceComponent: " << out_cs << " output rows per example exceed the "
+                << "offset table (" << KN_SPLICE_MAX_TAB << ")";
+    for (int32 oi = 0; oi < out_cs; oi++) {
+      KALDI_ASSERT(out_offsets[oi] >= -32768 && out_offsets[oi] <= 32767);
+      g.out_offset[oi] = (short)out_offsets[oi];
+    }
+  }
+  CNSL_SAFE_CALL(kn_splice_frames_prop(corpus.Data(), corpus.Dim(), out->Data(), out->Dim(),
+                                       examples, g, NS()));
+}
+
+void SpliceComponent::LayOutFrames(const CuMatrixBase<BaseFloat> &corpus,
+                                   CuMatrixBase<BaseFloat> *out, const int32 *examples,
+                                   int32 num, int32 chunk_rows, int32 in_first) {
+  KALDI_ASSERT(corpus.NumCols() == out->NumCols() && chunk_rows > 0);
+  kn_frames_splice_geom g;
+  g.num_examples = num;
+  g.out_cs = chunk_rows;
+  g.const_dim = 0;
+  g.dim = corpus.NumCols();
+  g.num_splice = 1;
+  g.context[0] = 0;
+  g.const_first = g.out_first = in_first;
+  g.table = 0;
+  CNSL_SAFE_CALL(kn_splice_frames_prop(corpus.Data(), corpus.Dim(), out->Data(), out->Dim(),
+                                       examples, g, NS()));
+}
+
 void SpliceComponent::Backprop(const ChunkInfo &in_info, const ChunkInfo &out_info,
                                const CuMatrixBase<BaseFloat> &,
                                const CuMatrixBase<BaseFloat> &,

@@ -324,6 +324,21 @@ class SpliceComponent : public Component {
   void PropagateRagged(const CuMatrixBase<BaseFloat> &in, CuMatrixBase<BaseFloat> *out,
                        const int32 *utt_start, int32 num_utts, int32 total, int32 in_ext,
                        int32 out_ext, int32 pad_left) const;
+  // Propagate on a minibatch given as rows of a device-resident corpus
+  // (kn_splice_frames_prop, nnet-kernels.h): `corpus` holds whole utterances
+  // stacked row-wise, examples is the DEVICE table of num {row, first row,
+  // last row of its utterance} triples.  *out holds out_offsets.size() rows an
+  // example; row oi is the frame out_offsets[oi] frames from the example's own
+  // (ascending), and the input chunk Propagate would be given starts
+  // in_first (<= 0) frames from it.  A read past an utterance's end repeats
+  // its first (last) frame.  LayOutFrames: the same pass with one context
+  // slot and no const tail writes the input chunk itself, chunk_rows rows an
+  // example from in_first on, for a stack whose component 0 is not a Splice.
+  void PropagateFrames(const CuMatrixBase<BaseFloat> &corpus, CuMatrixBase<BaseFloat> *out,
+                       const int32 *examples, int32 num,
+                       const std::vector<int32> &out_offsets, int32 in_first) const;
+  static void LayOutFrames(const CuMatrixBase<BaseFloat> &corpus, CuMatrixBase<BaseFloat> *out,
+                           const int32 *examples, int32 num, int32 chunk_rows, int32 in_first);
   virtual bool BackpropNeedsInput() const { return false; }
   virtual bool BackpropNeedsOutput() const { return false; }
   virtual Component *Copy() const;

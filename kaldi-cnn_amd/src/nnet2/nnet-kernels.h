@@ -78,6 +78,31 @@ typedef struct {
 int kn_splice_ragged_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                           const int *utt_start, kn_ragged_splice_geom geom, kcnn_stream_t st);
 
+/* SpliceComponent::Propagate on a minibatch given as rows of a corpus that
+ * stays on the device (whole utterances stacked row-wise in `feats`): the
+ * window matrix kn_splice_prop would read is never stored.  examples (DEVICE,
+ * 3 * num_examples ints) holds per example n {r, lo, hi}: its corpus row and
+ * the first and last row of its utterance.  Output row (n, oi) takes, for
+ * context slot c, corpus row clamp(r + out_offset(oi) + context[c], lo, hi),
+ * out_offset(oi) being the frame offset of output row oi from the example's
+ * own frame: out_first + oi, or out_offset[oi] with table = 1 (a gapped
+ * context deeper in the stack; out_cs <= KN_SPLICE_MAX_TAB).  The const_dim
+ * tail follows kn_splice_prop's rule, the input chunk's row oi: corpus row
+ * clamp(r + const_first + oi, lo, hi), const_first the offset of the input
+ * chunk's first frame.  num_splice = 1, context = {0}, out_cs the input chunk
+ * lays the window matrix itself out.  Rows are clamped into `feats` at last,
+ * so triples that disagree with the matrix still read inside it. */
+typedef struct {
+  int num_examples, out_cs;
+  int dim, const_dim, num_splice;
+  int context[KN_SPLICE_MAX_CONTEXT];
+  int const_first, out_first;
+  int table;
+  short out_offset[KN_SPLICE_MAX_TAB];
+} kn_frames_splice_geom;
+int kn_splice_frames_prop(const float *feats, MatrixDim dim, float *out, MatrixDim out_dim,
+                          const int *examples, kn_frames_splice_geom geom, kcnn_stream_t st);
+
 /* fp64 stat vectors of NonlinearComponent (Scale/Add/UpdateStats):
  * y = beta * y + alpha * x  (x may be NULL: y = beta * y). */
 int kn_dvec_update(double *y, const double *x, double alpha, double beta, int n,

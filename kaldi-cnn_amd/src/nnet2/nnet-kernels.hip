@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 
 #include "nnet-kernels.h"
 #include "../cnslmat/hip-util.h"
@@ -227,6 +228,72 @@ __global__ __launch_bounds__(256) void splice_ragged_kernel(const float *__restr
   }
 }
 
+// The frame-index form (kn_splice_frames_prop), shaped as the ragged kernel:
+// groups of `rpb` consecutive output rows to a block; one thread per row loads
+// the {row, first, last} triple of the row's example, staged by the host, so
+// nothing is searched here, and leaves the corpus row before the context
+// offset, the utterance's bounds and the const tail's row in LDS; then all 256
+// threads copy the group's V-float units.
+struct FramesArgs {
+  kn_frames_splice_geom g;
+  int in_rows, out_rows, rpb;
+  FastDiv div_units, div_dim, div_ocs;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void splice_frames_kernel(const float *__restrict__ in,
+                                                            int64_t is, float *__restrict__ out,
+                                                            int64_t os,
+                                                            const int *__restrict__ examples,
+                                                            FramesArgs a) {
+  __shared__ int s_row[kRaggedMaxRows], s_lo[kRaggedMaxRows], s_hi[kRaggedMaxRows],
+      s_const[kRaggedMaxRows];
+  const kn_frames_splice_geom &g = a.g;
+  const int units = (g.num_splice * g.dim + g.const_dim) / V;
+  const int ngroups = (a.out_rows + a.rpb - 1) / a.rpb;
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int r0 = grp * a.rpb;
+    const int nr = min(a.rpb, a.out_rows - r0);
+    __syncthreads();  // the last group's readers are done
+    if ((int)threadIdx.x < nr) {
+      uint32_t n, oi;
+      a.div_ocs.divmod((uint32_t)(r0 + (int)threadIdx.x), n, oi);
+      const int *ex = examples + 3 * (int64_t)n;
+      const int r = ex[0];
+      s_lo[threadIdx.x] = ex[1];
+      s_hi[threadIdx.x] = ex[2];
+      s_row[threadIdx.x] = r + (g.table ? (int)g.out_offset[oi] : g.out_first + (int)oi);
+      s_const[threadIdx.x] = r + g.const_first + (int)oi;
+    }
+    __syncthreads();
+    const int n = nr * units;
+    for (int e = threadIdx.x; e < n; e += 256) {
+      uint32_t lr, cu;
+      a.div_units.divmod((uint32_t)e, lr, cu);
+      const int col = (int)cu * V;
+      int row, icol;
+      if (col < g.num_splice * g.dim) {
+        uint32_t c, d;
+        a.div_dim.divmod((uint32_t)col, c, d);
+        row = s_row[lr] + g.context[c];
+        icol = (int)d;
+      } else {
+        row = s_const[lr];
+        icol = g.dim + (col - g.num_splice * g.dim);
+      }
+      row = max(s_lo[lr], min(row, s_hi[lr]));
+      // (triples that disagree with the matrix still read inside `in`)
+      row = max(0, min(row, a.in_rows - 1));
+      const float *src = in + (int64_t)row * is + icol;
+      float *dst = out + (int64_t)(r0 + (int)lr) * os + col;
+      if constexpr (V == 4)
+        *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
+      else
+        *dst = *src;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void splice_backprop_kernel(
     const float *__restrict__ od, int64_t ods, float *__restrict__ id, int64_t ids,
     SpliceArgs a, int64_t total) {
@@ -413,6 +480,54 @@ int kn_splice_ragged_prop(const float *in, MatrixDim in_dim, float *out, MatrixD
   else
     hipLaunchKernelGGL(splice_ragged_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), in,
                        (int64_t)in_dim.stride, out, (int64_t)out_dim.stride, utt_start, a);
+  return kcnn::launch_status();
+}
+
+int kn_splice_frames_prop(const float *feats, MatrixDim dim, float *out, MatrixDim out_dim,
+                          const int *examples, kn_frames_splice_geom g, kcnn_stream_t st) {
+  if (feats == nullptr || out == nullptr || examples == nullptr || g.num_examples <= 0 ||
+      g.out_cs <= 0 || g.dim <= 0 || g.const_dim < 0 || g.num_splice <= 0 ||
+      g.num_splice > KN_SPLICE_MAX_CONTEXT || dim.rows <= 0 ||
+      (int64_t)g.num_examples * g.out_cs != out_dim.rows || dim.cols != g.dim + g.const_dim ||
+      out_dim.cols != g.num_splice * g.dim + g.const_dim || dim.stride < dim.cols ||
+      out_dim.stride < out_dim.cols || (g.table && g.out_cs > KN_SPLICE_MAX_TAB))
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)out_dim.rows * out_dim.cols >= ((int64_t)1 << 31) ||
+      (int64_t)dim.rows * dim.cols >= ((int64_t)1 << 31))
+    return (int)hipErrorInvalidValue;
+  // a corpus row plus the largest offset stays an int
+  int64_t reach = std::llabs((long long)g.const_first) + g.out_cs;
+  if (g.table)
+    for (int oi = 0; oi < g.out_cs; oi++)
+      reach = std::max<int64_t>(reach, std::abs((int)g.out_offset[oi]));
+  else
+    reach = std::max<int64_t>(reach, std::llabs((long long)g.out_first) + g.out_cs);
+  int64_t ctx = 0;
+  for (int c = 0; c < g.num_splice; c++)
+    ctx = std::max<int64_t>(ctx, std::llabs((long long)g.context[c]));
+  if ((int64_t)dim.rows + reach + ctx >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+  const bool vec4 = g.dim % 4 == 0 && g.const_dim % 4 == 0 && dim.stride % 4 == 0 &&
+                    out_dim.stride % 4 == 0 && (uintptr_t)feats % 16 == 0 &&
+                    (uintptr_t)out % 16 == 0;
+  const int v = vec4 ? 4 : 1;
+  const int units = out_dim.cols / v;
+  FramesArgs a;
+  a.g = g;
+  a.in_rows = dim.rows;
+  a.out_rows = out_dim.rows;
+  // about four units a thread and group, as the ragged form
+  a.rpb = std::max(1, std::min(kRaggedMaxRows, 1024 / units));
+  a.div_units = FastDiv((uint32_t)units);
+  a.div_dim = FastDiv((uint32_t)g.dim);
+  a.div_ocs = FastDiv((uint32_t)g.out_cs);
+  const int ngroups = (out_dim.rows + a.rpb - 1) / a.rpb;
+  const dim3 grid((unsigned)std::min(ngroups, 256 * 32));
+  if (vec4)
+    hipLaunchKernelGGL(splice_frames_kernel<4>, grid, dim3(256), 0, kcnn::as_stream(st), feats,
+                       (int64_t)dim.stride, out, (int64_t)out_dim.stride, examples, a);
+  else
+    hipLaunchKernelGGL(splice_frames_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), feats,
+                       (int64_t)dim.stride, out, (int64_t)out_dim.stride, examples, a);
   return kcnn::launch_status();
 }
 
