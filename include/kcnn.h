@@ -289,6 +289,13 @@ int kcnn_component_conv_flip_branch(const kcnn_component *c);
 int kcnn_component_set_dropout_scale(kcnn_component *c, float scale);
 int kcnn_component_dropout_seed(const kcnn_component *c, uint64_t *seed);
 int kcnn_component_set_dropout_seed(kcnn_component *c, uint64_t seed);
+/* The row of the minibatch that row 0 of Propagate's input is (default 0):
+ * the mask of row r is the one drawn for row offset + r, so data-parallel
+ * ranks that share a seed and a call count draw the masks of their own shards
+ * of one global minibatch, and offset 0 draws what a whole minibatch draws.
+ * A Propagate with offset + rows > 2^32 is an error that runs no kernel.  The
+ * offset is not written to files and a copy starts at 0. */
+int kcnn_component_set_dropout_row_offset(kcnn_component *c, uint64_t offset);
 
 /* CuMatrix::CompObjfAndDeriv (reference cudamatrix/cu-matrix.h:624-637) for
  * num HOST elements {rows[i], cols[i], weights[i]} with no repeated (row,
@@ -385,9 +392,37 @@ int kcnn_nnet_backprop(kcnn_nnet *n, const float *out_deriv, MatrixDim od_dim);
  * kcnn_set_literal_path(1) asks for the literal sequence. */
 int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
                             const float *weights, int num, int skip_first_dx);
+/* The first half of kcnn_nnet_backprop_xent, for a caller that runs the
+ * backward itself (data parallelism: per component, the gradients all-reduced
+ * before the update): the same label contract and the same checks before any
+ * launch; the labels are staged, the objective and the weight added to the
+ * totals of kcnn_nnet_objf_total, and the output derivative is left where
+ * kcnn_nnet_backprop_component / _backprop_split read it.  *first is the
+ * component the backward starts at; *out_deriv / *od_dim are what to pass to
+ * those calls (the library's matrix, valid until the next call of this
+ * function).  With a last SoftmaxComponent, unless kcnn_set_literal_path(1),
+ * the fused kernel has already written that Softmax's input derivative:
+ * *first is num_components - 2 (-1 for a network of one Softmax: nothing is
+ * left to run), *out_deriv is NULL with a zero dim, since no component below
+ * the last reads it, and kcnn_nnet_backprop_component / _backprop_split of
+ * the LAST component are an error until the next forward pass -- its output
+ * derivative was never formed.  Otherwise *first is num_components - 1.
+ * Does not synchronise. */
+int kcnn_nnet_xent_deriv(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
+                         const float *weights, int num, int *first, const float **out_deriv,
+                         MatrixDim *od_dim);
+/* kcnn_component_set_dropout_row_offset on every DropoutComponent of the
+ * stack; nothing for a stack without one.  Holds until it is set again. */
+int kcnn_nnet_set_row_offset(kcnn_nnet *n, uint64_t offset);
+/* Every DropoutComponent of the stack counts one Propagate call without
+ * running one (the mask is a function of the call number): a data-parallel
+ * rank whose shard of a minibatch is empty runs no forward pass, and with this
+ * call its next masks are still those of the other ranks' call number. */
+int kcnn_nnet_skip_dropout_call(kcnn_nnet *n);
 /* out[0] = the objective, out[1] = the weight accumulated by
- * kcnn_nnet_backprop_xent since the last reset (their ratio is the average
- * log-probability per frame); reset != 0 zeroes them.  Synchronises. */
+ * kcnn_nnet_backprop_xent / _xent_deriv since the last reset (their ratio is
+ * the average log-probability per frame); reset != 0 zeroes them.
+ * Synchronises. */
 int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset);
 /* nnet-compute-prob on one minibatch: the forward pass over `in` and, for num
  * HOST label elements under the contract of kcnn_nnet_backprop_xent (checked

@@ -89,6 +89,14 @@ def lib():
             L.kcnn_nnet_compute_prob_frames.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(L, "kcnn_nnet_xent_deriv"):  # (absent from builds before the DP xent step)
+            L.kcnn_nnet_xent_deriv.argtypes = [
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            L.kcnn_nnet_skip_dropout_call.argtypes = [ctypes.c_void_p]
+            L.kcnn_nnet_set_row_offset.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+            L.kcnn_component_set_dropout_row_offset.argtypes = [ctypes.c_void_p,
+                                                                ctypes.c_uint64]
         L.kcnn_nnet_free.argtypes = [ctypes.c_void_p]
         L.kcnn_nnet_component.restype = ctypes.c_void_p
         L.kcnn_nnet_component.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -650,6 +658,14 @@ class Component:
         mask of Propagate call k is a function of (seed, k, row, column)."""
         check(lib().kcnn_component_set_dropout_seed(self._h, ctypes.c_uint64(seed)))
 
+    def SetDropoutRowOffset(self, offset: int):
+        """The row of the minibatch that row 0 of Propagate's input is
+        (kcnn_component_set_dropout_row_offset): the mask of row r is drawn
+        for row offset + r.  Not written to files; a Copy() starts at 0."""
+        if not 0 <= int(offset) < 1 << 64:
+            raise KcnnError(f"SetDropoutRowOffset: offset {offset}")
+        check(lib().kcnn_component_set_dropout_row_offset(self._h, ctypes.c_uint64(int(offset))))
+
 
 def _label_arrays(labels):
     """labels: a sequence of (row, col, weight) triples (the reference's
@@ -822,9 +838,41 @@ class Nnet:
             cols.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
             len(rows), int(skip_first_dx)))
 
+    def XentDeriv(self, labels):
+        """The first half of BackpropXent (kcnn_nnet_xent_deriv), for a caller
+        that runs the backward itself: checks and stages `labels`, adds to the
+        totals ObjfTotal returns, and leaves the output derivative in the
+        library.  Returns (first, out_deriv): the component the backward
+        starts at, and what to pass to BackpropComponent / BackpropSplit as
+        out_deriv -- a torch view, or None when a last Softmax took the fused
+        kernel (first is then NumComponents() - 2, and a backprop call of the
+        last component raises).  Does not synchronise."""
+        rows, cols, weights = _label_arrays(labels)
+        first = ctypes.c_int()
+        p = ctypes.c_void_p()
+        d = MatrixDim()
+        check(lib().kcnn_nnet_xent_deriv(
+            self._h, rows.ctypes.data_as(ctypes.c_void_p),
+            cols.ctypes.data_as(ctypes.c_void_p), weights.ctypes.data_as(ctypes.c_void_p),
+            len(rows), ctypes.byref(first), ctypes.byref(p), ctypes.byref(d)))
+        return first.value, (_device_view(p.value, d) if p.value else None)
+
+    def SetRowOffset(self, offset: int):
+        """Component.SetDropoutRowOffset on every DropoutComponent of the
+        stack (kcnn_nnet_set_row_offset); holds until set again."""
+        if not 0 <= int(offset) < 1 << 64:
+            raise KcnnError(f"SetRowOffset: offset {offset}")
+        check(lib().kcnn_nnet_set_row_offset(self._h, ctypes.c_uint64(int(offset))))
+
+    def SkipDropoutCall(self):
+        """Every DropoutComponent counts a Propagate call that did not run
+        here (kcnn_nnet_skip_dropout_call): a data-parallel rank with an empty
+        shard keeps the call number, and so the masks, of the others."""
+        check(lib().kcnn_nnet_skip_dropout_call(self._h))
+
     def ObjfTotal(self, reset=False):
         """(sum of weight * log-probability, sum of weight) over the
-        BackpropXent calls since the last reset; synchronises."""
+        BackpropXent / XentDeriv calls since the last reset; synchronises."""
         out = (ctypes.c_double * 2)()
         check(lib().kcnn_nnet_objf_total(self._h, out, int(bool(reset))))
         return out[0], out[1]

@@ -28,6 +28,15 @@ itself divides by its local row count, :767).
 BackpropComponent(i, out_deriv, mode, grad) and BackpropSplit(i, out_deriv,
 grad, skip_first_dx, between) -- kcnn.Nnet on the GPU; the tests drive the
 same function with a CPU stand-in over gloo.
+
+dp_train_step takes a caller's output derivative (the bench stacks).  The
+steps from labels -- dp_xent_step, dp_xent_step_frames, dp_train_epoch --
+train whole networks: SetRowOffset(shard start) makes a DropoutComponent draw
+the masks of the GLOBAL rows, XentDeriv leaves the cross-entropy derivative
+for the same per-component backward, and the objective totals are summed over
+the ranks (dp_objf_total, dp_prob_total).  For these `net` also has
+SetRowOffset(offset) and XentDeriv(labels) -> (first, out_deriv).
+NonlinearComponent statistics stay per replica: each covers its own shard.
 """
 from __future__ import annotations
 
@@ -76,8 +85,10 @@ def gradient_buffers(net, alloc, own=None):
     return GradientBuffers(net, alloc, own)
 
 
-def dp_train_step(net, x, out_deriv, grads, dist, frames_global, mark=None):
-    """Propagate + backprop + all-reduced update of one row shard.
+def _backward_update(net, first, out_deriv, grads, dist, frames_global, mark=None):
+    """The tail every step shares: the backward from component `first` down
+    (None: this rank's shard is empty and no kernel of the network runs), each
+    gradient's all-reduce, and the update with the global frame count.
 
     mode 1 = data gradient and parameter gradient (no update), mode 2 = data
     gradient only, mode 3 = parameter gradient only
@@ -85,13 +96,16 @@ def dp_train_step(net, x, out_deriv, grads, dist, frames_global, mark=None):
     computed too, as upstream NnetUpdater does and as the 1-GPU step
     (Nnet.Backprop) does, so N=1 and N>1 do the same work.
 
-    mark(name), when given, is called on the host at "wait_begin" (all
-    collectives issued, the backward queued) and "wait_end" (the compute
-    stream now waits for every collective): bench.py records stream events
-    there to measure the all-reduce time the step did not hide."""
-    net.Propagate(x)
+    The collectives and their order depend on `grads` alone, so a rank with
+    an empty shard issues the same ones over zeroed buffers."""
     pending = []
-    for i in reversed(range(net.NumComponents())):
+    if first is None:
+        for i in reversed(grads.large):
+            grads[i].zero_()
+            pending.append(([i], dist.all_reduce(grads[i], async_op=True)))
+        if grads.bucket is not None:
+            grads.bucket.zero_()
+    for i in reversed(range(0 if first is None else first + 1)):
         if i in grads.large and getattr(net.components[i], "SplitGradient", lambda: True)():
             # the gradient, its all-reduce started, then the data gradient
             # (one library call: both GEMMs' statistics from one pass)
@@ -122,3 +136,148 @@ def dp_train_step(net, x, out_deriv, grads, dist, frames_global, mark=None):
     for ids, _ in pending:
         for i in ids:
             net.components[i].ApplyGradient(grads[i], frames_global)
+
+
+def dp_train_step(net, x, out_deriv, grads, dist, frames_global, mark=None):
+    """Propagate + backprop from a caller's output derivative + all-reduced
+    update of one row shard (_backward_update from the last component).
+
+    mark(name), when given, is called on the host at "wait_begin" (all
+    collectives issued, the backward queued) and "wait_end" (the compute
+    stream now waits for every collective): bench.py records stream events
+    there to measure the all-reduce time the step did not hide."""
+    net.Propagate(x)
+    _backward_update(net, net.NumComponents() - 1, out_deriv, grads, dist, frames_global, mark)
+
+
+def shard(n, world, rank):
+    """Rank `rank`'s contiguous rows [lo, hi) of a global minibatch of n rows:
+    the shards partition [0, n) and their sizes differ by at most one (a
+    minibatch smaller than the world leaves some of them empty)."""
+    return n * rank // world, n * (rank + 1) // world
+
+
+def _xent_tail(net, forward, labels, grads, dist, frames_global, row_offset, mark):
+    if forward is None:
+        # An empty shard: no kernel of the network runs, but the dropout masks
+        # of the ranks' next minibatch are those of one Propagate call number,
+        # so this rank counts the call it did not make.
+        getattr(net, "SkipDropoutCall", lambda: None)()
+        _backward_update(net, None, None, grads, dist, frames_global, mark)
+        return
+    net.SetRowOffset(row_offset)
+    forward()
+    first, out_deriv = net.XentDeriv(labels)
+    _backward_update(net, first, out_deriv, grads, dist, frames_global, mark)
+
+
+def dp_xent_step(net, x, labels, grads, dist, frames_global, row_offset, mark=None):
+    """One training step from labels on this rank's shard `x` of a global
+    minibatch of `frames_global` rows, of which x's row 0 is row `row_offset`
+    (shard()): dropout masks drawn for the global rows, Propagate, the
+    cross-entropy derivative (Nnet.XentDeriv; the labels' rows are local to
+    the shard), then _backward_update.  With the replicas' dropout seeds equal
+    (sync_dropout) the masks are those one process draws on the whole
+    minibatch.  frames_global is the ROW count of the global minibatch, not
+    the labels' weight: the reference's Update divides by N.  A rank whose
+    shard has no rows runs no kernel of the network; it zeroes its gradient
+    buffers, joins the same collectives in the same order and applies the
+    update, so the replicas stay identical."""
+    forward = (lambda: net.Propagate(x)) if x.shape[0] > 0 else None
+    _xent_tail(net, forward, labels, grads, dist, frames_global, row_offset, mark)
+
+
+def dp_xent_step_frames(net, corpus, frames, labels, grads, dist, frames_global, row_offset,
+                        mark=None):
+    """dp_xent_step with Nnet.PropagateFrames as the forward: `frames` are
+    this rank's shard of the global minibatch's corpus rows.  Every rank holds
+    the whole corpus."""
+    forward = (lambda: net.PropagateFrames(corpus, frames)) if len(frames) > 0 else None
+    _xent_tail(net, forward, labels, grads, dist, frames_global, row_offset, mark)
+
+
+def _host_device(dist):
+    """Where the small host-side collectives live: RCCL reduces device
+    tensors only."""
+    return "cuda" if getattr(dist, "get_backend", lambda: None)() == "nccl" else "cpu"
+
+
+def _dropouts(net):
+    return [c for c in net.components
+            if getattr(c, "Type", lambda: "")() == "DropoutComponent"]
+
+
+def sync_dropout(net, dist):
+    """Rank 0's dropout seeds to every replica.  SetDropoutSeed restarts the
+    call count, so the counts agree too: call it once before training."""
+    import numpy as np
+    import torch
+    drops = _dropouts(net)
+    if not drops:
+        return
+    seeds = np.array([c.DropoutSeed() for c in drops], np.uint64)
+    t = torch.from_numpy(seeds.view(np.int64).copy()).to(_host_device(dist))
+    dist.broadcast(t, src=0)
+    for c, s in zip(drops, t.cpu().numpy().view(np.uint64)):
+        c.SetDropoutSeed(int(s))
+
+
+def _all_reduced(values, dist):
+    import torch
+    t = torch.tensor(values, dtype=torch.float64, device=_host_device(dist))
+    dist.all_reduce(t)
+    return tuple(t.tolist())
+
+
+def dp_objf_total(net, dist, reset=False):
+    """Nnet.ObjfTotal (synchronises) summed over the ranks: (objective,
+    weight) of the global minibatches since the last reset."""
+    return _all_reduced(net.ObjfTotal(reset), dist)
+
+
+def dp_prob_total(net, dist, reset=False):
+    """Nnet.ProbTotal (synchronises) summed over the ranks."""
+    return _all_reduced(net.ProbTotal(reset), dist)
+
+
+def dp_compute_prob_frames(net, corpus, frames, labels, dist):
+    """Evaluation under data parallelism: ComputeProbFrames on this rank's
+    shard of `frames` (global corpus rows) and of `labels` ((rows, cols,
+    weights) arrays, rows into `frames`, sorted by row); dp_prob_total sums
+    the ranks' totals.  The components run as they are, so a DropoutComponent
+    draws its mask, for the global rows as in training (evaluate the test
+    model to have none).  An empty shard runs nothing."""
+    import numpy as np
+    rows, cols, weights = (np.asarray(a) for a in labels)
+    frames = np.asarray(frames)
+    lo, hi = shard(len(frames), dist.get_world_size(), dist.get_rank())
+    if hi == lo:
+        getattr(net, "SkipDropoutCall", lambda: None)()
+        return
+    net.SetRowOffset(lo)
+    keep = (rows >= lo) & (rows < hi)
+    net.ComputeProbFrames(corpus, frames[lo:hi], (rows[keep] - lo, cols[keep], weights[keep]))
+
+
+def dp_train_epoch(net, corpus, pdfs, minibatch_size, srand, dist, grads):
+    """kcnn.train_epoch under data parallelism: every rank draws the same
+    numpy permutation of all corpus rows seeded by `srand`, takes its shard()
+    of every global minibatch (row_offset = the shard's start) and runs
+    dp_xent_step_frames with the minibatch's row count.  Returns the
+    all-reduced (objf, frames) of dp_objf_total(reset=True)."""
+    import numpy as np
+    pdfs = np.ascontiguousarray(pdfs, np.int32).ravel()
+    rows = corpus.NumRows()
+    if len(pdfs) != rows:
+        raise ValueError(f"dp_train_epoch: {len(pdfs)} pdfs for a corpus of {rows} rows")
+    if minibatch_size < 1:
+        raise ValueError(f"dp_train_epoch: minibatch_size {minibatch_size}")
+    world, rank = dist.get_world_size(), dist.get_rank()
+    order = np.random.default_rng(srand).permutation(rows).astype(np.int32)
+    for at in range(0, rows, minibatch_size):
+        batch = order[at:at + minibatch_size]
+        lo, hi = shard(len(batch), world, rank)
+        frames = batch[lo:hi]
+        labels = (np.arange(hi - lo, dtype=np.int32), pdfs[frames], np.ones(hi - lo, np.float32))
+        dp_xent_step_frames(net, corpus, frames, labels, grads, dist, len(batch), lo)
+    return dp_objf_total(net, dist, reset=True)

@@ -622,6 +622,9 @@ int kcnn_component_dropout_seed(const kcnn_component *c, uint64_t *seed) {
 int kcnn_component_set_dropout_seed(kcnn_component *c, uint64_t seed) {
   return guard([&] { dropout(c)->SetSeed(seed); });
 }
+int kcnn_component_set_dropout_row_offset(kcnn_component *c, uint64_t offset) {
+  return guard([&] { dropout(c)->SetRowOffset(offset); });
+}
 
 int kcnn_comp_objf_and_deriv(const int32_t *rows, const int32_t *cols, const float *weights,
                              int num, const float *probs, MatrixDim p_dim, float *deriv,
@@ -762,6 +765,21 @@ int kcnn_nnet_backprop(kcnn_nnet *n, const float *out_deriv, MatrixDim od_dim) {
 int kcnn_nnet_backprop_xent(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
                             const float *weights, int num, int skip_first_dx) {
   return guard([&] { n->stack.BackpropXent(rows, cols, weights, num, skip_first_dx != 0); });
+}
+int kcnn_nnet_xent_deriv(kcnn_nnet *n, const int32_t *rows, const int32_t *cols,
+                         const float *weights, int num, int *first, const float **out_deriv,
+                         MatrixDim *od_dim) {
+  return guard([&] {
+    if (first == nullptr || out_deriv == nullptr || od_dim == nullptr)
+      KALDI_ERR << "kcnn_nnet_xent_deriv: no result pointers";
+    *first = n->stack.XentDeriv(rows, cols, weights, num, out_deriv, od_dim);
+  });
+}
+int kcnn_nnet_set_row_offset(kcnn_nnet *n, uint64_t offset) {
+  return guard([&] { n->stack.SetRowOffset(offset); });
+}
+int kcnn_nnet_skip_dropout_call(kcnn_nnet *n) {
+  return guard([&] { n->stack.SkipDropoutCall(); });
 }
 int kcnn_nnet_objf_total(kcnn_nnet *n, double *out, int reset) {
   return guard([&] { n->stack.ObjfTotal(out, reset != 0); });

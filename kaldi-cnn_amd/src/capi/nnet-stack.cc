@@ -174,6 +174,7 @@ ChunkInfo NnetStack::out_info(int i) {
 // Everything that held for the last minibatch only.
 void NnetStack::ForgetMinibatch() {
   for (Comp &c : comps_) c.mask_valid = c.deriv_deferred = false;
+  xent_fused_ = false;
   for (Activation &a : acts_) {
     a.stale = kStored;
     a.stats_valid = false;
@@ -423,6 +424,7 @@ void NnetStack::BackpropComponent(int i, const float *out_deriv, MatrixDim od_di
   const int nc = NumComponents();
   KALDI_ASSERT(i >= 0 && i < nc);
   RequireTrainingForward("kcnn_nnet_backprop_component");
+  RequireLastNotFused(i, "kcnn_nnet_backprop_component");
   // a first Splice that gathered from the corpus: nothing to update, and its
   // input derivative would be a window matrix of rows that examples share
   if (i == 0 && frames_fused_) return;
@@ -474,6 +476,7 @@ void NnetStack::BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, f
   const int nc = NumComponents();
   KALDI_ASSERT(i >= 0 && i < nc && grad != NULL);
   RequireTrainingForward("kcnn_nnet_backprop_split");
+  RequireLastNotFused(i, "kcnn_nnet_backprop_split");
   Comp &c = comps_[i];
   if (c.affine == NULL) KALDI_ERR << "kcnn_nnet_backprop_split: component " << i << " is not affine";
   KALDI_ASSERT(!(i + 1 < nc && comps_[i + 1].deriv_deferred) && !c.mask_valid);
@@ -532,38 +535,64 @@ const char *NnetStack::LabelStaging::Commit(size_t bytes, hipStream_t st) {
   return static_cast<const char *>(dev.p);
 }
 
-void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights,
-                             int num, bool skip_first_dx) {
+int NnetStack::XentDeriv(const int32_t *rows, const int32_t *cols, const float *weights,
+                         int num, const float **out_deriv, MatrixDim *od_dim,
+                         const char *who) {
   const int nc = NumComponents();
-  RequireTrainingForward("kcnn_nnet_backprop_xent");
+  RequireTrainingForward(who);
   const Comp &last = comps_[nc - 1];
   const CuMatrix<BaseFloat> &y = out(nc - 1).value;
   const int N = y.NumRows(), dim = last.c->OutputDim();
-  if (N == 0 || y.NumCols() != dim) KALDI_ERR << "kcnn_nnet_backprop_xent: no Propagate ran";
-  if (num > 0 && weights == nullptr) KALDI_ERR << "kcnn_nnet_backprop_xent: bad label arrays";
+  if (N == 0 || y.NumCols() != dim) KALDI_ERR << who << ": no Propagate ran";
+  if (num > 0 && weights == nullptr) KALDI_ERR << who << ": bad label arrays";
   // every check before any launch
   const std::string bad = check_labels(rows, cols, num, N, dim, true);
-  if (!bad.empty()) KALDI_ERR << "kcnn_nnet_backprop_xent: " << bad;
+  if (!bad.empty()) KALDI_ERR << who << ": " << bad;
   const DeviceLabels lab = StageLabels(rows, cols, weights, num, N);
   const int32_t *d_start = lab.row_start, *d_row = lab.row, *d_col = lab.col;
   const float *d_w = lab.weight;
   double *tot = objf_totals();
-  int first = nc - 1;  // the component the generic backward starts at
   if (last.softmax != nullptr && !cnsl::nnet0::LiteralPath()) {
     // zeroed derivative + CompObjfAndDeriv + the Softmax's Backprop, fused
     last.softmax->BackpropXent(y, d_start, d_col, d_w, tot, last.softmax,
                                &comps_[nc - 1].deriv);
-    first = nc - 2;
-  } else {
-    // NnetUpdater::ComputeObjfAndDeriv: a zeroed [rows x OutputDim] matrix,
-    // CompObjfAndDeriv against the last output; Backprop follows
-    xent_deriv_.Resize(N, dim, kSetZero);
-    if (num > 0)
-      comp_objf_and_deriv(d_row, d_col, d_w, num, y.Data(), y.Dim(), xent_deriv_.Data(),
-                          xent_deriv_.Dim(), tot);
+    xent_fused_ = true;
+    *out_deriv = nullptr;
+    *od_dim = MatrixDim{0, 0, 0};
+    return nc - 2;
   }
+  // NnetUpdater::ComputeObjfAndDeriv: a zeroed [rows x OutputDim] matrix,
+  // CompObjfAndDeriv against the last output; Backprop follows
+  xent_deriv_.Resize(N, dim, kSetZero);
+  if (num > 0)
+    comp_objf_and_deriv(d_row, d_col, d_w, num, y.Data(), y.Dim(), xent_deriv_.Data(),
+                        xent_deriv_.Dim(), tot);
+  *out_deriv = xent_deriv_.Data();
+  *od_dim = xent_deriv_.Dim();
+  return nc - 1;
+}
+
+void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights,
+                             int num, bool skip_first_dx) {
+  const float *od = nullptr;
+  MatrixDim od_dim = {0, 0, 0};
+  const int first =
+      XentDeriv(rows, cols, weights, num, &od, &od_dim, "kcnn_nnet_backprop_xent");
   for (int i = first; i >= 0; i--)
-    BackpropComponent(i, xent_deriv_.Data(), xent_deriv_.Dim(), kUpdate, nullptr, skip_first_dx);
+    BackpropComponent(i, od, od_dim, kUpdate, nullptr, skip_first_dx);
+  // the whole backward has run: the last component is the caller's again
+  xent_fused_ = false;
+}
+
+void NnetStack::SkipDropoutCall() {
+  for (Comp &c : comps_)
+    if (DropoutComponent *d = dynamic_cast<DropoutComponent *>(c.c.get())) d->SkipCall();
+}
+
+void NnetStack::SetRowOffset(uint64_t offset) {
+  for (Comp &c : comps_)
+    if (DropoutComponent *d = dynamic_cast<DropoutComponent *>(c.c.get()))
+      d->SetRowOffset(offset);
 }
 
 // The list -> pinned staging buffer -> device, on the library's stream.
@@ -585,6 +614,13 @@ void NnetStack::RequireTrainingForward(const char *who) const {
     KALDI_ERR << who << ": the last forward pass was kcnn_nnet_compute_prob's or "
               << "kcnn_nnet_compute's, which keep nothing for a backprop; run "
               << "kcnn_nnet_propagate first";
+}
+
+void NnetStack::RequireLastNotFused(int i, const char *who) const {
+  if (xent_fused_ && i == NumComponents() - 1)
+    KALDI_ERR << who << ": kcnn_nnet_xent_deriv has already written the last "
+              << "SoftmaxComponent's input derivative from the labels; start the backward at "
+              << "the component it returned (" << i - 1 << ")";
 }
 
 double *NnetStack::prob_totals() {

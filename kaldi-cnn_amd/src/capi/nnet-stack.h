@@ -104,8 +104,30 @@ class NnetStack {
   // Does not synchronise.
   void BackpropXent(const int32_t *rows, const int32_t *cols, const float *weights, int num,
                     bool skip_first_dx);
+  // The first half of BackpropXent, for a caller that runs the backward
+  // itself (kcnn_dp.py: per component, gradients all-reduced): the labels
+  // checked and staged, the objective and weight added to the totals, and
+  // d(last output) left where the generic backward reads it.  Returns the
+  // component that backward starts at.  With a last SoftmaxComponent (not on
+  // the literal path) the fused kernel has written that Softmax's input
+  // derivative too: nc - 2 is returned, *out_deriv is NULL with a zero dim
+  // (nothing below the last component reads it), and BackpropComponent /
+  // BackpropSplit of the last component throw until the next forward pass,
+  // since its out_deriv was never formed.  Otherwise nc - 1, and *out_deriv /
+  // *od_dim are the stack's own matrix, to be passed to those calls; valid
+  // until the next XentDeriv.  `who` names the C entry point in errors.
+  // Does not synchronise.
+  int XentDeriv(const int32_t *rows, const int32_t *cols, const float *weights, int num,
+                const float **out_deriv, MatrixDim *od_dim,
+                const char *who = "kcnn_nnet_xent_deriv");
   // {objective, weight} summed since the last reset; synchronises.
   void ObjfTotal(double out[2], bool reset);
+  // DropoutComponent::SetRowOffset on every DropoutComponent of the stack
+  // (none: nothing happens); holds until set again.
+  void SetRowOffset(uint64_t offset);
+  // Every DropoutComponent counts one Propagate call without running: a
+  // data-parallel rank with an empty shard stays on the others' call number.
+  void SkipDropoutCall();
   // nnet-compute-prob on one minibatch: the forward pass, then the objective,
   // the weight and the accuracy weight of the labels (as for BackpropXent)
   // added to totals of their own.  No component changes.  A last Softmax is
@@ -269,6 +291,8 @@ class NnetStack {
   void ComputeProbOn(const float *in, MatrixDim in_dim, FrameList *fl, const int32_t *rows,
                      const int32_t *cols, const float *weights, int num, const char *who);
   void RequireTrainingForward(const char *who) const;
+  // throws for the last component after a fused XentDeriv
+  void RequireLastNotFused(int i, const char *who) const;
   // the checked labels staged on the device (xent-labels.h)
   struct DeviceLabels {
     const int32_t *row_start, *row, *col;
@@ -303,6 +327,10 @@ class NnetStack {
   // the last forward was ComputeProb's or Compute's: there is nothing to
   // backpropagate
   bool prob_forward_ = false;
+  // XentDeriv took the fused route: the last Softmax's input derivative is
+  // written and its Backprop must not run; until the next forward pass, or
+  // the end of BackpropXent
+  bool xent_fused_ = false;
   // the last forward was Compute's: an activation is one chunk of utt_rows
   bool whole_utts_ = false;
   LabelStaging utts_;                   // Compute's utterance starts and prior offsets

@@ -778,11 +778,16 @@ void DropoutComponent::Propagate(const ChunkInfo &in_info, const ChunkInfo &out_
             high_scale = (1.0 - (dp * low_scale)) / (1.0 - dp),
             average = (low_scale * dp) + (high_scale * (1.0 - dp));
   KALDI_ASSERT(fabs(average - 1.0) < 0.01);
+  // before the call is counted: the generator's row word is 32 bits
+  if (row_offset_ > ((uint64_t)1 << 32) - (uint64_t)in.NumRows())
+    KALDI_ERR << "DropoutComponent: row offset " << row_offset_ << " + " << in.NumRows()
+              << " rows exceeds 2^32";
   // RandUniform; Add(-dp); ApplyHeaviside; Scale(high - low) unless 1;
   // Add(low) unless 0; MulElements(in) -- one pass, the draw generated in it
   CuProfileScope prof("kn_dropout_prop");
   CNSL_SAFE_CALL(kn_dropout_prop(in.Data(), in.Dim(), out->Data(), out->Dim(), dp,
-                                 high_scale - low_scale, low_scale, seed_, NextCall(), NS()));
+                                 high_scale - low_scale, low_scale, seed_, NextCall(),
+                                 (int64_t)row_offset_, NS()));
 }
 
 void DropoutComponent::Backprop(const ChunkInfo &, const ChunkInfo &,

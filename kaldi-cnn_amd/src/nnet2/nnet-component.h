@@ -428,6 +428,9 @@ class RandomComponent : public Component {
   uint64_t Seed() const { return seed_; }
   // Also restarts the call count.
   void SetSeed(uint64_t seed) { seed_ = seed; calls_.store(0); }
+  // Counts a Propagate call that did not happen here (a data-parallel rank
+  // whose shard of the minibatch is empty keeps step with the others).
+  void SkipCall() { (void)NextCall(); }
 
  protected:
   void DrawSeed();
@@ -455,6 +458,13 @@ class DropoutComponent : public RandomComponent {
   void SetDropoutScale(BaseFloat scale) { dropout_scale_ = scale; }
   BaseFloat DropoutScale() const { return dropout_scale_; }
   BaseFloat DropoutProportion() const { return dropout_proportion_; }
+  // The row of the minibatch that row 0 of Propagate's input is: the mask of
+  // row r is drawn for row offset + r, so data-parallel ranks that share a seed
+  // draw the masks of their own shards of one minibatch.  Propagate throws,
+  // launching nothing, when offset + rows > 2^32.  Not in the file, and Copy()
+  // starts at 0, as neither carries the seed.
+  void SetRowOffset(uint64_t offset) { row_offset_ = offset; }
+  uint64_t RowOffset() const { return row_offset_; }
   virtual bool BackpropNeedsInput() const { return true; }
   virtual bool BackpropNeedsOutput() const { return true; }
   virtual Component *Copy() const;
@@ -472,6 +482,7 @@ class DropoutComponent : public RandomComponent {
  private:
   BaseFloat dropout_proportion_;
   BaseFloat dropout_scale_;
+  uint64_t row_offset_ = 0;
 };
 
 /// Shared by the components' Read functions (nnet-component-nnet0.cc:24-39).

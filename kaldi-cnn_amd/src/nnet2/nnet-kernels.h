@@ -188,12 +188,15 @@ int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, Matrix
 
 /* DropoutComponent::Propagate (:3592-3625).  The uniform draw of element
  * (row, col) is output col % 4 of Philox4x32-10 with key = seed and counter =
- * (col / 4, row, call low, call high), u = (x >> 8) * 2^-24; then in fp32
- * mask = Heaviside(u - dropout_proportion), scaled by high_minus_low unless
- * that is 1, plus low unless that is 0; out = mask * in. */
+ * (col / 4, row_offset + row, call low, call high), u = (x >> 8) * 2^-24;
+ * then in fp32 mask = Heaviside(u - dropout_proportion), scaled by
+ * high_minus_low unless that is 1, plus low unless that is 0; out = mask * in.
+ * row_offset is the matrix's first row in the minibatch the mask belongs to (a
+ * data-parallel rank's shard start; 0 for a whole minibatch).  row_offset < 0
+ * or row_offset + rows > 2^32 is hipErrorInvalidValue and launches nothing. */
 int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                     float dropout_proportion, float high_minus_low, float low, uint64_t seed,
-                    uint64_t call, kcnn_stream_t st);
+                    uint64_t call, int64_t row_offset, kcnn_stream_t st);
 
 /* DropoutComponent::Backprop (:3627-3637), upstream AddMatMatDivMat:
  * in_deriv = in_value == 0 ? out_deriv : out_deriv * out_value / in_value. */

@@ -11,7 +11,9 @@
 //     are reduced in a fixed order (per-part partials, then one ordered final
 //     pass), never with float atomics, so results repeat bit for bit;
 //   * the dropout mask is Philox4x32-10 of (seed, call, row, column / 4): a
-//     pure function of the element's position, not of the launch geometry.
+//     pure function of the element's position, not of the launch geometry;
+//     the row is the minibatch's (the matrix's row plus the caller's offset),
+//     so a data-parallel shard draws its rows of the whole minibatch's mask.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -525,6 +527,7 @@ struct DropoutArgs {
   float dp, hl, low;   // proportion, high - low, low
   int scale_hl, add_low;
   uint32_t k0, k1, call_lo, call_hi;
+  uint32_t row0;  // the matrix's first row in the minibatch the mask is drawn for
 };
 
 // The reference's sequence on one uniform draw (nnet-component.cc:3613-3622):
@@ -556,7 +559,7 @@ __global__ __launch_bounds__(256) void dropout_prop_kernel(const float *__restri
       if (a.add_low) h += a.low;
       m[0] = m[1] = m[2] = m[3] = h;
     } else {
-      const Philox4 x = philox4x32_10(cb, row, a.call_lo, a.call_hi, a.k0, a.k1);
+      const Philox4 x = philox4x32_10(cb, a.row0 + row, a.call_lo, a.call_hi, a.k0, a.k1);
       m[0] = dropout_mask(x.x, a);
       m[1] = dropout_mask(x.y, a);
       m[2] = dropout_mask(x.z, a);
@@ -864,11 +867,14 @@ int kn_softmax_loglikes(const float *logits, MatrixDim l_dim, float *out, Matrix
 
 int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out_dim,
                     float dropout_proportion, float high_minus_low, float low, uint64_t seed,
-                    uint64_t call, kcnn_stream_t st) {
+                    uint64_t call, int64_t row_offset, kcnn_stream_t st) {
   if (!same_shape(in_dim, out_dim) || !contiguous_enough(in_dim) ||
       !contiguous_enough(out_dim))
     return (int)hipErrorInvalidValue;
   const int rows = in_dim.rows, cols = in_dim.cols;
+  // the counter word row_offset + row must not wrap: two rows would share a mask
+  if (rows < 0 || row_offset < 0 || row_offset > ((int64_t)1 << 32) - rows)
+    return (int)hipErrorInvalidValue;
   if (rows == 0 || cols == 0) return 0;
   const int ncb = (cols + 3) / 4;
   const int64_t total = (int64_t)rows * ncb;
@@ -883,6 +889,7 @@ int kn_dropout_prop(const float *in, MatrixDim in_dim, float *out, MatrixDim out
   a.k1 = (uint32_t)(seed >> 32);
   a.call_lo = (uint32_t)call;
   a.call_hi = (uint32_t)(call >> 32);
+  a.row0 = (uint32_t)row_offset;
   const bool vec4 = in_dim.stride % 4 == 0 && out_dim.stride % 4 == 0 &&
                     (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
   hipStream_t s = kcnn::as_stream(st);
