@@ -543,6 +543,63 @@ int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
                                   const int32_t *frames, int num_frames, const int32_t *rows,
                                   const int32_t *cols, const float *weights, int num);
 
+/* ---- streaming forward pass over concurrent utterances -------------------- */
+/* Upstream NnetOnlineComputer(nnet, pad_input = true), the decodable of
+ * online2-wav-nnet2-latgen-faster --online=true, for num_streams >= 1
+ * concurrent utterances ("slots") batched into one pass per step; each step
+ * gives a slot at most max_chunk >= 1 new frames.  priors / num_priors /
+ * prior_scale / apply_log are kcnn_nnet_compute's, fixed for the computer's
+ * life and checked as there (priors finite and > 0, OutputDim of them, only
+ * with apply_log).  The handle BORROWS n, which must outlive it.  With L and R
+ * the contexts of kcnn_nnet_left_context / _right_context, each slot owns two
+ * device buffers of L + R + max_chunk rows of InputDim floats, allocated once,
+ * by the first accepted step: creating the handle touches no device.  NULL on
+ * error (no net, num_streams < 1, max_chunk < 1, bad priors, an arena of 2^31
+ * rows or elements), the message in kcnn_last_error(). */
+typedef struct kcnn_online kcnn_online;
+kcnn_online *kcnn_online_new(kcnn_nnet *n, int num_streams, int max_chunk, const float *priors,
+                             int num_priors, float prior_scale, int apply_log);
+void kcnn_online_free(kcnn_online *o);
+/* One step.  For i < num (HOST arrays), slot streams[i] -- each slot named at
+ * most once -- gets num_new[i] frames, 0 <= num_new[i] <= max_chunk: the next
+ * rows of `chunk`, the DEVICE matrix [sum of num_new x InputDim] (any row
+ * stride; NULL allowed for no rows).  final[i] != 0 ends the slot's utterance
+ * with these frames; num_new[i] == 0 is allowed only then (a pure flush).  A
+ * slot that has seen `seen` frames and emitted `emitted` rows has, after the
+ * step, ready = seen if final, else max(0, seen - R), and contributes the rows
+ * of frames [emitted, ready): frame t is what the network gives for the input
+ * frames clamp(t + o, 0, T - 1), o = -L .. R, of the eventual utterance of T
+ * frames, as kcnn_nnet_compute(pad_input) gives it.  final then frees the
+ * slot for a new utterance (a final step on a slot that saw nothing emits
+ * nothing).  Slots not named keep their state.  num_out[i] (HOST, written) is
+ * the number of rows slot streams[i] contributes; *data / *out_dim is the
+ * borrowed device view [sum of num_out x OutputDim] of those rows, slots in the
+ * step's order, frames ascending, valid until the next forward call of the net
+ * (this one included): P, or with apply_log log(max(P, 1e-20)) - prior_scale *
+ * log(priors[col]) as kcnn_nnet_compute forms it.  A step that emits nothing
+ * gives [0 x OutputDim], *data NULL, and runs no network kernel.
+ * One kernel moves each named slot's history and new frames into the slot's
+ * other buffer (nothing is copied through the host or in place); the forward
+ * pass is kcnn_nnet_propagate_frames' with that arena as its corpus and, for
+ * each emitted frame, a host-made triple as its example, then kcnn_nnet_
+ * compute's epilogue.  The net's activations hold nothing of a stream: its
+ * other forward calls between steps disturb none.  A DropoutComponent draws
+ * its mask: use the test model.  Leaves the net in the state kcnn_nnet_compute
+ * leaves.  Every check -- a slot out of range or named twice, num_new outside
+ * [0, max_chunk], num_new == 0 without final, chunk rows other than the sum of
+ * num_new, chunk columns other than InputDim, a stride below the columns, any
+ * activation reaching 2^31 rows or elements -- is made before anything is
+ * launched and before any slot changes; a violation is an error that runs
+ * nothing.  Does not synchronise and reads nothing back. */
+int kcnn_online_accept(kcnn_online *o, const float *chunk, MatrixDim dim, const int32_t *streams,
+                       const int32_t *num_new, const int32_t *final, int num, int32_t *num_out,
+                       const float **data, MatrixDim *out_dim);
+/* Abandons the slot's utterance: the slot is free, nothing is emitted. */
+int kcnn_online_reset(kcnn_online *o, int stream);
+/* out[0] = the frames the slot's utterance has seen, out[1] = the rows it has
+ * emitted (both 0 for a free slot). */
+int kcnn_online_frames(const kcnn_online *o, int stream, int64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ Mirrors the reference's interfaces with the same names and argument meaning:
   * ``Nnet``            = a component stack run NnetUpdater-style.
   * ``Corpus`` / ``train_epoch`` = training minibatches as rows of a corpus
     that stays on the device (nnet-get-egs + nnet-shuffle-egs + nnet-train).
+  * ``OnlineComputer``  = upstream ``NnetOnlineComputer`` (the decodable of
+    online2-wav-nnet2-latgen-faster) over concurrent utterances.
 
 Matrices are 2-D float32 CUDA tensors with unit column stride (any row
 stride); they are handed to the C++ library as raw device pointers + MatrixDim
@@ -89,6 +91,17 @@ def lib():
             L.kcnn_nnet_compute_prob_frames.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(L, "kcnn_online_new"):  # (absent from builds before the streaming pass)
+            L.kcnn_online_new.restype = ctypes.c_void_p
+            L.kcnn_online_new.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
+                                          ctypes.c_int]
+            L.kcnn_online_free.argtypes = [ctypes.c_void_p]
+            L.kcnn_online_accept.argtypes = [
+                ctypes.c_void_p, ctypes.c_void_p, MatrixDim, ctypes.c_void_p, ctypes.c_void_p,
+                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            L.kcnn_online_reset.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.kcnn_online_frames.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         if hasattr(L, "kcnn_nnet_xent_deriv"):  # (absent from builds before the DP xent step)
             L.kcnn_nnet_xent_deriv.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -1004,6 +1017,81 @@ class Corpus:
                 self._h = None
         except Exception:
             pass
+
+
+class OnlineComputer:
+    """The streaming forward pass over `num_streams` concurrent utterances
+    (kcnn_online_*; upstream NnetOnlineComputer with pad_input): each Accept
+    gives some slots their next frames, at most `max_chunk` each, and returns
+    the rows that became computable.  `priors`, `prior_scale` and `apply_log`
+    are Compute's.  `net` (the test model) is borrowed and kept alive here; the
+    streams' history lives in device buffers of the computer's own, allocated
+    by the first accepted step, so other forward calls of `net` between steps
+    disturb nothing."""
+
+    def __init__(self, net: Nnet, num_streams: int, max_chunk: int, priors=None,
+                 prior_scale=1.0, apply_log=False):
+        import numpy as np
+        self._h = None
+        self.net = net
+        pp, np_ = None, 0
+        if priors is not None:
+            pr = np.ascontiguousarray(priors, np.float32).ravel()
+            pp, np_ = pr.ctypes.data_as(ctypes.c_void_p), len(pr)
+        h = lib().kcnn_online_new(net._h, int(num_streams), int(max_chunk), pp, np_,
+                                  ctypes.c_float(prior_scale), int(bool(apply_log)))
+        if not h:
+            raise KcnnError(lib().kcnn_last_error().decode(errors="replace"))
+        self._h = ctypes.c_void_p(h)
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().kcnn_online_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def Accept(self, chunk, streams, num_new, final):
+        """One step (kcnn_online_accept).  `chunk`: the [sum(num_new) x
+        InputDim] device matrix of the named slots' new frames, in the order
+        of `streams` (None for a step of pure flushes); `streams`, `num_new`,
+        `final`: host sequences, one entry per named slot, each slot at most
+        once; num_new 0 only with final, which ends the utterance and frees
+        the slot.  Returns (out, counts): `out` the rows that became
+        computable -- a torch view valid until the next forward call of the
+        net -- slots in the step's order, frames ascending, and `counts` the
+        rows of each slot, so torch.split(out, counts) gives them per slot.
+        Does not synchronise."""
+        import numpy as np
+        try:
+            st = np.ascontiguousarray(streams, np.int32).ravel()
+            nn = np.ascontiguousarray(num_new, np.int32).ravel()
+            fi = np.ascontiguousarray([bool(f) for f in final], np.int32).ravel()
+        except (OverflowError, ValueError, TypeError) as e:
+            raise KcnnError(f"Accept: bad stream arrays: {e}") from None
+        if not len(st) == len(nn) == len(fi):
+            raise KcnnError(f"Accept: {len(st)} streams, {len(nn)} num_new, {len(fi)} final")
+        counts = np.zeros(len(st), np.int32)
+        self._chunk = chunk  # read by the step's kernel on the stream
+        d = dim(chunk) if chunk is not None else MatrixDim(0, 0, 0)
+        p = ctypes.c_void_p()
+        od = MatrixDim()
+        check(lib().kcnn_online_accept(
+            self._h, ptr(chunk), d, st.ctypes.data_as(ctypes.c_void_p),
+            nn.ctypes.data_as(ctypes.c_void_p), fi.ctypes.data_as(ctypes.c_void_p), len(st),
+            counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(p), ctypes.byref(od)))
+        return _device_view(p.value, od), [int(c) for c in counts]
+
+    def Reset(self, stream: int):
+        """Abandons the slot's utterance (kcnn_online_reset)."""
+        check(lib().kcnn_online_reset(self._h, int(stream)))
+
+    def Frames(self, stream: int):
+        """(frames seen, rows emitted) of the slot's utterance."""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().kcnn_online_frames(self._h, int(stream), out))
+        return int(out[0]), int(out[1])
 
 
 def train_epoch(net: Nnet, corpus: Corpus, pdfs, minibatch_size: int, srand: int = 0):

@@ -24,6 +24,7 @@
 #include "../nnet2/nnet-component.h"
 #include "../nnet2/nnet-kernels.h"
 #include "nnet-stack.h"
+#include "online-computer.h"
 #include "xent-labels.h"
 
 using namespace kaldi;
@@ -41,6 +42,12 @@ struct kcnn_corpus {
   const float *feats = nullptr;
   MatrixDim dim = {0, 0, 0};
   kcnn::CorpusIndex index;
+};
+
+struct kcnn_online {
+  kcnn::OnlineComputer computer;
+  template <typename... Args>
+  explicit kcnn_online(Args &&...args) : computer(std::forward<Args>(args)...) {}
 };
 
 namespace {
@@ -840,6 +847,42 @@ int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
     if (corpus == nullptr) KALDI_ERR << "kcnn_nnet_compute_prob_frames: no corpus";
     n->stack.ComputeProbFrames(corpus->feats, corpus->dim, corpus->index, frames, num_frames,
                                rows, cols, weights, num);
+  });
+}
+
+// ---- streaming forward pass (kcnn::OnlineComputer) ---------------------------------
+kcnn_online *kcnn_online_new(kcnn_nnet *n, int num_streams, int max_chunk, const float *priors,
+                             int num_priors, float prior_scale, int apply_log) {
+  kcnn_online *o = nullptr;
+  guard([&] {
+    o = new kcnn_online(n ? &n->stack : nullptr, num_streams, max_chunk, priors, num_priors,
+                        prior_scale, apply_log != 0);
+  });
+  return o;
+}
+void kcnn_online_free(kcnn_online *o) { delete o; }
+
+int kcnn_online_accept(kcnn_online *o, const float *chunk, MatrixDim dim, const int32_t *streams,
+                       const int32_t *num_new, const int32_t *final, int num, int32_t *num_out,
+                       const float **data, MatrixDim *out_dim) {
+  return guard([&] {
+    if (o == nullptr) KALDI_ERR << "kcnn_online_accept: no computer";
+    if (data == nullptr || out_dim == nullptr)
+      KALDI_ERR << "kcnn_online_accept: no result pointers";
+    matrix_out(o->computer.Accept(chunk, dim, streams, num_new, final, num, num_out), data,
+               out_dim);
+  });
+}
+int kcnn_online_reset(kcnn_online *o, int stream) {
+  return guard([&] {
+    if (o == nullptr) KALDI_ERR << "kcnn_online_reset: no computer";
+    o->computer.Reset(stream);
+  });
+}
+int kcnn_online_frames(const kcnn_online *o, int stream, int64_t out[2]) {
+  return guard([&] {
+    if (o == nullptr || out == nullptr) KALDI_ERR << "kcnn_online_frames: no computer";
+    o->computer.Frames(stream, out);
   });
 }
 

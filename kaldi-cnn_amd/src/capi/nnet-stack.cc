@@ -340,12 +340,19 @@ int NnetStack::CheckFrames(const FrameList &fl, const char *who) const {
   if (fl.dim.rows != fl.corpus->rows())
     KALDI_ERR << who << ": the corpus index covers " << fl.corpus->rows() << " rows, the matrix "
               << "has " << fl.dim.rows;
-  std::string bad =
+  const std::string bad =
       check_frames(*fl.corpus, fl.frames, fl.num, (int)acts_[0].offsets.size());
+  if (!bad.empty()) KALDI_ERR << who << ": " << bad;
+  CheckExamples(fl.num, who);
+  return fl.num;
+}
+
+void NnetStack::CheckExamples(int num, const char *who) const {
+  std::string bad;
   // every activation of the pass, the window matrix among them
   for (size_t k = 0; bad.empty() && k < acts_.size(); k++)
     bad = check_frames_matrix(k == 0 ? "the input" : "an activation",
-                              (int64_t)fl.num * (int64_t)acts_[k].offsets.size(),
+                              (int64_t)num * (int64_t)acts_[k].offsets.size(),
                               k == 0 ? comps_[0].c->InputDim() : comps_[k - 1].c->OutputDim());
   if (!bad.empty()) KALDI_ERR << who << ": " << bad;
   if (comps_[0].splice != nullptr) {
@@ -356,7 +363,6 @@ int NnetStack::CheckFrames(const FrameList &fl, const char *who) const {
       KALDI_ERR << who << ": " << o.size() << " gapped output rows per example in a context of "
                 << acts_[0].offsets.back() << " frames exceed the first Splice's offset table";
   }
-  return fl.num;
 }
 
 // The examples' triples -> pinned staging buffer -> device, on the library's
@@ -382,6 +388,26 @@ void NnetStack::ComputeProbFrames(const float *feats, MatrixDim dim, const Corpu
   FrameList fl = {feats, dim, &corpus, frames, num, nullptr};
   ComputeProbOn(feats, dim, &fl, rows, cols, weights, num_labels,
                 "kcnn_nnet_compute_prob_frames");
+}
+
+const CuMatrix<BaseFloat> &NnetStack::ComputeExamples(const float *feats, MatrixDim dim,
+                                                      const int32_t *examples, int num,
+                                                      bool apply_log,
+                                                      const double *prior_offsets) {
+  const int nc = NumComponents();
+  const int count = FusedLoglikes(apply_log) ? nc - 1 : nc;
+  // every step emits another row count and every forward kernel writes its
+  // whole output: sized as PropagateUtterances sizes them
+  if (!cnsl::nnet0::LiteralPath())
+    for (int i = 0; i < count; i++) {
+      CuMatrix<BaseFloat> &y = out(i).value;
+      const int rows = num * (int)out(i).offsets.size(), cols = comps_[i].c->OutputDim();
+      if (y.NumRows() != rows || y.NumCols() != cols) y.Resize(rows, cols, kUndefined);
+    }
+  const FrameList fl = {feats, dim, nullptr, nullptr, num, examples};
+  PropagateFirst(feats, dim, count, &fl);
+  prob_forward_ = true;
+  return Loglikes(apply_log, prior_offsets, num);
 }
 
 const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
@@ -784,16 +810,7 @@ const CuMatrix<BaseFloat> &NnetStack::Compute(const float *input, MatrixDim in_d
               << in_dim.rows << " rows";
   if (total + (int64_t)num_utts * context >= ((int64_t)1 << 31))
     KALDI_ERR << "kcnn_nnet_compute: too many rows";
-  if (priors != nullptr) {
-    if (!apply_log)
-      KALDI_ERR << "kcnn_nnet_compute: priors without apply_log are not supported";
-    if (num_priors != dim)
-      KALDI_ERR << "kcnn_nnet_compute: " << num_priors << " priors for " << dim << " outputs";
-    for (int c = 0; c < dim; c++)
-      if (!(priors[c] > 0.0f) || !std::isfinite(priors[c]))
-        KALDI_ERR << "kcnn_nnet_compute: prior " << c << " is " << priors[c]
-                  << "; priors must be finite and > 0";
-  }
+  CheckPriors(priors, num_priors, apply_log, "kcnn_nnet_compute");
   // The starts of the utterances' result rows and the fp64 prior offsets, in
   // one staged image (first, as ComputeProb stages its labels first).
   const size_t off_at = ((size_t)(num_utts + 1) * sizeof(int32_t) + 7) / 8 * 8;
@@ -811,14 +828,35 @@ const CuMatrix<BaseFloat> &NnetStack::Compute(const float *input, MatrixDim in_d
   const int32_t *d_starts = reinterpret_cast<const int32_t *>(base);
   const double *d_off = priors ? reinterpret_cast<const double *>(base + off_at) : nullptr;
 
-  const bool fused = apply_log && last.softmax != nullptr && !cnsl::nnet0::LiteralPath();
   PropagateUtterances(input, in_dim, d_starts, num_utts, (int)total, pad_input,
-                      fused ? nc - 1 : nc);
+                      FusedLoglikes(apply_log) ? nc - 1 : nc);
+  return Loglikes(apply_log, d_off, (int)total);
+}
+
+void NnetStack::CheckPriors(const float *priors, int num_priors, bool apply_log,
+                            const char *who) const {
+  if (priors == nullptr) return;
+  const int dim = OutputDim();
+  if (!apply_log) KALDI_ERR << who << ": priors without apply_log are not supported";
+  if (num_priors != dim)
+    KALDI_ERR << who << ": " << num_priors << " priors for " << dim << " outputs";
+  for (int c = 0; c < dim; c++)
+    if (!(priors[c] > 0.0f) || !std::isfinite(priors[c]))
+      KALDI_ERR << who << ": prior " << c << " is " << priors[c]
+                << "; priors must be finite and > 0";
+}
+
+bool NnetStack::FusedLoglikes(bool apply_log) const {
+  return apply_log && comps_.back().softmax != nullptr && !cnsl::nnet0::LiteralPath();
+}
+
+const CuMatrix<BaseFloat> &NnetStack::Loglikes(bool apply_log, const double *d_off, int total) {
+  const int nc = NumComponents(), dim = OutputDim();
   if (!apply_log) return out(nc - 1).value;
   const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
   if (loglikes_.NumRows() != total || loglikes_.NumCols() != dim)
-    loglikes_.Resize((int)total, dim, kUndefined);  // written whole
-  if (fused) {
+    loglikes_.Resize(total, dim, kUndefined);  // written whole
+  if (FusedLoglikes(apply_log)) {
     out(nc - 1).stale = kRecomputable;  // the Softmax did not run
     const CuMatrix<BaseFloat> &x = in(nc - 1).value;
     KALDI_ASSERT(x.NumRows() == total && x.NumCols() == dim);

@@ -194,6 +194,53 @@ class NnetStack {
                          const int32_t *frames, int num, const int32_t *rows,
                          const int32_t *cols, const float *weights, int num_labels);
 
+  // What kcnn::OnlineComputer (online-computer.h) needs: Compute's checks of
+  // its priors under another caller's name; the checks PropagateFrames makes
+  // of its pass once the frame list itself is checked (`num` examples: the
+  // window matrix and every activation below 2^31 rows and elements, a gapped
+  // first Splice within its offset table); and the pass itself from triples
+  // the caller has made and put on the device, `examples` ({row, lo, hi} per
+  // example, rows of `feats`), instead of a CorpusIndex and a frame list.
+  // ComputeExamples is PropagateFrames' forward (a first Splice gathering
+  // straight from `feats`, any other component 0 getting its window matrix
+  // laid out, the fused pairs, the statistics hand-off) with the outputs sized
+  // as Compute sizes them, without the zero fill, then Compute's result: the
+  // last output, or with apply_log its log less prior_offsets (DEVICE fp64,
+  // OutputDim entries, or NULL), by the fused kernel from a last Softmax's
+  // input unless the literal path is on.  Checks nothing: CheckExamples first.
+  // Leaves the state ComputeProbFrames leaves; does not synchronise.
+  void CheckPriors(const float *priors, int num_priors, bool apply_log, const char *who) const;
+  void CheckExamples(int num, const char *who) const;
+  const CuMatrix<BaseFloat> &ComputeExamples(const float *feats, MatrixDim dim,
+                                             const int32_t *examples, int num, bool apply_log,
+                                             const double *prior_offsets);
+  int InputDim() const { return comps_.front().c->InputDim(); }
+  int OutputDim() const { return comps_.back().c->OutputDim(); }
+
+  // BackpropXent: the label list's pinned staging buffer and its device image
+  // (xent-labels.h), the event after which the staging buffer may be
+  // rewritten, and the fp64 {objective, weight} totals on the device.
+  // Compute stages its utterance starts and prior offsets through another,
+  // PropagateFrames its example triples (frame-index.h) through a third, and
+  // an OnlineComputer its steps through one of its own.
+  struct LabelStaging {
+    void *host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t copied = nullptr;
+    kaldi::CuBuffer totals, dev;
+    LabelStaging() {}
+    ~LabelStaging();  // waits for the last copy to leave `host`
+    LabelStaging(const LabelStaging &) = delete;
+    LabelStaging &operator=(const LabelStaging &) = delete;
+    // the staging buffer, of `bytes` at least and free to be written
+    char *Begin(size_t bytes);
+    // its first `bytes` -> dev on `st`; returns dev
+    const char *Commit(size_t bytes, hipStream_t st);
+    // the checked labels -> host -> dev on `st`; returns dev
+    const char *Stage(const int32_t *rows, const int32_t *cols, const float *weights, int num,
+                      int num_rows, hipStream_t st);
+  };
+
  private:
   struct Comp {
     std::unique_ptr<kaldi::nnet2::Component> c;
@@ -245,33 +292,11 @@ class NnetStack {
     PoolColDeferred col_deferred;
     kaldi::CuBuffer col_partials;
   };
-  // BackpropXent: the label list's pinned staging buffer and its device image
-  // (xent-labels.h), the event after which the staging buffer may be
-  // rewritten, and the fp64 {objective, weight} totals on the device.
-  // Compute stages its utterance starts and prior offsets through another,
-  // PropagateFrames its example triples (frame-index.h) through a third.
-  struct LabelStaging {
-    void *host = nullptr;
-    size_t host_bytes = 0;
-    hipEvent_t copied = nullptr;
-    kaldi::CuBuffer totals, dev;
-    LabelStaging() {}
-    ~LabelStaging();  // waits for the last copy to leave `host`
-    LabelStaging(const LabelStaging &) = delete;
-    LabelStaging &operator=(const LabelStaging &) = delete;
-    // the staging buffer, of `bytes` at least and free to be written
-    char *Begin(size_t bytes);
-    // its first `bytes` -> dev on `st`; returns dev
-    const char *Commit(size_t bytes, hipStream_t st);
-    // the checked labels -> host -> dev on `st`; returns dev
-    const char *Stage(const int32_t *rows, const int32_t *cols, const float *weights, int num,
-                      int num_rows, hipStream_t st);
-  };
-
   // the constructors' shared tail: the checks, the kinds, the chunk offsets
   void Init(std::vector<std::unique_ptr<kaldi::nnet2::Component>> parsed);
   // A minibatch of corpus rows (PropagateFrames): the caller's arguments, and
-  // `examples`, their staged triples on the device once StageFrames has run.
+  // `examples`, their staged triples on the device once StageFrames has run
+  // (ComputeExamples: the caller's own, with no corpus and no frames).
   struct FrameList {
     const float *feats;
     MatrixDim dim;
@@ -301,6 +326,12 @@ class NnetStack {
   DeviceLabels StageLabels(const int32_t *rows, const int32_t *cols, const float *weights,
                            int num, int num_rows);
   double *prob_totals();
+  // whether a result with apply_log is formed from a last Softmax's input
+  bool FusedLoglikes(bool apply_log) const;
+  // Compute's result once the forward has run (all components, or all but
+  // the last with FusedLoglikes): the last output, or its `total` rows of
+  // log-likelihoods less d_off (device, or NULL)
+  const CuMatrix<BaseFloat> &Loglikes(bool apply_log, const double *d_off, int total);
   // Compute's forward pass over the first `count` components
   void PropagateUtterances(const float *in, MatrixDim in_dim, const int32_t *utt_start,
                            int num_utts, int total, bool pad_input, int count);

@@ -103,6 +103,22 @@ typedef struct {
 int kn_splice_frames_prop(const float *feats, MatrixDim dim, float *out, MatrixDim out_dim,
                           const int *examples, kn_frames_splice_geom geom, kcnn_stream_t st);
 
+/* One step of the streaming forward pass's history arena (capi/stream-state.h):
+ * for each of num_slots slots named by the step, desc (DEVICE, 5 ints a slot)
+ * holds {src, tail, dst, chunk_first, num_new}: arena rows [src, src + tail)
+ * -- the frames the slot still needs, in its current buffer -- are copied to
+ * arena rows [dst, dst + tail), its other buffer, and chunk rows [chunk_first,
+ * chunk_first + num_new) behind them.  row_start (DEVICE, num_slots + 1
+ * ascending entries from 0 to total_rows) is the prefix of tail + num_new; a
+ * written row's slot is found by a search over it.  The host keeps a step's
+ * sources and destinations disjoint; nothing is copied in place.  `chunk` is
+ * read with its own stride and may be NULL when no slot has new frames.  A
+ * row outside its matrix is not copied, so descriptors that disagree with the
+ * matrices still stay inside them. */
+int kn_stream_assemble(float *arena, MatrixDim arena_dim, const float *chunk, MatrixDim chunk_dim,
+                       const int *row_start, const int *desc, int num_slots, int total_rows,
+                       kcnn_stream_t st);
+
 /* fp64 stat vectors of NonlinearComponent (Scale/Add/UpdateStats):
  * y = beta * y + alpha * x  (x may be NULL: y = beta * y). */
 int kn_dvec_update(double *y, const double *x, double alpha, double beta, int n,

@@ -294,6 +294,68 @@ __global__ __launch_bounds__(256) void splice_frames_kernel(const float *__restr
   }
 }
 
+// The streaming arena's step (kn_stream_assemble), shaped as the ragged
+// kernel: groups of `rpb` consecutive written rows to a block; one thread per
+// row finds the row's slot (a binary search over the num_slots + 1 staged
+// prefix entries; a slot that writes nothing is never found) and leaves where
+// the row comes from -- an arena row of the slot's current buffer, or a row of
+// the caller's chunk -- and the arena row it goes to in LDS; then all 256
+// threads copy the group's V-float units.  The arena is read and written
+// through one pointer: sources and destinations are different buffers.
+constexpr int kAssembleMaxBlocks = 1024;  // a step writes a few rows a stream
+struct AssembleArgs {
+  int num_slots, total_rows, arena_rows, chunk_rows, rpb;
+  FastDiv div_units;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void stream_assemble_kernel(
+    float *arena, int64_t as, const float *__restrict__ chunk, int64_t cs,
+    const int *__restrict__ row_start, const int *__restrict__ desc, AssembleArgs a, int units) {
+  // s_src: the source row, in the chunk when s_chunk; s_dst < 0: nothing to copy
+  __shared__ int s_src[kRaggedMaxRows], s_dst[kRaggedMaxRows], s_chunk[kRaggedMaxRows];
+  const int ngroups = (a.total_rows + a.rpb - 1) / a.rpb;
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int r0 = grp * a.rpb;
+    const int nr = min(a.rpb, a.total_rows - r0);
+    __syncthreads();  // the last group's readers are done
+    if ((int)threadIdx.x < nr) {
+      const int r = r0 + (int)threadIdx.x;
+      int lo = 0, hi = a.num_slots;  // row_start[lo] <= r < row_start[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (row_start[mid] <= r) lo = mid; else hi = mid;
+      }
+      const int *d = desc + 5 * (int64_t)lo;
+      const int k = r - row_start[lo], tail = d[1];
+      const bool from_chunk = k >= tail;
+      const int src = from_chunk ? d[3] + (k - tail) : d[0] + k;
+      const int dst = d[2] + k;
+      const bool ok = k >= 0 && k < tail + d[4] && src >= 0 &&
+                      src < (from_chunk ? a.chunk_rows : a.arena_rows) && dst >= 0 &&
+                      dst < a.arena_rows;
+      s_src[threadIdx.x] = src;
+      s_chunk[threadIdx.x] = from_chunk;
+      s_dst[threadIdx.x] = ok ? dst : -1;
+    }
+    __syncthreads();
+    const int n = nr * units;
+    for (int e = threadIdx.x; e < n; e += 256) {
+      uint32_t lr, cu;
+      a.div_units.divmod((uint32_t)e, lr, cu);
+      if (s_dst[lr] < 0) continue;
+      const int col = (int)cu * V;
+      const float *src = s_chunk[lr] ? chunk + (int64_t)s_src[lr] * cs + col
+                                     : arena + (int64_t)s_src[lr] * as + col;
+      float *dst = arena + (int64_t)s_dst[lr] * as + col;
+      if constexpr (V == 4)
+        *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
+      else
+        *dst = *src;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void splice_backprop_kernel(
     const float *__restrict__ od, int64_t ods, float *__restrict__ id, int64_t ids,
     SpliceArgs a, int64_t total) {
@@ -528,6 +590,44 @@ int kn_splice_frames_prop(const float *feats, MatrixDim dim, float *out, MatrixD
   else
     hipLaunchKernelGGL(splice_frames_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), feats,
                        (int64_t)dim.stride, out, (int64_t)out_dim.stride, examples, a);
+  return kcnn::launch_status();
+}
+
+int kn_stream_assemble(float *arena, MatrixDim arena_dim, const float *chunk, MatrixDim chunk_dim,
+                       const int *row_start, const int *desc, int num_slots, int total_rows,
+                       kcnn_stream_t st) {
+  const int cols = arena_dim.cols;
+  if (arena == nullptr || row_start == nullptr || desc == nullptr || num_slots <= 0 ||
+      total_rows < 0 || arena_dim.rows <= 0 || cols <= 0 || arena_dim.stride < cols ||
+      chunk_dim.rows < 0 || (chunk_dim.rows > 0 && (chunk == nullptr || chunk_dim.cols != cols ||
+                                                    chunk_dim.stride < cols)))
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)arena_dim.rows * cols >= ((int64_t)1 << 31) ||
+      (int64_t)chunk_dim.rows * cols >= ((int64_t)1 << 31))
+    return (int)hipErrorInvalidValue;
+  if (total_rows == 0) return 0;
+  const bool with_chunk = chunk_dim.rows > 0;
+  const bool vec4 = cols % 4 == 0 && arena_dim.stride % 4 == 0 && (uintptr_t)arena % 16 == 0 &&
+                    (!with_chunk || (chunk_dim.stride % 4 == 0 && (uintptr_t)chunk % 16 == 0));
+  const int units = cols / (vec4 ? 4 : 1);
+  AssembleArgs a;
+  a.num_slots = num_slots;
+  a.total_rows = total_rows;
+  a.arena_rows = arena_dim.rows;
+  a.chunk_rows = chunk_dim.rows;
+  // about four units a thread and group, as the ragged form
+  a.rpb = std::max(1, std::min(kRaggedMaxRows, 1024 / units));
+  a.div_units = FastDiv((uint32_t)units);
+  const int ngroups = (total_rows + a.rpb - 1) / a.rpb;
+  const dim3 grid((unsigned)std::min(ngroups, kAssembleMaxBlocks));
+  if (vec4)
+    hipLaunchKernelGGL(stream_assemble_kernel<4>, grid, dim3(256), 0, kcnn::as_stream(st), arena,
+                       (int64_t)arena_dim.stride, chunk, (int64_t)chunk_dim.stride, row_start,
+                       desc, a, units);
+  else
+    hipLaunchKernelGGL(stream_assemble_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), arena,
+                       (int64_t)arena_dim.stride, chunk, (int64_t)chunk_dim.stride, row_start,
+                       desc, a, units);
   return kcnn::launch_status();
 }
 
