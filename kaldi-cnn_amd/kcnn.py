@@ -919,8 +919,26 @@ class Nnet:
         """The frames it reads after that frame (Nnet::RightContext)."""
         return lib().kcnn_nnet_right_context(self._h)
 
+    def TimeSharedPrefix(self):
+        """The number of leading components Compute(share_time=True) runs once
+        per time step (kcnn_nnet_time_shared_prefix); 0: it runs Compute's own
+        pass."""
+        return lib().kcnn_nnet_time_shared_prefix(self._h)
+
+    def TimeMap(self, level):
+        """Level `level` of the last Compute(share_time=True)
+        (kcnn_nnet_time_map): (torch view of its computed rows, one per input
+        row, by channels; channels; positions; dilation).  Valid until the
+        next forward call; for tests and debugging."""
+        p = ctypes.c_void_p()
+        d = MatrixDim()
+        c, n, dil = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib().kcnn_nnet_time_map(self._h, int(level), ctypes.byref(p), ctypes.byref(d),
+                                       ctypes.byref(c), ctypes.byref(n), ctypes.byref(dil)))
+        return _device_view(p.value, d), c.value, n.value, dil.value
+
     def Compute(self, feats, lengths=None, pad_input=True, priors=None, prior_scale=1.0,
-                apply_log=False):
+                apply_log=False, share_time=False):
         """The forward pass of upstream NnetComputer (nnet-am-compute, the
         decodable) on whole utterances (kcnn_nnet_compute).  `feats`: the
         utterances' frames stacked row-wise in one device matrix; `lengths`:
@@ -931,7 +949,13 @@ class Nnet:
         log of the output, minus prior_scale * log(priors) when `priors` (one
         per output, host) are given.  Returns a torch view of the result,
         valid until the next forward call; changes nothing in the network and
-        does not synchronise; Backprop* raise until the next Propagate."""
+        does not synchronise; Backprop* raise until the next Propagate.
+        share_time (kcnn_nnet_compute_shared): the leading Splice ->
+        {Convolution | Maxpool | ReLU}... components run once per time step
+        instead of once per window -- the same values to the error bar of the
+        GEMMs, not the same bits; Output(i) of those components but the last
+        then raises, TimeMap gives their maps.  A network this does not cover
+        (TimeSharedPrefix() == 0) runs as without it."""
         import numpy as np
         if lengths is None:
             lengths = [feats.shape[0]]
@@ -946,7 +970,8 @@ class Nnet:
         self._input = feats  # the library borrows it as Propagate does
         p = ctypes.c_void_p()
         d = MatrixDim()
-        check(lib().kcnn_nnet_compute(
+        fn = lib().kcnn_nnet_compute_shared if share_time else lib().kcnn_nnet_compute
+        check(fn(
             self._h, ptr(feats), dim(feats), lens.ctypes.data_as(ctypes.c_void_p), len(lens),
             int(bool(pad_input)), pp, np_, ctypes.c_float(prior_scale), int(bool(apply_log)),
             ctypes.byref(p), ctypes.byref(d)))

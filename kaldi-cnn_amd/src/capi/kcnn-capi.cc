@@ -811,6 +811,37 @@ int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int
                data, dim);
   });
 }
+int kcnn_nnet_compute_shared(kcnn_nnet *n, const float *in, MatrixDim in_dim,
+                             const int32_t *lengths, int num_utts, int pad_input,
+                             const float *priors, int num_priors, float prior_scale,
+                             int apply_log, const float **data, MatrixDim *dim) {
+  return guard([&] {
+    if (data == nullptr || dim == nullptr)
+      KALDI_ERR << "kcnn_nnet_compute_shared: no result pointers";
+    matrix_out(n->stack.ComputeShared(in, in_dim, lengths, num_utts, pad_input != 0, priors,
+                                      num_priors, prior_scale, apply_log != 0),
+               data, dim);
+  });
+}
+int kcnn_nnet_time_shared_prefix(const kcnn_nnet *n) {
+  int prefix = 0;
+  guard([&] { prefix = n->stack.TimeSharedPlan().prefix(); });
+  return prefix;
+}
+int kcnn_nnet_time_map(const kcnn_nnet *n, int level, const float **data, MatrixDim *dim,
+                       int *channels, int *positions, int *dilation) {
+  return guard([&] {
+    if (data == nullptr || dim == nullptr || channels == nullptr || positions == nullptr ||
+        dilation == nullptr)
+      KALDI_ERR << "kcnn_nnet_time_map: no result pointers";
+    const kcnn::NnetStack::TimeMapInfo m = n->stack.TimeMap(level);
+    *data = m.data;
+    *dim = m.dim;
+    *channels = m.channels;
+    *positions = m.positions;
+    *dilation = m.dilation;
+  });
+}
 
 // ---- training from a device-resident corpus ----------------------------------------
 kcnn_corpus *kcnn_corpus_new(const float *feats, MatrixDim dim, const int32_t *lengths,

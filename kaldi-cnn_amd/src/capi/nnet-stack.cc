@@ -114,6 +114,7 @@ void NnetStack::Init(std::vector<std::unique_ptr<Component>> parsed) {
   // sized once: handles, PoolColDeferreds and matrices are pointed at
   comps_.resize(nc);
   acts_.resize(nc + 1);
+  time_maps_.resize(nc);
   for (size_t i = 0; i < nc; i++) {
     Comp &c = comps_[i];
     c.c = std::move(parsed[i]);
@@ -290,7 +291,7 @@ void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count,
   num_chunks_ = fl ? fl->num : checked_num_chunks(in_dim, comps_[0].c->InputDim(), in_cs);
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   ForgetMinibatch();
-  prob_forward_ = whole_utts_ = frames_fused_ = false;
+  prob_forward_ = whole_utts_ = frames_fused_ = time_shared_ = false;
   int first = 0;  // the component the loop starts at
   if (fl != nullptr) {
     // the offset of the input chunk's first frame from an example's own
@@ -413,6 +414,10 @@ const CuMatrix<BaseFloat> &NnetStack::ComputeExamples(const float *feats, Matrix
 const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
   KALDI_ASSERT(i >= -1 && i < NumComponents());
   Activation &a = out(i);
+  if (time_shared_ && i >= 0 && i + 1 < (int)time_views_.size())
+    KALDI_ERR << "output of component " << i << " was not formed: kcnn_nnet_compute_shared ran "
+              << "components 0 to " << time_views_.size() - 1 << " as time maps; see "
+              << "kcnn_nnet_time_map";
   if (a.stale == kGone)
     KALDI_ERR << "output of component " << i << " was not stored (fused with the "
               << "next Maxpool, kcnn_set_fusion(1)) and its backprop has run; "
@@ -712,9 +717,31 @@ int NnetStack::RightContext() const {
   return right;
 }
 
+// The clamped frames of a padded pass laid out by a one-slot Splice: an
+// utterance of T frames gets T + ext rows of padded_input_, `left` copies of
+// its first frame in front.
+void NnetStack::LayOutClamped(const float *input, MatrixDim in_dim, const int32_t *utt_start,
+                              int num_utts, int total, int ext, int left) {
+  size_output(&padded_input_, total + num_utts * ext, in_dim.cols);
+  kn_ragged_splice_geom g;
+  g.num_utts = num_utts;
+  g.total = total;
+  g.in_ext = 0;
+  g.out_ext = ext;
+  g.shift = g.const_shift = -left;
+  g.dim = in_dim.cols;
+  g.const_dim = 0;
+  g.num_splice = 1;
+  g.context[0] = 0;
+  CuProfileScope prof("kn_splice_ragged_prop");
+  CNSL_SAFE_CALL(kn_splice_ragged_prop(
+      input, in_dim, padded_input_.Data(), padded_input_.Dim(), utt_start, g,
+      reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream())));
+}
+
 void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
                                     const int32_t *utt_start, int num_utts, int total,
-                                    bool pad_input, int count) {
+                                    bool pad_input, int count, int first) {
   const int nc = NumComponents();
   // an activation's extra rows per utterance: the contexts still to come
   int ext = 0;
@@ -732,41 +759,31 @@ void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
   ForgetMinibatch();
   prob_forward_ = whole_utts_ = true;
   frames_fused_ = false;
-  if (pad_input && ext > 0 && !clamp_in_splice) {
+  time_shared_ = first > 0;
+  if (first > 0) {
+    // the time maps have run and the gather has written component first's input
+    acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
+  } else if (pad_input && ext > 0 && !clamp_in_splice) {
     // component 0 is row-wise: the clamped frames laid out by a one-slot Splice
-    size_output(&padded_input_, acts_[0].utt_rows, in_dim.cols);
-    kn_ragged_splice_geom g;
-    g.num_utts = num_utts;
-    g.total = total;
-    g.in_ext = 0;
-    g.out_ext = ext;
-    g.shift = g.const_shift = -left;
-    g.dim = in_dim.cols;
-    g.const_dim = 0;
-    g.num_splice = 1;
-    g.context[0] = 0;
-    CuProfileScope prof("kn_splice_ragged_prop");
-    CNSL_SAFE_CALL(kn_splice_ragged_prop(
-        input, in_dim, padded_input_.Data(), padded_input_.Dim(), utt_start, g,
-        reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream())));
+    LayOutClamped(input, in_dim, utt_start, num_utts, total, ext, left);
     acts_[0].value.Borrow(padded_input_.Data(), padded_input_.NumRows(),
                           padded_input_.NumCols(), padded_input_.Stride());
   } else {
     acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   }
-  KALDI_ASSERT(acts_[0].value.NumRows() == acts_[0].utt_rows);
+  KALDI_ASSERT(first > 0 || acts_[0].value.NumRows() == acts_[0].utt_rows);
   // Every batch of utterances has another row count, and every forward kernel
   // writes its whole output: the outputs are sized here without the zero fill
   // of Component::Propagate's Resize (at 26438 rows of nnet.config that fill
   // is 1.7 ms of an 11.2 ms call, profiles/compute.md).  The literal path
   // keeps the reference's zeroing Resize.
   if (!cnsl::nnet0::LiteralPath())
-    for (int i = 0; i < count; i++) {
+    for (int i = first; i < count; i++) {
       CuMatrix<BaseFloat> &y = out(i).value;
       if (y.NumRows() != out(i).utt_rows || y.NumCols() != comps_[i].c->OutputDim())
         y.Resize(out(i).utt_rows, comps_[i].c->OutputDim(), kUndefined);
     }
-  for (int i = 0; i < count; i++) {
+  for (int i = first; i < count; i++) {
     if (const SpliceComponent *splice = comps_[i].splice) {
       const bool clamp = i == 0 && clamp_in_splice;
       size_output(&out(i).value, out(i).utt_rows, splice->OutputDim());
@@ -786,31 +803,60 @@ const CuMatrix<BaseFloat> &NnetStack::Compute(const float *input, MatrixDim in_d
                                               bool pad_input, const float *priors,
                                               int num_priors, float prior_scale,
                                               bool apply_log) {
+  return ComputeOn(input, in_dim, lengths, num_utts, pad_input, priors, num_priors, prior_scale,
+                   apply_log, false, "kcnn_nnet_compute");
+}
+
+const CuMatrix<BaseFloat> &NnetStack::ComputeShared(const float *input, MatrixDim in_dim,
+                                                    const int32_t *lengths, int num_utts,
+                                                    bool pad_input, const float *priors,
+                                                    int num_priors, float prior_scale,
+                                                    bool apply_log) {
+  return ComputeOn(input, in_dim, lengths, num_utts, pad_input, priors, num_priors, prior_scale,
+                   apply_log, true, "kcnn_nnet_compute_shared");
+}
+
+const CuMatrix<BaseFloat> &NnetStack::ComputeOn(const float *input, MatrixDim in_dim,
+                                                const int32_t *lengths, int num_utts,
+                                                bool pad_input, const float *priors,
+                                                int num_priors, float prior_scale,
+                                                bool apply_log, bool share_time,
+                                                const char *who) {
   const int nc = NumComponents();
   const Comp &last = comps_[nc - 1];
   const int dim = last.c->OutputDim();
   const int context = LeftContext() + RightContext();
   // every check before any launch
-  if (lengths == nullptr || num_utts < 1) KALDI_ERR << "kcnn_nnet_compute: no utterances";
+  if (lengths == nullptr || num_utts < 1) KALDI_ERR << who << ": no utterances";
   if (in_dim.cols != comps_[0].c->InputDim())
-    KALDI_ERR << "kcnn_nnet_compute: input of " << in_dim.cols << " columns for a network of "
+    KALDI_ERR << who << ": input of " << in_dim.cols << " columns for a network of "
               << comps_[0].c->InputDim();
   const int min_len = pad_input ? 1 : context + 1;
   int64_t sum = 0, total = 0;  // input rows, result rows
   for (int u = 0; u < num_utts; u++) {
     if (lengths[u] < min_len)
-      KALDI_ERR << "kcnn_nnet_compute: utterance " << u << " has " << lengths[u]
+      KALDI_ERR << who << ": utterance " << u << " has " << lengths[u]
                 << " frames; at least " << min_len << " are needed"
                 << (pad_input ? "" : " without pad_input");
     sum += lengths[u];
     total += pad_input ? lengths[u] : lengths[u] - context;
   }
   if (sum != in_dim.rows)
-    KALDI_ERR << "kcnn_nnet_compute: the lengths sum to " << sum << ", the input has "
+    KALDI_ERR << who << ": the lengths sum to " << sum << ", the input has "
               << in_dim.rows << " rows";
   if (total + (int64_t)num_utts * context >= ((int64_t)1 << 31))
-    KALDI_ERR << "kcnn_nnet_compute: too many rows";
-  CheckPriors(priors, num_priors, apply_log, "kcnn_nnet_compute");
+    KALDI_ERR << who << ": too many rows";
+  CheckPriors(priors, num_priors, apply_log, who);
+  // the time maps' rows, when the leading components run as time maps (a
+  // stack the plan declines takes Compute's own pass)
+  TimePlan plan;
+  TimeRows rows;
+  if (share_time) plan = TimeSharedPlan();
+  if (plan.prefix() > 0) {
+    const std::string bad = plan_time_rows(plan, lengths, num_utts, pad_input, &rows);
+    if (!bad.empty()) KALDI_ERR << who << ": " << bad;
+    KALDI_ASSERT(rows.result_rows == total && rows.input_rows == total + (int64_t)num_utts * context);
+  }
   // The starts of the utterances' result rows and the fp64 prior offsets, in
   // one staged image (first, as ComputeProb stages its labels first).
   const size_t off_at = ((size_t)(num_utts + 1) * sizeof(int32_t) + 7) / 8 * 8;
@@ -828,9 +874,154 @@ const CuMatrix<BaseFloat> &NnetStack::Compute(const float *input, MatrixDim in_d
   const int32_t *d_starts = reinterpret_cast<const int32_t *>(base);
   const double *d_off = priors ? reinterpret_cast<const double *>(base + off_at) : nullptr;
 
+  if (plan.prefix() > 0)
+    PropagateTimeShared(input, in_dim, d_starts, num_utts, (int)total, pad_input, plan, rows);
   PropagateUtterances(input, in_dim, d_starts, num_utts, (int)total, pad_input,
-                      FusedLoglikes(apply_log) ? nc - 1 : nc);
+                      FusedLoglikes(apply_log) ? nc - 1 : nc, plan.prefix());
   return Loglikes(apply_log, d_off, (int)total);
+}
+
+TimePlan NnetStack::TimeSharedPlan() const {
+  std::vector<TimeComp> desc(comps_.size());
+  for (size_t i = 0; i < comps_.size(); i++) {
+    const Comp &c = comps_[i];
+    TimeComp &t = desc[i];
+    const std::vector<int32> ctx = c.c->Context();
+    t.input_dim = c.c->InputDim();
+    t.output_dim = c.c->OutputDim();
+    t.left = -ctx.front();
+    t.right = ctx.back();
+    if (c.splice) {
+      t.kind = TimeComp::kSplice;
+      t.contiguous = ctx.back() - ctx.front() + 1 == (int32)ctx.size();
+      t.const_dim = c.splice->ConstComponentDim();
+    } else if (c.conv) {
+      t.kind = TimeComp::kConv;
+      t.in_height = c.conv->In_height();
+      t.in_width = c.conv->In_width();
+      t.in_channel = c.conv->In_channels();
+      t.kernel_height = c.conv->Kernel_height();
+      t.kernel_width = c.conv->Kernel_width();
+      t.stride = c.conv->Stride();
+      t.pad_height = c.conv->In_pad_height();
+      t.pad_width = c.conv->In_pad_width();
+      t.group = c.conv->Group();
+      t.out_height = c.conv->Out_height();
+      t.out_width = c.conv->Out_width();
+    } else if (c.pool) {
+      t.kind = TimeComp::kPool;
+      t.in_height = c.pool->In_height();
+      t.in_width = c.pool->In_width();
+      t.in_channel = c.pool->In_channels();
+      t.pool_height = c.pool->Pool_height_dim();
+      t.pool_width = c.pool->Pool_width_dim();
+      t.pool_channel = c.pool->Pool_channel_dim();
+      t.overlap = c.pool->Overlapping();
+    } else if (c.relu) {
+      t.kind = TimeComp::kRelu;
+    }
+  }
+  return make_time_plan(desc, cnsl::nnet0::LiteralPath());
+}
+
+NnetStack::TimeMapInfo NnetStack::TimeMap(int level) const {
+  if (!time_shared_)
+    KALDI_ERR << "kcnn_nnet_time_map: the last forward pass was not kcnn_nnet_compute_shared's "
+              << "over time maps";
+  if (level < 0 || level >= (int)time_views_.size())
+    KALDI_ERR << "kcnn_nnet_time_map: level " << level << " outside [0, " << time_views_.size()
+              << ")";
+  return time_views_[level];
+}
+
+// The components the plan covers as time maps (time-plan.h), then the gather
+// into component plan.prefix()'s input; `rows` has been checked.
+void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
+                                    const int32_t *utt_start, int num_utts, int total,
+                                    bool pad_input, const TimePlan &plan, const TimeRows &rows) {
+  const int p = plan.prefix();
+  const int context = plan.levels[0].positions - 1;
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  time_views_.assign((size_t)p, TimeMapInfo());
+  auto view_of = [&](int l, const float *data, MatrixDim dim) {
+    const TimeLevel &lev = plan.levels[l];
+    TimeMapInfo &v = time_views_[l];
+    v.data = data;
+    v.dim = dim;
+    v.channels = lev.channels;
+    v.positions = lev.positions;
+    v.dilation = lev.dilation;
+  };
+  // a level's own map, sized as Compute sizes its outputs: without the fill
+  auto map_of = [&](int l) -> CuMatrix<BaseFloat> & {
+    CuMatrix<BaseFloat> &m = time_maps_[l];
+    const int r = (int)rows.computed[l], c = plan.levels[l].width;
+    if (m.NumRows() != r || m.NumCols() != c) m.Resize(r, c, kUndefined);
+    view_of(l, m.Data(), m.Dim());
+    return m;
+  };
+  // level 0: the frames themselves, clamped when padded
+  if (pad_input && context > 0) {
+    LayOutClamped(input, in_dim, utt_start, num_utts, total, context, LeftContext());
+    view_of(0, padded_input_.Data(), padded_input_.Dim());
+  } else {
+    view_of(0, input, in_dim);
+  }
+  KALDI_ASSERT(time_views_[0].dim.rows == rows.input_rows);
+  for (int l = 1; l < p; l++) {
+    const TimeLevel &lev = plan.levels[l], &below = plan.levels[l - 1];
+    const TimeMapInfo in = time_views_[l - 1];
+    const int nrows = (int)rows.computed[l];
+    if (lev.kind == TimeComp::kConv) {
+      // tap d: map'[rows] (+)= map[rows + delta d] W_d, GEMMs of the matrix layer
+      cnsl::nnet0::ConvolutionComponent *conv = comps_[l].conv;
+      const CuMatrix<BaseFloat> &W = conv->LinearParams();
+      CuMatrix<BaseFloat> &m = map_of(l);
+      CuSubMatrix<BaseFloat> y(m.Data(), nrows, lev.channels, m.Stride());
+      const bool on_splice = below.kind == TimeComp::kSplice;
+      for (int d = 0; d < lev.taps; d++) {
+        CuSubMatrix<BaseFloat> a(
+            const_cast<float *>(in.data) + (int64_t)below.dilation * d * in.dim.stride, nrows,
+            below.width, in.dim.stride);
+        // weight row i + d kh + c kh kw: a whole frame's block on the Splice
+        // (c = 0, kh = the frame), every kw-th row from d above (kh = 1)
+        float *w0 = const_cast<float *>(W.Data());
+        CuSubMatrix<BaseFloat> wd =
+            on_splice ? CuSubMatrix<BaseFloat>(w0 + (int64_t)d * below.width * W.Stride(),
+                                               below.width, lev.channels, W.Stride())
+                      : CuSubMatrix<BaseFloat>(w0 + (int64_t)d * W.Stride(), below.width,
+                                               lev.channels, lev.taps * W.Stride());
+        if (d == 0)
+          y.AddMatMatBias(1.0f, a, kNoTrans, wd, kNoTrans, conv->BiasParams());
+        else
+          y.AddMatMat(1.0f, a, kNoTrans, wd, kNoTrans, 1.0f);
+      }
+      continue;
+    }
+    // a pool, a ReLU, or a pool and the ReLU on it in one pass
+    const bool pool = lev.kind == TimeComp::kPool;
+    const bool both = pool && l + 1 < p && plan.levels[l + 1].kind == TimeComp::kRelu;
+    MatrixDim in_rows = in.dim;
+    in_rows.rows = (int)rows.computed[l - 1];
+    CuMatrix<BaseFloat> &m = map_of(l);
+    CuMatrix<BaseFloat> *act = both ? &map_of(l + 1) : (pool ? nullptr : &m);
+    CuProfileScope prof("kn_timemap_epilogue");
+    CNSL_SAFE_CALL(kn_timemap_epilogue(
+        in.data, in_rows, pool ? m.Data() : nullptr, pool ? m.Dim() : MatrixDim{0, 0, 0},
+        act ? act->Data() : nullptr, act ? act->Dim() : MatrixDim{0, 0, 0}, nrows,
+        pool ? lev.taps : 1, pool ? lev.pool_channel : 1, below.dilation, st));
+    if (both) l++;
+  }
+  const TimeLevel &top = plan.levels[p - 1];
+  CuMatrix<BaseFloat> &y = out(p - 1).value;
+  KALDI_ASSERT(comps_[p - 1].c->OutputDim() == top.channels * top.positions);
+  if (y.NumRows() != total || y.NumCols() != top.channels * top.positions)
+    y.Resize(total, top.channels * top.positions, kUndefined);  // written whole
+  MatrixDim map_dim = time_views_[p - 1].dim;
+  map_dim.rows = (int)rows.computed[p - 1];
+  CuProfileScope prof("kn_timemap_gather");
+  CNSL_SAFE_CALL(kn_timemap_gather(time_views_[p - 1].data, map_dim, y.Data(), y.Dim(), utt_start,
+                                   num_utts, context, top.positions, top.dilation, st));
 }
 
 void NnetStack::CheckPriors(const float *priors, int num_priors, bool apply_log,

@@ -6,7 +6,9 @@
 // and what follows a training iteration: the <Nnet> file (Nnet::Read / Write),
 // the scaled, Dropout-free copy (nnet-am-copy), ComputeProb
 // (nnet-compute-prob) and Compute, the whole-utterance forward pass of
-// upstream NnetComputer (nnet-am-compute, the decodable); and what comes
+// upstream NnetComputer (nnet-am-compute, the decodable), with ComputeShared,
+// the same pass with the convolutional prefix run once per time step
+// (time-plan.h); and what comes
 // before one: PropagateFrames, a minibatch as rows of a corpus that stays on
 // the device (nnet-get-egs and nnet-shuffle-egs without the window matrices).
 // Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
@@ -26,6 +28,7 @@
 #include "../nnet0/nnet-component-nnet0.h"
 #include "../nnet2/nnet-component.h"
 #include "frame-index.h"
+#include "time-plan.h"
 
 struct kcnn_component {
   kaldi::nnet2::Component *c;
@@ -173,6 +176,35 @@ class NnetStack {
   const CuMatrix<BaseFloat> &Compute(const float *in, MatrixDim in_dim, const int32_t *lengths,
                                      int num_utts, bool pad_input, const float *priors,
                                      int num_priors, float prior_scale, bool apply_log);
+  // Compute with the leading Splice -> {Convolution | Maxpool | ReLU}...
+  // components (the prefix, time-plan.h) run once per time step instead of
+  // once per window: each is a TIME MAP, one row per row of the (clamped)
+  // input and one column per channel -- a convolution tap a GEMM of the matrix
+  // layer on a row-shifted view (AddMatMatBias, then AddMatMat with beta = 1),
+  // pools and ReLUs one pass each (kn_timemap_epilogue) -- and a gather
+  // (kn_timemap_gather) then writes Output(prefix - 1) in the window layout
+  // Compute gives it; from component `prefix` upwards the pass is Compute's
+  // own.  Same arguments, checks, result and state as Compute; to the error
+  // bar of the GEMMs, not the bits, the same values.  Output(i) below prefix -
+  // 1 throws afterwards (those activations are never formed); TimeMap gives
+  // the maps.  A stack the plan declines runs Compute itself.
+  const CuMatrix<BaseFloat> &ComputeShared(const float *in, MatrixDim in_dim,
+                                           const int32_t *lengths, int num_utts, bool pad_input,
+                                           const float *priors, int num_priors,
+                                           float prior_scale, bool apply_log);
+  // The plan of ComputeShared for this stack as the literal path now stands
+  // (no levels: declined); host only.
+  TimePlan TimeSharedPlan() const;
+  // Level `level` (the output of component `level`) of the last ComputeShared:
+  // its first dim.rows rows are computed, row s being row s of the level-0
+  // map, the (clamped) input.  Valid until the next forward call; throws when
+  // the last forward was not ComputeShared's over time maps.
+  struct TimeMapInfo {
+    const float *data = nullptr;
+    MatrixDim dim = {0, 0, 0};
+    int channels = 0, positions = 0, dilation = 0;
+  };
+  TimeMapInfo TimeMap(int level) const;
 
   // Propagate on a minibatch given as `num` rows (HOST indices, any order,
   // repeats allowed) of a corpus that stays on the device: `feats` holds whole
@@ -332,9 +364,20 @@ class NnetStack {
   // the last with FusedLoglikes): the last output, or its `total` rows of
   // log-likelihoods less d_off (device, or NULL)
   const CuMatrix<BaseFloat> &Loglikes(bool apply_log, const double *d_off, int total);
-  // Compute's forward pass over the first `count` components
+  // Compute's forward pass over components first .. count - 1; first > 0:
+  // ComputeShared's time maps have written component first's input
   void PropagateUtterances(const float *in, MatrixDim in_dim, const int32_t *utt_start,
-                           int num_utts, int total, bool pad_input, int count);
+                           int num_utts, int total, bool pad_input, int count, int first = 0);
+  void LayOutClamped(const float *in, MatrixDim in_dim, const int32_t *utt_start, int num_utts,
+                     int total, int ext, int left);
+  // Compute and ComputeShared (share_time) under the caller's name
+  const CuMatrix<BaseFloat> &ComputeOn(const float *in, MatrixDim in_dim, const int32_t *lengths,
+                                       int num_utts, bool pad_input, const float *priors,
+                                       int num_priors, float prior_scale, bool apply_log,
+                                       bool share_time, const char *who);
+  void PropagateTimeShared(const float *in, MatrixDim in_dim, const int32_t *utt_start,
+                           int num_utts, int total, bool pad_input, const TimePlan &plan,
+                           const TimeRows &rows);
 
   Activation &in(int i) { return acts_[i]; }
   Activation &out(int i) { return acts_[i + 1]; }
@@ -367,6 +410,12 @@ class NnetStack {
   LabelStaging utts_;                   // Compute's utterance starts and prior offsets
   CuMatrix<BaseFloat> padded_input_;    // Compute's clamped input frames, when laid out
   CuMatrix<BaseFloat> loglikes_;        // Compute's result with apply_log
+  // the last forward was ComputeShared's over time maps: time_views_ holds
+  // its levels, level 0 a view of the input or of padded_input_, the others
+  // of time_maps_ (one a component, sized once)
+  bool time_shared_ = false;
+  std::vector<CuMatrix<BaseFloat>> time_maps_;
+  std::vector<TimeMapInfo> time_views_;
   // the last forward was PropagateFrames' through a first Splice: component
   // 0's input is the corpus, not a window matrix, and it has no Backprop
   bool frames_fused_ = false;

@@ -1,0 +1,238 @@
+// capi/time-plan.h -- host-side plan of NnetStack::ComputeShared (nnet-stack.h;
+// kcnn_nnet_compute_shared): which leading components of a stack run as TIME
+// MAPS, one row per time step of the concatenated (padded) utterances instead
+// of one row per frame holding the frame's whole window, and the row
+// bookkeeping of such a pass.  Pure host code with no GPU call: a pass whose
+// rows do not fit is refused here, before any launch, so it can never become
+// an out-of-range device access.  Header-only so that a stand-alone program
+// can run it under a host sanitizer (scripts/time_plan_check.cc).
+//
+// A level is the output of one component of the prefix, described by (C, n,
+// delta): channels, positions per window, dilation.  The window-layout row of
+// result frame t of utterance u has element (position k, channel c) at column
+// k + c n, and that element is map[base_u + t + delta k][c]; base_u, the
+// utterance's first row in the (padded) input, is the same at every level: the
+// maps keep the input's row numbering.
+//   level 0, the Splice output: the map is the (clamped) feature matrix, rows
+//     of `width` = input-dim floats; n = L + R + 1, delta = 1 (C = 1)
+//   Convolution, kw taps: n' = n - kw + 1, delta' = delta;
+//     map'[s][g] = b[g] + sum_d map[s + delta d][:] . W_d[:][g]
+//   Maxpool 1 x pw x pc: n' = n / pw, delta' = delta pw, C' = C / pc;
+//     map'[s][oc] folds map[s + delta w][oc pc + c] over c (outer), w (inner)
+//   ReLU: element-wise
+// Level l reads `reach` = delta (taps - 1) rows past its own row, so with M
+// rows of input the first M - (sum of the reaches up to l) rows of level l are
+// computed, in one piece over all utterances.  The rows whose taps cross from
+// one utterance into the next are computed and never read: utterance u's
+// windows read its rows [base_u, base_u + F_u + delta (n - 1)) only (F_u its
+// result frames), and delta (n - 1) never grows from level to level.
+#ifndef KCNN_CAPI_TIME_PLAN_H_
+#define KCNN_CAPI_TIME_PLAN_H_
+
+#include <stdint.h>
+
+#include <sstream>
+#include <string>
+#include <vector>
+
+namespace kcnn {
+
+constexpr int64_t kTimeRowLimit = (int64_t)1 << 31;  // rows of a matrix
+// positions per window the gather stages for one channel (its LDS tile)
+constexpr int kTimeMaxPositions = 8192;
+
+// What the plan reads of a component (NnetStack fills it from the component).
+struct TimeComp {
+  enum Kind { kOther, kSplice, kConv, kPool, kRelu };
+  Kind kind = kOther;
+  int input_dim = 0, output_dim = 0;
+  // -Context().front(), Context().back(); every component has them
+  int left = 0, right = 0;
+  // Splice
+  bool contiguous = true;  // the context is left .. right without gaps
+  int const_dim = 0;
+  // Convolution and Maxpool
+  int in_height = 0, in_width = 0, in_channel = 0;
+  // Convolution
+  int kernel_height = 0, kernel_width = 0, stride = 1, pad_height = 0, pad_width = 0;
+  int group = 0, out_height = 0, out_width = 0;
+  // Maxpool
+  int pool_height = 0, pool_width = 0, pool_channel = 0;
+  bool overlap = false;
+};
+
+struct TimeLevel {
+  TimeComp::Kind kind;
+  int channels, positions, dilation;  // (C, n, delta) of this level's map
+  int width;                          // floats a map row holds: C, input-dim at level 0
+  int taps;                           // kw of a Convolution, pw of a Maxpool, else 1
+  int pool_channel;                   // pc of a Maxpool, else 1
+  int reach;                          // rows past its own that a row reads below: delta_in (taps - 1)
+  int sum_reach;                      // the reaches of levels 1 .. this one
+};
+
+struct TimePlan {
+  // levels[l] is the output of component l; empty when the plan declines
+  std::vector<TimeLevel> levels;
+  std::string declined;  // why, when it does
+  int prefix() const { return (int)levels.size(); }
+};
+
+inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_path) {
+  TimePlan plan;
+  std::ostringstream why;
+  auto decline = [&]() {
+    plan.levels.clear();
+    plan.declined = why.str();
+    return plan;
+  };
+  if (literal_path) {
+    why << "the literal path is on";
+    return decline();
+  }
+  if (comps.empty() || comps[0].kind != TimeComp::kSplice) {
+    why << "component 0 is not a SpliceComponent";
+    return decline();
+  }
+  const TimeComp &sp = comps[0];
+  if (!sp.contiguous || sp.const_dim != 0) {
+    why << "component 0 has a gapped context or a const-component-dim";
+    return decline();
+  }
+  if (sp.left < 0 || sp.right < 0 || sp.input_dim < 1 ||
+      (int64_t)sp.left + sp.right + 1 > kTimeMaxPositions) {
+    why << "component 0 has a context of " << sp.left << " + " << sp.right << " frames";
+    return decline();
+  }
+  for (size_t i = 1; i < comps.size(); i++)
+    if (comps[i].left != 0 || comps[i].right != 0) {
+      why << "component " << i << " has a context of its own";
+      return decline();
+    }
+  TimeLevel cur;
+  cur.kind = TimeComp::kSplice;
+  cur.channels = 1;
+  cur.positions = sp.left + sp.right + 1;
+  cur.dilation = 1;
+  cur.width = sp.input_dim;
+  cur.taps = cur.pool_channel = 1;
+  cur.reach = cur.sum_reach = 0;
+  plan.levels.push_back(cur);
+  bool conv_seen = false;
+  for (size_t i = 1; i < comps.size(); i++) {
+    const TimeComp &c = comps[i];
+    const TimeLevel in = plan.levels.back();
+    TimeLevel out = in;
+    out.kind = c.kind;
+    out.taps = out.pool_channel = 1;
+    if (c.kind == TimeComp::kConv) {
+      const bool first = in.kind == TimeComp::kSplice;
+      // directly on the Splice a filter spans the whole frame; above, one row
+      const int height = first ? in.width : 1, chans = first ? 1 : in.channels;
+      if (c.in_channel != chans || c.in_height != height || c.kernel_height != c.in_height ||
+          c.pad_height != 0 || c.pad_width != 0 || c.in_width != in.positions ||
+          c.stride != 1 || c.kernel_width < 1 || c.kernel_width > c.in_width ||
+          c.out_height != 1 || c.out_width != c.in_width - c.kernel_width + 1 || c.group < 1) {
+        why << "Convolution " << i << " is not a 1-D convolution along time of its input ("
+            << chans << " channels, height " << height << ", " << in.positions << " positions)";
+        return decline();
+      }
+      out.channels = out.width = c.group;
+      out.positions = c.out_width;
+      out.taps = c.kernel_width;
+      conv_seen = true;
+    } else if (c.kind == TimeComp::kPool) {
+      if (!conv_seen) break;  // (a pool of the Splice output itself: no prefix)
+      if (c.overlap || c.pool_height != 1 || c.in_height != 1 || c.pool_width < 1 ||
+          c.pool_channel < 1 || c.in_width != in.positions || c.in_channel != in.channels ||
+          c.in_width % c.pool_width != 0 || c.in_channel % c.pool_channel != 0) {
+        why << "Maxpool " << i << " is overlapping, pools over height or does not divide its "
+            << "input (" << in.channels << " channels, " << in.positions << " positions) evenly";
+        return decline();
+      }
+      out.channels = out.width = in.channels / c.pool_channel;
+      out.positions = in.positions / c.pool_width;
+      out.dilation = in.dilation * c.pool_width;
+      out.taps = c.pool_width;
+      out.pool_channel = c.pool_channel;
+    } else if (c.kind == TimeComp::kRelu) {
+      if (!conv_seen) break;
+      if (c.input_dim != in.channels * in.positions) break;  // (the stack checks dimensions)
+    } else {
+      break;
+    }
+    out.reach = in.dilation * (out.taps - 1);
+    out.sum_reach = in.sum_reach + out.reach;
+    plan.levels.push_back(out);
+  }
+  if (!conv_seen) {
+    why << "no Convolution follows component 0";
+    return decline();
+  }
+  return plan;
+}
+
+// The rows of one pass: utterance u has len[u] input frames and, with L + R =
+// context, gives F_u = len[u] (pad_input: it is laid out clamped, len[u] +
+// context rows) or len[u] - context result rows.
+struct TimeRows {
+  int64_t input_rows = 0;              // M: the rows of the level-0 map
+  int64_t result_rows = 0;             // the sum of F_u
+  std::vector<int64_t> base, frames;   // base_u, F_u
+  std::vector<int64_t> computed;       // per level: its first `computed` rows are
+};
+
+// "" and *rows, or what is wrong: lengths the pass cannot take, 2^31 rows, a
+// tap or a window that would read past the rows computed below it.
+inline std::string plan_time_rows(const TimePlan &plan, const int32_t *lengths, int num_utts,
+                                  bool pad_input, TimeRows *rows) {
+  std::ostringstream err;
+  if (plan.levels.empty()) return "no plan";
+  if (lengths == nullptr || num_utts < 1) return "no utterances";
+  const int64_t context = plan.levels[0].positions - 1;
+  TimeRows r;
+  for (int u = 0; u < num_utts; u++) {
+    const int64_t f = pad_input ? lengths[u] : lengths[u] - context;
+    if (f < 1) {
+      err << "utterance " << u << " has " << lengths[u] << " frames; at least "
+          << (pad_input ? 1 : context + 1) << " are needed";
+      return err.str();
+    }
+    r.base.push_back(r.input_rows);
+    r.frames.push_back(f);
+    r.input_rows += f + context;
+    r.result_rows += f;
+    if (r.input_rows >= kTimeRowLimit) return "too many rows";
+  }
+  for (size_t l = 0; l < plan.levels.size(); l++) {
+    const TimeLevel &lev = plan.levels[l];
+    const int64_t computed = r.input_rows - lev.sum_reach;
+    // the highest row of the level below that this level's last row reads
+    if (l > 0 && computed - 1 + lev.reach > r.computed[l - 1] - 1) {
+      err << "level " << l << " reads past the " << r.computed[l - 1] << " rows below it";
+      return err.str();
+    }
+    // every window of every utterance lies in the computed rows
+    const int64_t span = (int64_t)lev.dilation * (lev.positions - 1);
+    if (computed < 1 || span > context ||
+        r.base.back() + r.frames.back() - 1 + span > computed - 1) {
+      err << "level " << l << " computes " << computed << " rows, fewer than its windows read";
+      return err.str();
+    }
+    r.computed.push_back(computed);
+  }
+  *rows = r;
+  return "";
+}
+
+// The rows of level `l` that utterance u's windows read: [first, first + num).
+inline void time_valid_rows(const TimePlan &plan, const TimeRows &rows, int l, int u,
+                            int64_t *first, int64_t *num) {
+  const TimeLevel &lev = plan.levels[(size_t)l];
+  *first = rows.base[(size_t)u];
+  *num = rows.frames[(size_t)u] + (int64_t)lev.dilation * (lev.positions - 1);
+}
+
+}  // namespace kcnn
+
+#endif  // KCNN_CAPI_TIME_PLAN_H_

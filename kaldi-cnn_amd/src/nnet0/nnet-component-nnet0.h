@@ -68,6 +68,7 @@ class ConvolutionComponent : public nnet2::UpdatableComponent {
   inline int32 KernelDim() const { return kernel_height_ * kernel_width_ * in_channel_; }
   inline int32 Kernel_height() const { return kernel_height_; }
   inline int32 Kernel_width() const { return kernel_width_; }
+  inline int32 Stride() const { return stride_; }
 
   void Init(BaseFloat learning_rate, int32 in_height, int32 in_width,
             int32 in_channels, int32 in_pad_height, int32 in_pad_width,
@@ -250,6 +251,10 @@ class MaxpoolComponent : public nnet2::Component {
   inline int32 In_height() const { return in_height_; }
   inline int32 In_width() const { return in_width_; }
   inline int32 In_channels() const { return in_channel_; }
+  inline int32 Pool_height_dim() const { return pool_height_dim_; }
+  inline int32 Pool_width_dim() const { return pool_width_dim_; }
+  inline int32 Pool_channel_dim() const { return pool_channel_dim_; }
+  inline bool Overlapping() const { return overlap_ || overlap2D_; }
   // pool_channel_dim when the pool is channel-only (1 x 1 x pc, no overlap,
   // pc in {2, 4, 8}): the shape the convolution forward can fuse; else 0.
   int32 FusableChannelPool() const;

@@ -303,6 +303,7 @@ class SpliceComponent : public Component {
   virtual int32 InputDim() const { return input_dim_; }
   virtual int32 OutputDim() const;
   virtual std::vector<int32> Context() const { return context_; }
+  int32 ConstComponentDim() const { return const_component_dim_; }
   using Component::Propagate;
   virtual void Propagate(const ChunkInfo &in_info, const ChunkInfo &out_info,
                          const CuMatrixBase<BaseFloat> &in,

@@ -238,6 +238,36 @@ int kn_normalize_backprop(const float *in_value, MatrixDim iv_dim, const float *
                           MatrixDim od_dim, float *in_deriv, MatrixDim id_dim,
                           kcnn_stream_t st);
 
+/* ---- nnet-timemap-kernels.hip: the time-shared whole-utterance forward ---- */
+
+/* One pass over a time map (capi/time-plan.h): `in` holds one row per time
+ * step and one column per channel.  With pooled != NULL, a MaxpoolComponent
+ * 1 x pool_width x pool_channel along time at dilation delta: pooled(r, oc) is
+ * the reference's fold (start -1e20f, replace when v < x) over c < pool_channel
+ * (outer), w < pool_width (inner) of in(r + delta w, oc pool_channel + c), for
+ * r < rows; in_dim.rows must hold the last row's highest tap.  With relu !=
+ * NULL, RectifiedLinearComponent::Propagate (x < 0 -> 0) of the pooled values,
+ * or of `in` itself when pooled == NULL (pool_width = pool_channel = 1), to
+ * relu(r, oc).  Both: the pool level and the ReLU level from one read.  16-byte
+ * accesses when pool_channel = 1 and every stride, base and the column count
+ * allow; scalar otherwise. */
+int kn_timemap_epilogue(const float *in, MatrixDim in_dim, float *pooled, MatrixDim p_dim,
+                        float *relu, MatrixDim r_dim, int rows, int pool_width, int pool_channel,
+                        int delta, kcnn_stream_t st);
+
+/* The window layout of the last time map: out(r, k + c positions) = map(r + u
+ * ext + dilation k, c) for result row r of utterance u (utt_start: DEVICE,
+ * num_utts + 1 ascending entries from 0 to out_dim.rows, as for
+ * kn_splice_ragged_prop; the map holds ext more rows an utterance), k <
+ * positions <= KN_TIMEMAP_MAX_POSITIONS, c < map_dim.cols.  The map is read
+ * along c and the output written in contiguous runs, staged through LDS.  A
+ * source row is clamped into the map, so a table that disagrees with the
+ * matrices still reads inside it. */
+#define KN_TIMEMAP_MAX_POSITIONS 8192
+int kn_timemap_gather(const float *map, MatrixDim map_dim, float *out, MatrixDim out_dim,
+                      const int *utt_start, int num_utts, int ext, int positions, int dilation,
+                      kcnn_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,513 @@
+// scripts/time_plan_check.cc -- the host plan of the time-shared whole-utterance
+// forward (kaldi-cnn_amd/src/capi/time-plan.h) as a stand-alone host program,
+// for a run under a host sanitizer.  No GPU call.
+//
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
+//       -Ikaldi-cnn_amd/src scripts/time_plan_check.cc -o time_plan_check
+//   ./time_plan_check tests/golden/nnet.config tests/golden/train_conv.config
+//
+// 1. The two golden configs (parsed here, line by line): their prefixes and
+//    (C, n, delta) chains.
+// 2. Every decline of the plan.
+// 3. For utterances of (1, 37, 5) frames, padded and not (unpadded: that many
+//    RESULT frames, the lengths themselves being refused there): the bases,
+//    the computed and the valid rows of every level, and a host model of the
+//    pass.  The model runs the plan on integer data exactly as the device
+//    pass does -- taps on row-shifted maps, the dilated fold, the gather --
+//    with every map access checked against the rows computed, marks the rows
+//    the gather and the taps below a read row touch, and compares the gathered
+//    matrix with the window pass (each frame's own window through the same
+//    layers in the window layout of the reference).  A row whose taps cross
+//    into the next utterance must be read by nothing.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <fstream>
+#include <map>
+#include <random>
+
+#include "capi/time-plan.h"
+
+using kcnn::TimeComp;
+using kcnn::TimeLevel;
+using kcnn::TimePlan;
+using kcnn::TimeRows;
+
+namespace {
+
+int failures = 0;
+long checks = 0;
+
+void expect(bool ok, const char *what, long a = 0, long b = 0) {
+  checks++;
+  if (ok) return;
+  if (failures < 20) printf("WRONG: %s (%ld, %ld)\n", what, a, b);
+  failures++;
+}
+
+// ---- a config line -> TimeComp ------------------------------------------------
+TimeComp parse_line(const std::string &line) {
+  std::istringstream is(line);
+  std::string type, tok;
+  is >> type;
+  std::map<std::string, std::string> kv;
+  while (is >> tok) {
+    const size_t eq = tok.find('=');
+    if (eq != std::string::npos) kv[tok.substr(0, eq)] = tok.substr(eq + 1);
+  }
+  auto num = [&](const char *k, int def = 0) {
+    return kv.count(k) ? atoi(kv[k].c_str()) : def;
+  };
+  TimeComp c;
+  if (type == "SpliceComponent") {
+    c.kind = TimeComp::kSplice;
+    c.input_dim = num("input-dim");
+    c.left = num("left-context");
+    c.right = num("right-context");
+    c.contiguous = !kv.count("context");
+    c.const_dim = num("const-component-dim");
+    c.output_dim = c.input_dim * (c.left + c.right + 1);
+  } else if (type == "ConvolutionComponent") {
+    c.kind = TimeComp::kConv;
+    c.in_height = num("in-height");
+    c.in_width = num("in-width");
+    c.in_channel = num("in-channel");
+    c.kernel_height = num("kernel-height");
+    c.kernel_width = num("kernel-width");
+    c.stride = num("stride", 1);
+    c.pad_height = num("in-pad-height");
+    c.pad_width = num("in-pad-width");
+    c.group = num("group");
+    c.out_height = num("out-height");
+    c.out_width = num("out-width");
+    c.input_dim = c.in_height * c.in_width * c.in_channel;
+    c.output_dim = c.out_height * c.out_width * c.group;
+  } else if (type == "MaxpoolComponent") {
+    c.kind = TimeComp::kPool;
+    c.in_height = num("in-height");
+    c.in_width = num("in-width");
+    c.in_channel = num("in-channel");
+    c.pool_height = num("pool-height-dim");
+    c.pool_width = num("pool-width-dim");
+    c.pool_channel = num("pool-channel-dim");
+    c.input_dim = c.in_height * c.in_width * c.in_channel;
+    c.output_dim = c.input_dim / (c.pool_height * c.pool_width * c.pool_channel);
+  } else if (type == "RectifiedLinearComponent") {
+    c.kind = TimeComp::kRelu;
+    c.input_dim = c.output_dim = num("dim");
+  } else {
+    c.input_dim = kv.count("dim") ? num("dim") : num("input-dim");
+    c.output_dim = kv.count("dim") ? num("dim") : num("output-dim");
+  }
+  return c;
+}
+
+std::vector<TimeComp> parse_config(const std::string &text) {
+  std::vector<TimeComp> out;
+  std::istringstream is(text);
+  std::string line;
+  while (std::getline(is, line)) {
+    const size_t b = line.find_first_not_of(" \t\r");
+    if (b == std::string::npos || line[b] == '#') continue;
+    out.push_back(parse_line(line.substr(b)));
+  }
+  return out;
+}
+
+struct Cnd {
+  int c, n, d;
+};
+
+void check_chain(const char *name, const std::vector<TimeComp> &comps,
+                 const std::vector<Cnd> &want) {
+  const TimePlan plan = kcnn::make_time_plan(comps, false);
+  expect(plan.prefix() == (int)want.size(), name, plan.prefix(), (long)want.size());
+  if (plan.prefix() != (int)want.size()) {
+    printf("  declined: %s\n", plan.declined.c_str());
+    return;
+  }
+  for (size_t l = 0; l < want.size(); l++) {
+    const TimeLevel &lev = plan.levels[l];
+    expect(lev.channels == want[l].c && lev.positions == want[l].n && lev.dilation == want[l].d,
+           "a level's (C, n, delta)", (long)l, lev.channels * 1000 + lev.positions);
+  }
+  printf("%s: prefix %d, ending at (%d, %d, %d)\n", name, plan.prefix(),
+         plan.levels.back().channels, plan.levels.back().positions, plan.levels.back().dilation);
+}
+
+// ---- the shrunken nets ----------------------------------------------------------
+std::string conv_line(int h, int w, int c, int kw, int g, const char *extra = "") {
+  std::ostringstream s;
+  s << "ConvolutionComponent in-height=" << h << " in-width=" << w << " in-channel=" << c
+    << " kernel-height=" << h << " kernel-width=" << kw << " stride=1 group=" << g
+    << " out-height=1 out-width=" << w - kw + 1 << " " << extra << "\n";
+  return s.str();
+}
+std::string pool_line(int w, int c, int pw, int pc, int ph = 1) {
+  std::ostringstream s;
+  s << "MaxpoolComponent in-height=1 in-width=" << w << " in-channel=" << c
+    << " pool-height-dim=" << ph << " pool-width-dim=" << pw << " pool-channel-dim=" << pc << "\n";
+  return s.str();
+}
+std::string splice_line(int d, int l, int r, int cdim = 0) {
+  std::ostringstream s;
+  s << "SpliceComponent input-dim=" << d << " left-context=" << l << " right-context=" << r
+    << " const-component-dim=" << cdim << "\n";
+  return s.str();
+}
+std::string relu_line(int dim) {
+  return "RectifiedLinearComponent dim=" + std::to_string(dim) + "\n";
+}
+std::string fc_line(int i, int o) {
+  return "FullyConnectedComponent input-dim=" + std::to_string(i) + " output-dim=" +
+         std::to_string(o) + "\n";
+}
+
+// Splice d = 8, L = R = 5; conv kw 4 -> 32, ReLU; conv kw 3 -> 32; pool 1 x 2 x
+// pc; ReLU; conv kw 2 -> 64 (dilation 2); ReLU; FC
+std::string shrunken(int pc) {
+  const int c2 = 32 / pc;
+  return splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + relu_line(8 * 32) +
+         conv_line(1, 8, 32, 3, 32) + pool_line(6, 32, 2, pc) + relu_line(3 * c2) +
+         conv_line(1, 3, c2, 2, 64) + relu_line(2 * 64) + fc_line(128, 10);
+}
+
+void check_declines() {
+  struct Case {
+    const char *what;
+    std::string config;
+    bool literal;
+  };
+  const std::string tail = relu_line(8 * 32) + fc_line(8 * 32, 10);
+  const std::vector<Case> cases = {
+      {"component 0 is not a Splice", relu_line(88) + splice_line(88, 0, 0), false},
+      {"a gapped Splice context",
+       "SpliceComponent input-dim=8 context=-5:0:5 const-component-dim=0\n" +
+           conv_line(8, 3, 1, 2, 4),
+       false},
+      {"const-component-dim", splice_line(8, 5, 5, 2) + fc_line(68, 10), false},
+      {"no Convolution follows", splice_line(8, 5, 5) + fc_line(88, 10), false},
+      {"a ReLU on the Splice", splice_line(8, 5, 5) + relu_line(88) + conv_line(8, 11, 1, 4, 32),
+       false},
+      {"a pool on the Splice", splice_line(1, 5, 5) + pool_line(11, 1, 1, 1) + fc_line(11, 4),
+       false},
+      {"in-channel != 1 on the Splice", splice_line(8, 5, 5) + conv_line(4, 11, 2, 4, 32) + tail,
+       false},
+      {"kernel-height != in-height",
+       splice_line(8, 5, 5) +
+           "ConvolutionComponent in-height=8 in-width=11 in-channel=1 kernel-height=4 "
+           "kernel-width=4 stride=1 group=32 out-height=5 out-width=8\n",
+       false},
+      {"padding", splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32, "in-pad-width=1") + tail,
+       false},
+      {"height padding", splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32, "in-pad-height=1") + tail,
+       false},
+      {"in-width != n", splice_line(8, 5, 5) + conv_line(8, 10, 1, 4, 32) + tail, false},
+      {"a second Convolution with in-width != n",
+       splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + conv_line(1, 7, 32, 3, 32), false},
+      {"a second Convolution with other channels",
+       splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + conv_line(1, 8, 16, 3, 32), false},
+      {"an overlapping pool", "", false},  // (filled below)
+      {"pool-height-dim != 1",
+       splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + pool_line(8, 32, 2, 1, 2), false},
+      {"a pool that does not divide the width",
+       splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + pool_line(8, 32, 3, 1), false},
+      {"a pool that does not divide the channels",
+       splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) + pool_line(8, 32, 2, 5), false},
+      {"a Splice above", shrunken(1) + splice_line(10, 1, 1), false},
+      {"the literal path", shrunken(1), true},
+  };
+  for (const Case &c : cases) {
+    std::vector<TimeComp> comps = parse_config(c.config);
+    if (std::string(c.what) == "an overlapping pool") {
+      comps = parse_config(splice_line(8, 5, 5) + conv_line(8, 11, 1, 4, 32) +
+                           pool_line(8, 32, 2, 1));
+      comps.back().overlap = true;
+    }
+    const TimePlan plan = kcnn::make_time_plan(comps, c.literal);
+    expect(plan.prefix() == 0 && !plan.declined.empty(), c.what, plan.prefix());
+    printf("declined (%s): %s\n", c.what, plan.declined.c_str());
+  }
+  // and the same stack with nothing wrong is taken
+  expect(kcnn::make_time_plan(parse_config(shrunken(1)), false).prefix() == 8, "shrunken prefix");
+  expect(kcnn::make_time_plan(parse_config(shrunken(4)), false).prefix() == 8,
+         "channel-pool prefix");
+  // a prefix ends before the first component of another kind
+  const std::vector<TimeComp> a = parse_config(
+      splice_line(5, 2, 2) + conv_line(5, 5, 1, 2, 4) + pool_line(4, 4, 2, 1) + relu_line(8) +
+      "NormalizeComponent dim=8\n" + fc_line(8, 12));
+  expect(kcnn::make_time_plan(a, false).prefix() == 4, "net A's prefix");
+}
+
+// ---- the host model of one pass ---------------------------------------------------
+struct Weights {
+  std::vector<std::vector<int>> w;  // [kernel row][g]
+  std::vector<int> b;
+};
+
+// the window pass: one frame's window row through component c
+std::vector<long> window_layer(const TimeComp &c, const Weights &wt, const std::vector<long> &x) {
+  std::vector<long> y((size_t)c.output_dim);
+  if (c.kind == TimeComp::kConv) {
+    const int H = c.in_height, W = c.in_width, kh = c.kernel_height, kw = c.kernel_width;
+    for (int g = 0; g < c.group; g++)
+      for (int ow = 0; ow < c.out_width; ow++) {
+        long s = wt.b[(size_t)g];
+        for (int ch = 0; ch < c.in_channel; ch++)
+          for (int d = 0; d < kw; d++)
+            for (int i = 0; i < kh; i++)
+              s += x[(size_t)(i + (ow + d) * H + ch * H * W)] *
+                   wt.w[(size_t)(i + d * kh + ch * kh * kw)][(size_t)g];
+        y[(size_t)(ow + g * c.out_width)] = s;
+      }
+  } else if (c.kind == TimeComp::kPool) {
+    const int W = c.in_width, OW = W / c.pool_width;
+    for (int oc = 0; oc < c.in_channel / c.pool_channel; oc++)
+      for (int ow = 0; ow < OW; ow++) {
+        long v = -(1L << 40);
+        for (int ch = 0; ch < c.pool_channel; ch++)
+          for (int w = 0; w < c.pool_width; w++) {
+            const long xv = x[(size_t)(ow * c.pool_width + w + (oc * c.pool_channel + ch) * W)];
+            if (v < xv) v = xv;
+          }
+        y[(size_t)(ow + oc * OW)] = v;
+      }
+  } else {
+    for (size_t i = 0; i < x.size(); i++) y[i] = x[i] < 0 ? 0 : x[i];
+  }
+  return y;
+}
+
+struct Map {
+  int64_t rows = 0;  // computed
+  int width = 0;
+  std::vector<long> v;
+  std::vector<char> read;  // rows read by the gather, or by a tap of a read row above
+  long at(int64_t r, int c) const {
+    if (r < 0 || r >= rows || c < 0 || c >= width) {
+      printf("WRONG: map access (%ld, %d) outside %ld x %d\n", (long)r, c, (long)rows, width);
+      exit(1);
+    }
+    return v[(size_t)(r * width + c)];
+  }
+};
+
+void run_model(const char *name, const std::string &config, const std::vector<int32_t> &lengths,
+               bool pad, unsigned seed) {
+  const std::vector<TimeComp> comps = parse_config(config);
+  const TimePlan plan = kcnn::make_time_plan(comps, false);
+  expect(plan.prefix() > 1, "the model's plan", plan.prefix());
+  if (plan.prefix() < 2) return;
+  const int p = plan.prefix(), L = comps[0].left, R = comps[0].right, D = comps[0].input_dim;
+  const int context = L + R, U = (int)lengths.size();
+  TimeRows rows;
+  const std::string bad = kcnn::plan_time_rows(plan, lengths.data(), U, pad, &rows);
+  expect(bad.empty(), "plan_time_rows accepts the lengths");
+  if (!bad.empty()) {
+    printf("  %s\n", bad.c_str());
+    return;
+  }
+  // the bases and the row counts
+  int64_t base = 0, total = 0;
+  for (int u = 0; u < U; u++) {
+    const int64_t f = pad ? lengths[(size_t)u] : lengths[(size_t)u] - context;
+    expect(rows.base[(size_t)u] == base && rows.frames[(size_t)u] == f, "base and frames", u);
+    base += pad ? lengths[(size_t)u] + context : lengths[(size_t)u];
+    total += f;
+  }
+  expect(rows.input_rows == base && rows.result_rows == total, "the row totals");
+  for (int l = 0; l < p; l++) {
+    const TimeLevel &lev = plan.levels[(size_t)l];
+    expect(rows.computed[(size_t)l] == base - lev.sum_reach, "computed rows", l);
+    // the highest row any tap of this level reads is a computed row below
+    if (l > 0)
+      expect(rows.computed[(size_t)l] - 1 + lev.reach <= rows.computed[(size_t)l - 1] - 1,
+             "a tap inside the buffer", l);
+    for (int u = 0; u < U; u++) {
+      int64_t first, num;
+      kcnn::time_valid_rows(plan, rows, l, u, &first, &num);
+      const int64_t next = u + 1 < U ? rows.base[(size_t)u + 1] : rows.input_rows;
+      expect(first == rows.base[(size_t)u] && first + num <= next &&
+                 first + num <= rows.computed[(size_t)l] &&
+                 num == rows.frames[(size_t)u] + (int64_t)lev.dilation * (lev.positions - 1),
+             "valid rows inside the utterance and the computed rows", l, u);
+    }
+  }
+  // integer data, weights and biases
+  std::mt19937 gen(seed);
+  auto draw = [&](int lo, int hi) { return lo + (int)(gen() % (unsigned)(hi - lo + 1)); };
+  std::vector<std::vector<std::vector<long>>> utts((size_t)U);
+  for (int u = 0; u < U; u++) {
+    utts[(size_t)u].assign((size_t)lengths[(size_t)u], std::vector<long>((size_t)D));
+    for (auto &fr : utts[(size_t)u])
+      for (long &x : fr) x = draw(-2, 2);
+  }
+  std::vector<Weights> wts((size_t)p);
+  for (int l = 1; l < p; l++)
+    if (comps[(size_t)l].kind == TimeComp::kConv) {
+      const TimeComp &c = comps[(size_t)l];
+      wts[(size_t)l].w.assign((size_t)(c.kernel_height * c.kernel_width * c.in_channel),
+                              std::vector<int>((size_t)c.group));
+      for (auto &r : wts[(size_t)l].w)
+        for (int &x : r) x = draw(-1, 1);
+      for (int g = 0; g < c.group; g++) wts[(size_t)l].b.push_back(draw(-3, 3));
+    }
+  // level 0: the frames, clamped when padded
+  std::vector<Map> maps((size_t)p);
+  maps[0].rows = rows.input_rows;
+  maps[0].width = D;
+  for (int u = 0; u < U; u++) {
+    const int T = lengths[(size_t)u];
+    const int n = pad ? T + context : T;
+    for (int r = 0; r < n; r++) {
+      const int f = pad ? std::min(std::max(r - L, 0), T - 1) : r;
+      for (int h = 0; h < D; h++) maps[0].v.push_back(utts[(size_t)u][(size_t)f][(size_t)h]);
+    }
+  }
+  expect((int64_t)maps[0].v.size() == rows.input_rows * D, "level 0's size");
+  // the levels, as the device pass runs them
+  for (int l = 1; l < p; l++) {
+    const TimeLevel &lev = plan.levels[(size_t)l], &below = plan.levels[(size_t)l - 1];
+    const TimeComp &c = comps[(size_t)l];
+    Map &m = maps[(size_t)l];
+    const Map &in = maps[(size_t)l - 1];
+    m.rows = rows.computed[(size_t)l];
+    m.width = lev.width;
+    m.v.assign((size_t)(m.rows * m.width), 0);
+    const bool on_splice = below.kind == TimeComp::kSplice;
+    for (int64_t s = 0; s < m.rows; s++)
+      for (int g = 0; g < m.width; g++) {
+        long v;
+        if (c.kind == TimeComp::kConv) {
+          v = wts[(size_t)l].b[(size_t)g];
+          for (int d = 0; d < lev.taps; d++)
+            for (int k = 0; k < below.width; k++) {
+              // tap d's weight rows: a block of the frame's on the Splice,
+              // every kw-th row from d above
+              const int wr = on_splice ? k + d * below.width : d + k * lev.taps;
+              v += in.at(s + (int64_t)below.dilation * d, k) * wts[(size_t)l].w[(size_t)wr][(size_t)g];
+            }
+        } else if (c.kind == TimeComp::kPool) {
+          v = -(1L << 40);
+          for (int ch = 0; ch < lev.pool_channel; ch++)
+            for (int w = 0; w < lev.taps; w++) {
+              const long x = in.at(s + (int64_t)below.dilation * w, g * lev.pool_channel + ch);
+              if (v < x) v = x;
+            }
+        } else {
+          v = in.at(s, g);
+          if (v < 0) v = 0;
+        }
+        m.v[(size_t)(s * m.width + g)] = v;
+      }
+  }
+  // the gather, against the window pass; the rows it reads are marked
+  const TimeLevel &top = plan.levels[(size_t)p - 1];
+  for (Map &m : maps) m.read.assign((size_t)m.rows, 0);
+  long compared = 0;
+  for (int u = 0; u < U; u++)
+    for (int64_t t = 0; t < rows.frames[(size_t)u]; t++) {
+      // the frame's own window, as Propagate is given it
+      std::vector<long> x;
+      for (int k = 0; k <= context; k++) {
+        const int T = lengths[(size_t)u];
+        const int f = pad ? std::min(std::max((int)t + k - L, 0), T - 1) : (int)t + k;
+        for (int h = 0; h < D; h++) x.push_back(utts[(size_t)u][(size_t)f][(size_t)h]);
+      }
+      for (int l = 1; l < p; l++) x = window_layer(comps[(size_t)l], wts[(size_t)l], x);
+      expect((int)x.size() == top.channels * top.positions, "the window row's width");
+      for (int k = 0; k < top.positions; k++) {
+        const int64_t src = rows.base[(size_t)u] + t + (int64_t)top.dilation * k;
+        maps[(size_t)p - 1].read[(size_t)src] = 1;
+        for (int ch = 0; ch < top.channels; ch++) {
+          const long got = maps[(size_t)p - 1].at(src, ch);
+          if (got != x[(size_t)(k + ch * top.positions)]) {
+            expect(false, "a gathered element differs from the window pass", u, (long)t);
+            return;
+          }
+          compared++;
+        }
+      }
+    }
+  // what the read rows read below, and that it stays inside the utterance's
+  // valid rows: nothing reads a row whose taps cross into the next utterance
+  for (int l = p - 1; l >= 1; l--) {
+    const TimeLevel &lev = plan.levels[(size_t)l], &below = plan.levels[(size_t)l - 1];
+    for (int64_t s = 0; s < maps[(size_t)l].rows; s++)
+      if (maps[(size_t)l].read[(size_t)s])
+        for (int d = 0; d < lev.taps; d++)
+          maps[(size_t)l - 1].read[(size_t)(s + (int64_t)below.dilation * d)] = 1;
+  }
+  long crossing = 0;
+  for (int l = 0; l < p; l++)
+    for (int64_t s = 0; s < maps[(size_t)l].rows; s++) {
+      bool valid = false;
+      for (int u = 0; u < U; u++) {
+        int64_t first, num;
+        kcnn::time_valid_rows(plan, rows, l, u, &first, &num);
+        valid = valid || (s >= first && s < first + num);
+      }
+      if (!valid) crossing++;
+      // (a dilated level of a short utterance has valid rows no window reads)
+      expect(valid || !maps[(size_t)l].read[(size_t)s],
+             "a row that is read is one of its utterance's valid rows", l, (long)s);
+    }
+  printf("%s %s: %ld elements equal the window pass, %ld rows computed and read by nothing\n",
+         name, pad ? "padded" : "unpadded", compared, crossing);
+}
+
+std::string slurp(const char *path) {
+  std::ifstream f(path);
+  std::ostringstream s;
+  s << f.rdbuf();
+  return s.str();
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  if (argc != 3) {
+    printf("usage: %s nnet.config train_conv.config\n", argv[0]);
+    return 2;
+  }
+  check_chain("nnet.config", parse_config(slurp(argv[1])),
+              {{1, 21, 1}, {128, 18, 1}, {128, 18, 1}, {128, 16, 1}, {128, 16, 1}, {256, 14, 1},
+               {256, 14, 1}, {256, 12, 1}, {256, 6, 2}, {256, 6, 2}, {512, 4, 2}, {512, 4, 2},
+               {512, 2, 2}, {512, 2, 2}});
+  check_chain("train_conv.config", parse_config(slurp(argv[2])),
+              {{1, 21, 1}, {128, 18, 1}, {128, 9, 2}, {128, 9, 2}});
+  check_chain("shrunken", parse_config(shrunken(1)),
+              {{1, 11, 1}, {32, 8, 1}, {32, 8, 1}, {32, 6, 1}, {32, 3, 2}, {32, 3, 2}, {64, 2, 2},
+               {64, 2, 2}});
+  check_declines();
+  const std::string net_a = splice_line(5, 2, 2) + conv_line(5, 5, 1, 2, 4) +
+                            pool_line(4, 4, 2, 1) + relu_line(8) + "NormalizeComponent dim=8\n";
+  unsigned seed = 1;
+  for (const std::string &cfg : {shrunken(1), shrunken(4), net_a}) {
+    const std::vector<TimeComp> comps = parse_config(cfg);
+    const int context = comps[0].left + comps[0].right;
+    const char *name = cfg == net_a ? "net A" : "shrunken";
+    run_model(name, cfg, {1, 37, 5}, true, seed++);
+    run_model(name, cfg, {1 + context, 37 + context, 5 + context}, false, seed++);
+    run_model(name, cfg, {1}, true, seed++);
+    // unpadded, the lengths themselves are too short
+    TimeRows rows;
+    const std::vector<int32_t> len = {1, 37, 5};
+    const TimePlan plan = kcnn::make_time_plan(comps, false);
+    expect(!kcnn::plan_time_rows(plan, len.data(), 3, false, &rows).empty(),
+           "an unpadded utterance of one frame is refused");
+  }
+  {  // 2^31 rows are refused
+    const TimePlan plan = kcnn::make_time_plan(parse_config(shrunken(1)), false);
+    const std::vector<int32_t> len = {2000000000, 2000000000};
+    TimeRows rows;
+    expect(kcnn::plan_time_rows(plan, len.data(), 2, true, &rows) == "too many rows", "2^31 rows");
+    expect(kcnn::plan_time_rows(plan, nullptr, 0, true, &rows) == "no utterances", "no lengths");
+  }
+  if (failures) {
+    printf("REFUSED: %d of %ld checks failed\n", failures, checks);
+    return 1;
+  }
+  printf("all time plan checks passed (%ld)\n", checks);
+  return 0;
+}
