@@ -5,8 +5,8 @@
 // prints each return code, workspace size and kernel launch (kernel handle
 // offset, grid, block, dynamic LDS bytes).  No kernel runs: hipLaunchKernel,
 // the call-configuration pair and the few device calls the host code makes
-// are defined here and take precedence over the runtime's.  The KCNN_*_X6
-// environment variables select the kernel families.  Arguments after the
+// are defined in launch_log.h and take precedence over the runtime's.  The
+// KCNN_*_X6 environment variables select the kernel families.  Arguments after the
 // library replace the built-in sweep by a list of geometries, each
 // "H,W,C,kh,kw,G,pad_h,pad_w[,rows]" (9 rows when left out); "-" reads them
 // from standard input, one per line (tests/test_conv_routes.py pins the
@@ -18,74 +18,12 @@
 //   ./conv_launch_log kaldi-cnn_amd/libkcnn.so > new.raw
 //   ./conv_launch_log kaldi-cnn_amd/libkcnn.so 20,13,8,3,1,32,0,0 40,61,1,8,3,256,0,0,5
 //   python scripts/conv_launch_names.py kaldi-cnn_amd/libkcnn.so new.raw > new.txt
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
 #include "cnsl-hip-kernels.h"
-
-static void *g_lib = nullptr;
-
-static void log_launch(const void *f, dim3 g, dim3 b, size_t shmem) {
-  Dl_info di;
-  uintptr_t off = (uintptr_t)f;
-  if (dladdr(f, &di) && di.dli_fbase) off -= (uintptr_t)di.dli_fbase;
-  printf("  K %lx grid %u,%u,%u block %u,%u,%u lds %zu\n", (unsigned long)off, g.x, g.y, g.z,
-         b.x, b.y, b.z, shmem);
-}
-
-static dim3 c_grid, c_block;
-static size_t c_shmem;
-static hipStream_t c_stream;
-extern "C" {
-hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t s, hipStream_t st) {
-  c_grid = g; c_block = b; c_shmem = s; c_stream = st;
-  return hipSuccess;
-}
-hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *s, hipStream_t *st) {
-  *g = c_grid; *b = c_block; *s = c_shmem; *st = c_stream;
-  return hipSuccess;
-}
-hipError_t hipLaunchKernel(const void *f, dim3 g, dim3 b, void **, size_t shmem, hipStream_t) {
-  log_launch(f, g, b, shmem);
-  return hipSuccess;
-}
-hipError_t hipGetLastError(void) { return hipSuccess; }
-hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipMalloc(void **p, size_t n) {
-  static uintptr_t next = 0xb00000000ull;
-  *p = (void *)next;
-  next += (n + 4095) & ~(size_t)4095;
-  printf("  malloc %zu\n", n);
-  return hipSuccess;
-}
-hipError_t hipFree(void *) { return hipSuccess; }
-int rocblas_create_handle(void **h) { *h = (void *)0x1; return 0; }
-int rocblas_destroy_handle(void *) { return 0; }
-int rocblas_set_atomics_mode(void *, int) { return 0; }
-int rocblas_set_pointer_mode(void *, int) { return 0; }
-int rocblas_set_stream(void *, void *) { return 0; }
-hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) {
-  printf("  memset %d %zu\n", v, n);
-  return hipSuccess;
-}
-}
-
-template <class F>
-static F sym(const char *n) {
-  void *p = dlsym(g_lib, n);
-  if (!p) { fprintf(stderr, "missing %s\n", n); exit(2); }
-  return reinterpret_cast<F>(p);
-}
+#include "launch_log.h"  // hipLaunchKernel and friends, g_lib, sym
 
 static MatrixDim md(int r, int c, int s = -1) { return MatrixDim{r, c, s < 0 ? c : s}; }
 
@@ -111,8 +49,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "usage: %s libkcnn.so [H,W,C,kh,kw,G,pad_h,pad_w[,rows] ... | -]\n", argv[0]);
     return 2;
   }
-  g_lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
-  if (!g_lib) { fprintf(stderr, "%s\n", dlerror()); return 2; }
+  open_lib(argv[1]);
   auto conv2d = sym<decltype(&hipF_conv2d)>("hipF_conv2d");
   auto relu = sym<decltype(&hipF_conv2d_relu)>("hipF_conv2d_relu");
   auto maxpool = sym<decltype(&hipF_conv2d_maxpool)>("hipF_conv2d_maxpool");

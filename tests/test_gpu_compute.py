@@ -26,7 +26,9 @@ import numpy as np
 import pytest
 
 import oracle as O
+import nnet2_kernel_cases as T
 import nnet2_loss_ref as R
+from _pitched import assert_bits, edge_columns, place, stream, sync
 from _util import assert_bound, assert_same, dev, host, padded, rng, triple
 
 pytestmark = pytest.mark.gpu
@@ -463,6 +465,37 @@ def test_loglikes_special_rows(kc, cols):
     assert_within_one_ulp(got, expected_loglikes(p, priors), f"special {cols}")
     want = F32(np.log(np.float64(F32(1e-20))) - np.log(np.float64(priors[7])))
     assert abs(float(got[3, 7]) - float(want)) <= abs(float(np.spacing(want)))
+
+
+@pytest.mark.parametrize("case", T.select("kn_softmax_loglikes"), ids=T.name_of)
+def test_softmax_loglikes_layouts(kc, case):
+    """kn_softmax_loglikes directly, on pitched operands with sentinels at the
+    layouts of tests/nnet2_kernel_cases.py (every access width at every count of
+    values a lane holds; tests/test_nnet2_routes.py pins the kernel).  The
+    expected P: kn_softmax_prop into an output laid out as `out`
+    (nnet-kernels.h); with more than one row, a -inf logit in row 0's edge
+    columns (in an only row it would hide a dropped last column)."""
+    import torch
+    KN = T.bind(kc)
+    rows, cols = case["rows"], case["cols"]
+    r = rng(820 + cols + rows)
+    logits = (r.standard_normal((rows, cols)) * 3).astype(F32)
+    if rows > 1:
+        logits[0, edge_columns(cols)] = -np.inf
+    priors = (r.random(cols) + 0.01).astype(F32)
+    offset = torch.from_numpy(np.log(priors.astype(np.float64))).cuda()
+    X, Pm = place(kc, case["ops"][0], logits), place(kc, case["ops"][1])
+    assert KN.kn_softmax_prop(X.ptr, X.dim, Pm.ptr, Pm.dim, stream()) == 0
+    sync()
+    p = Pm.get()
+    assert rows == 1 or (p[0, edge_columns(cols)] == F32(1e-20)).all()
+    for off, pri in ((offset, priors), (None, None)):
+        Y = place(kc, case["ops"][1])
+        assert KN.kn_softmax_loglikes(X.ptr, X.dim, Y.ptr, Y.dim,
+                                      off.data_ptr() if off is not None else None, stream()) == 0
+        sync()
+        assert_within_one_ulp(Y.get(), expected_loglikes(p, pri), case["name"])
+    assert_bits(X.get(), logits, "the logits")
 
 
 def test_loglikes_of_a_network_without_softmax(kc):

@@ -16,6 +16,12 @@ Bars: weight and accuracy are sums of multiples of 1/8 and must be EQUAL; the
 objective within 1e-6 relative (the bar of test_gpu_nnet2_loss.py); the two
 paths take log of the same bits and differ in fp64 summation order alone:
 1e-12 * sum |w log p|.
+
+test_objf_accuracy_layouts calls both launchers directly on pitched operands
+with sentinels at the layouts of tests/nnet2_kernel_cases.py: every access
+width at every count of values a lane holds, either side of each step, with
+best columns and labels in a row's last column and element-wise tail
+(tests/test_nnet2_routes.py pins the kernel of each case).
 """
 import functools
 import math
@@ -24,6 +30,9 @@ import os
 import numpy as np
 import pytest
 
+import nnet2_kernel_cases as T
+from _pitched import GUARD, assert_bits, edge_columns, stream, sync
+from _pitched import place as place_op
 from _util import dev, host, padded, rng, with_ties
 
 pytestmark = pytest.mark.gpu
@@ -189,6 +198,61 @@ def test_tied_maxima_take_the_lowest_column(kc, shape, layout):
         assert split[0] >= 60
     # the first maximal column scores, the last does not
     assert want[2] == rows and want[1] == rows + 0.5 * split[0]
+
+
+@pytest.fixture(scope="module")
+def KN(kc):
+    return T.bind(kc)
+
+
+@pytest.mark.parametrize("case", T.select("kn_objf_accuracy") + T.select("kn_softmax_objf_accuracy"),
+                         ids=T.name_of)
+def test_objf_accuracy_layouts(kc, KN, case):
+    """The stored path on P, the fused path on the logits, in the case's layout.
+    The expected P: kn_softmax_prop of the logits in that layout into a 16-byte
+    aligned output (nnet-kernels.h).  Every other row is labelled with its best
+    column (soft_labels), and that is one of the edge columns in turn, the last
+    column first."""
+    import torch
+    rows, cols = case["rows"], case["cols"]
+    fused = case["launcher"] == "kn_softmax_objf_accuracy"
+    r = rng(rows * 10007 + cols + fused)
+    logits = (r.standard_normal((rows, cols)) * 3).astype(F32)
+    edges = edge_columns(cols)[::-1]
+    for i in range(0, rows, 2):
+        logits[i, edges[(i // 2) % len(edges)]] = F32(20.0)
+    X = place_op(kc, case["ops"][0], logits)
+    Pm = place_op(kc, (rows, cols) + T.layout(cols, "v4"))
+    assert KN.kn_softmax_prop(X.ptr, X.dim, Pm.ptr, Pm.dim, stream()) == 0
+    sync()
+    p = Pm.get()
+    assert best_columns(p)[0] == edges[0] == cols - 1
+    labels = soft_labels(r, p)
+    assert all((i, edges[(i // 2) % len(edges)]) in {lab[:2] for lab in labels}
+               for i in range(0, rows, 2))
+    want, scale = expected_totals(p, labels)
+    assert 0 < want[2] <= want[1]
+    count = np.bincount([lab[0] for lab in labels], minlength=rows)
+    row_start = torch.from_numpy(np.concatenate([[0], np.cumsum(count)]).astype(np.int32)).cuda()
+    lab_col = torch.from_numpy(np.array([lab[1] for lab in labels], np.int32)).cuda()
+    lab_w = torch.from_numpy(np.array([lab[2] for lab in labels], F32)).cuda()
+    Q = X if fused else place_op(kc, case["ops"][0], p)
+    n = KN.kn_prob_ws(KN.kn_prob_blocks(Q.dim)) // 8
+    got = []
+    for _ in range(2):
+        ws = torch.full((n + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+        tot = torch.full((3 + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+        tot[:3] = 0
+        launcher = KN.kn_softmax_objf_accuracy if fused else KN.kn_objf_accuracy
+        assert launcher(Q.ptr, Q.dim, row_start.data_ptr(), lab_col.data_ptr(), lab_w.data_ptr(),
+                        tot.data_ptr(), ws.data_ptr(), stream()) == 0
+        sync()
+        t = tot.cpu().numpy()
+        assert np.isnan(t[3:]).all() and np.isnan(ws[n:].cpu().numpy()).all()
+        got.append(tuple(float(v) for v in t[:3]))
+    assert all(same(u, v) for u, v in zip(*got)), got
+    check(got[0], want, scale, case["name"])
+    assert_bits(Q.get(), logits if fused else p, "the input")
 
 
 def special_matrix(kind, shape):

@@ -17,12 +17,11 @@ import math
 import numpy as np
 import pytest
 
+from _pitched import GUARD, PAD, Mat, assert_bits, bits, stream, sync
 from _util import rng
 
 pytestmark = pytest.mark.gpu
 
-PAD = np.float32(-12345.5)
-GUARD = 64
 P = ctypes.c_void_p
 I = ctypes.c_int
 F = ctypes.c_float
@@ -45,53 +44,6 @@ def L(kc):
                  "kl_sum_partials", "kl_col_sum", "kl_dot"):
         getattr(lib, name).restype = I
     return lib
-
-
-def stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-class Mat:
-    """A pitched device matrix holding x; padding and guard hold PAD."""
-
-    def __init__(self, kc, x, extra=3):
-        import torch
-        x = np.asarray(x, np.float32)
-        if x.ndim == 1:
-            x = x[None, :]
-        self.rows, self.cols = x.shape
-        self.stride = self.cols + extra
-        self.h = np.full(self.rows * self.stride + GUARD, PAD, np.float32)
-        self.body()[:, :self.cols] = x
-        self.t = torch.from_numpy(self.h.copy()).cuda()
-        self.ptr = self.t.data_ptr()
-        self.dim = kc.MatrixDim(self.rows, self.cols, self.stride)
-
-    def body(self, h=None):
-        h = self.h if h is None else h
-        return h[:self.rows * self.stride].reshape(self.rows, self.stride)
-
-    def get(self):
-        """The matrix now; the padding and the guard must be as they were."""
-        g = self.t.cpu().numpy()
-        assert (self.body(g)[:, self.cols:] == PAD).all(), "padding was written"
-        assert (g[self.rows * self.stride:] == PAD).all(), "guard was written"
-        return self.body(g)[:, :self.cols].copy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(got, want, what):
-    bad = np.argwhere(bits(got) != bits(np.asarray(want, np.float32)))
-    assert bad.size == 0, f"{what}: {len(bad)} elements differ, first at {bad[:3].tolist()}"
 
 
 def ints(r, shape, lim=8):

@@ -5,13 +5,22 @@ Bars: the project's 1e-5 bound against fp64 for everything that rounds
 (softmax outputs: rtol 1e-5 after the floor; derivatives: 1e-5 * the sum of
 |terms|; parameters: 1e-5 normwise); bit-exact where the fp32 operation
 sequence is fixed (CompObjfAndDeriv's derivative, Dropout both ways, model
-files)."""
+files).
+
+The *_layouts tests call the kn_* launchers directly on pitched operands with
+sentinels, at the shapes and layouts of tests/nnet2_kernel_cases.py: every
+access width (4, 2, 1 columns a lane) at every count of values a lane holds,
+either side of each step (256 | 257, 1024 | 1025, 4096 | 4097), 1 and 70 rows;
+tests/test_nnet2_routes.py pins the kernel each case launches.  Same
+references, same bars."""
 import os
 
 import numpy as np
 import pytest
 
+import nnet2_kernel_cases as T
 import nnet2_loss_ref as R
+from _pitched import GUARD, PAD, assert_bits, edge_columns, place, stream, sync
 from _util import assert_same, dev, host, padded, rng
 
 pytestmark = pytest.mark.gpu
@@ -418,3 +427,166 @@ def test_small_end_to_end(kc):
     print(f"objf {objf!r} vs fp64 {objf64!r}")
     assert abs(objf - objf64) <= 1e-5 * abs(objf64)
     assert w == 2 * sum(float(F32(wt)) for _, _, wt in labels)
+
+
+# ---- every (access width, values a lane) instantiation, through the launchers -------------
+@pytest.fixture(scope="module")
+def KN(kc):
+    return T.bind(kc)
+
+
+def edge_input(rows, cols, seed=0):
+    """softmax_input with a -inf also in row 0's last column, in the last column
+    of its last whole vector and in the first column of the element-wise tail."""
+    x = softmax_input(rows, cols, seed)
+    x[0, edge_columns(cols)] = -np.inf
+    return x
+
+
+def stats_buffers(KN, dim, cols):
+    """value_sum (zero, then a NaN guard) and the workspace (then a PAD guard)."""
+    import torch
+    vs = torch.full((cols + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    vs[:cols] = 0
+    n = KN.kn_softmax_stats_ws(dim) // 4
+    ws = torch.full((n + GUARD,), float(PAD), dtype=torch.float32, device="cuda")
+    return vs, ws, n
+
+
+def check_stats_buffers(vs, ws, n, cols, want, what):
+    got = vs.cpu().numpy()
+    assert np.isnan(got[cols:]).all(), "words after value_sum were written"
+    assert (ws[n:].cpu().numpy() == PAD).all(), "workspace guard was written"
+    np.testing.assert_allclose(got[:cols], want, rtol=2e-6, atol=1e-5, err_msg=what)
+
+
+@pytest.mark.parametrize("case", T.select("kn_softmax_prop"), ids=T.name_of)
+def test_softmax_propagate_layouts(kc, KN, case):
+    rows, cols = case["rows"], case["cols"]
+    x = edge_input(rows, cols, seed=3)
+    X, Y = place(kc, case["ops"][0], x), place(kc, case["ops"][1])
+    assert KN.kn_softmax_prop(X.ptr, X.dim, Y.ptr, Y.dim, stream()) == 0
+    sync()
+    y = Y.get()
+    check_softmax(y, x)
+    assert (y[0, edge_columns(cols)] == FLOOR).all()
+    assert_bits(X.get(), x, "the input")
+    if rows == 1:
+        # the only row's edge columns hold -inf: a dropped last column would not
+        # show, so the same row with numbers there as well
+        x = softmax_input(rows, cols, seed=3)
+        X, Y = place(kc, case["ops"][0], x), place(kc, case["ops"][1])
+        assert KN.kn_softmax_prop(X.ptr, X.dim, Y.ptr, Y.dim, stream()) == 0
+        sync()
+        check_softmax(Y.get(), x)
+
+
+@pytest.mark.parametrize("case", T.select("kn_softmax_backprop"), ids=T.name_of)
+def test_softmax_backprop_layouts(kc, KN, case):
+    rows, cols = case["rows"], case["cols"]
+    r = rng(cols + rows)
+    p = R.softmax_prop64(r.standard_normal((rows, cols)) * 2).astype(F32)
+    e = r.standard_normal((rows, cols)).astype(F32)
+    Pm, Em, Dm = place(kc, case["ops"][0], p), place(kc, case["ops"][1], e), place(kc, case["ops"][2])
+    vs, ws, n = stats_buffers(KN, Pm.dim, cols)
+    t, s = R.softmax_backprop64(p, e)
+    calls = 2 if case["stats"] else 1
+    for _ in range(calls):
+        assert KN.kn_softmax_backprop(Pm.ptr, Pm.dim, Em.ptr, Em.dim, Dm.ptr, Dm.dim,
+                                      vs.data_ptr() if case["stats"] else None,
+                                      ws.data_ptr() if case["stats"] else None, stream()) == 0
+        sync()
+        d = Dm.get().astype(np.float64)
+        err = np.abs(d - t) / np.maximum(s, 1e-300)
+        print(f"softmax backprop {case['name']}: worst err / sum|P E| = {err.max():.3e}")
+        assert (np.abs(d - t) <= 1e-5 * s).all(), err.max()
+    want = calls * p.astype(np.float64).sum(axis=0) if case["stats"] else np.zeros(cols)
+    check_stats_buffers(vs, ws, n, cols, want, case["name"])
+    assert_bits(Pm.get(), p, "out_value")
+    assert_bits(Em.get(), e, "out_deriv")
+
+
+def edge_labels(r, rows, cols, skip=()):
+    """soft_labels, and in row 0 a label in each edge column as well."""
+    labels = [l for l in soft_labels(r, rows, cols, skip) if l[0] != 0]
+    return [(0, c, (k + 1) / 8) for k, c in enumerate(edge_columns(cols))] + labels
+
+
+def label_arrays(labels, rows):
+    import torch
+    count = np.bincount([l[0] for l in labels], minlength=rows)
+    row_start = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    col = np.array([l[1] for l in labels], np.int32)
+    w = np.array([l[2] for l in labels], F32)
+    return [torch.from_numpy(a).cuda() for a in (row_start, col, w)]
+
+
+@pytest.mark.parametrize("case", T.select("kn_softmax_xent_backprop"), ids=T.name_of)
+def test_softmax_xent_layouts(kc, KN, case):
+    import torch
+    rows, cols = case["rows"], case["cols"]
+    r = rng(2 * cols + rows)
+    p = R.softmax_prop64(r.standard_normal((rows, cols)) * 2).astype(F32)
+    labels = edge_labels(r, rows, cols, skip=(2,))
+    row_start, lab_col, lab_w = label_arrays(labels, rows)
+    Pm, Dm = place(kc, case["ops"][0], p), place(kc, case["ops"][1])
+    vs, ws, n = stats_buffers(KN, Pm.dim, cols)
+    nb = KN.kn_softmax_xent_blocks(Pm.dim)
+    objf_n = KN.kn_objf_ws(nb) // 8
+    assert objf_n == 2 * nb
+    objf_ws = torch.full((objf_n + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    tot = torch.full((2 + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    tot[:2] = 0
+    assert KN.kn_softmax_xent_backprop(Pm.ptr, Pm.dim, Dm.ptr, Dm.dim, row_start.data_ptr(),
+                                       lab_col.data_ptr(), lab_w.data_ptr(),
+                                       vs.data_ptr() if case["stats"] else None,
+                                       ws.data_ptr() if case["stats"] else None, tot.data_ptr(),
+                                       objf_ws.data_ptr(), stream()) == 0
+    sync()
+    t, s = R.xent_deriv64(p, labels)
+    err = np.abs(Dm.get().astype(np.float64) - t)
+    print(f"xent {case['name']}: worst |D - D64| / S_r = {(err / np.maximum(s, 1e-300)).max():.3e}")
+    assert (err <= 1e-5 * s).all()
+    objf64 = sum(float(F32(w)) * np.log(np.float64(p[i, c])) for i, c, w in labels)
+    wsum = sum(float(F32(w)) for _, _, w in labels)
+    got = tot.cpu().numpy()
+    assert np.isnan(got[2:]).all() and np.isnan(objf_ws[objf_n:].cpu().numpy()).all()
+    assert abs(got[0] - objf64) <= 1e-6 * abs(objf64)
+    assert got[1] == wsum
+    want = p.astype(np.float64).sum(axis=0) if case["stats"] else np.zeros(cols)
+    check_stats_buffers(vs, ws, n, cols, want, case["name"])
+    assert_bits(Pm.get(), p, "out_value")
+
+
+@pytest.mark.parametrize("case", T.select("kn_comp_objf_and_deriv"), ids=T.name_of)
+def test_comp_objf_and_deriv_layouts(kc, KN, case):
+    import torch
+    rows, cols, per_row = case["rows"], case["cols"], case["per_row"]
+    r = rng(cols + per_row)
+    p = R.softmax_prop64(r.standard_normal((rows, cols)) * 3).astype(F32)
+    start = r.standard_normal((rows, cols)).astype(F32)
+    labels = []
+    for i in range(rows):
+        edge = edge_columns(cols)[-min(per_row, 2):]
+        others = [int(c) for c in r.choice(cols - 8, size=per_row - len(edge), replace=False)]
+        labels += [(i, c, float(r.integers(1, 9)) / 8) for c in sorted(others + edge)]
+    assert len(labels) == case["args"][0]
+    el = [torch.from_numpy(np.array([l[k] for l in labels], t)).cuda()
+          for k, t in ((0, np.int32), (1, np.int32), (2, F32))]
+    Pm, Dm = place(kc, case["ops"][0], p), place(kc, case["ops"][1], start)
+    nb = KN.kn_comp_objf_blocks(len(labels))
+    objf_n = KN.kn_objf_ws(nb) // 8
+    objf_ws = torch.full((objf_n + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    tot = torch.full((2 + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
+    tot[:2] = 0
+    assert KN.kn_comp_objf_and_deriv(el[0].data_ptr(), el[1].data_ptr(), el[2].data_ptr(),
+                                     len(labels), Pm.ptr, Pm.dim, Dm.ptr, Dm.dim, tot.data_ptr(),
+                                     objf_ws.data_ptr(), stream()) == 0
+    sync()
+    exp_d, exp_objf, exp_w = R.comp_objf_and_deriv32(p, labels, start)
+    assert_same(Dm.get(), exp_d, "deriv += w / p")
+    got = tot.cpu().numpy()
+    assert np.isnan(got[2:]).all() and np.isnan(objf_ws[objf_n:].cpu().numpy()).all()
+    assert abs(got[0] - exp_objf) <= 1e-6 * abs(exp_objf)
+    assert got[1] == exp_w
+    assert_bits(Pm.get(), p, "probs")

@@ -10,14 +10,19 @@ of another batch, in_deriv aliasing out_deriv, model files).
 The widths cover the three kernel forms and their edges: a row in one wave's
 registers (up to 4096 columns, 4 / 16 / 32 / 64 values a lane), a row in a
 block's registers (4097 to 16384, 32 / 64 values a thread), the re-read form
-beyond."""
+beyond.  The *_layouts tests call the launchers directly on pitched operands
+with sentinels, at the layouts of tests/nnet2_kernel_cases.py: every access
+width (4, 2, 1 columns a lane) at every count of values a thread holds, either
+side of each step (tests/test_nnet2_routes.py pins the kernel of each case)."""
 import functools
 import os
 
 import numpy as np
 import pytest
 
+import nnet2_kernel_cases as T
 import normalize_ref as R
+from _pitched import assert_bits, place, stream, sync
 from _util import assert_same, host, padded, rng
 from _util import dev as _dev
 
@@ -115,6 +120,33 @@ def test_normalize_at_register_steps(kc, cols):
     c = new(kc, cols)
     check_prop(host(c.Propagate(dev(x))), x, t, (70, cols))
     check_backprop(host(c.Backprop(dev(x), None, dev(dy))), d, terms, (70, cols))
+
+
+@pytest.fixture(scope="module")
+def KN(kc):
+    return T.bind(kc)
+
+
+@pytest.mark.parametrize("kcase", T.select("kn_normalize_prop"), ids=T.name_of)
+def test_normalize_propagate_layouts(kc, KN, kcase):
+    x, _, t, _, _ = case(kcase["rows"], kcase["cols"], seed=6)
+    check_inputs_clear_of_floor_and_overflow(x)
+    X, Y = place(kc, kcase["ops"][0], x), place(kc, kcase["ops"][1])
+    assert KN.kn_normalize_prop(X.ptr, X.dim, Y.ptr, Y.dim, stream()) == 0
+    sync()
+    check_prop(Y.get(), x, t, kcase["name"])
+    assert_bits(X.get(), x, "the input")
+
+
+@pytest.mark.parametrize("kcase", T.select("kn_normalize_backprop"), ids=T.name_of)
+def test_normalize_backprop_layouts(kc, KN, kcase):
+    x, dy, _, t, terms = case(kcase["rows"], kcase["cols"], seed=6)
+    X, E, D = place(kc, kcase["ops"][0], x), place(kc, kcase["ops"][1], dy), place(kc, kcase["ops"][2])
+    assert KN.kn_normalize_backprop(X.ptr, X.dim, E.ptr, E.dim, D.ptr, D.dim, stream()) == 0
+    sync()
+    check_backprop(D.get(), t, terms, kcase["name"])
+    assert_bits(X.get(), x, "in_value")
+    assert_bits(E.get(), dy, "out_deriv")
 
 
 @pytest.mark.parametrize("cols", [1, 64, 4096, 8192])
