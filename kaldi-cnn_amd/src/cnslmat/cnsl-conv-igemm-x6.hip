@@ -1374,6 +1374,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_efix_kernel(
 constexpr int kLdsMax = 160 * 1024;
 constexpr int img_bytes(bool f16) { return 2 * (f16 ? 2 : 3) * 384 * ROWB; }  // double-buffered planes
 
+// Raises a kernel's dynamic-LDS limit; the launchers keep the answer in a
+// static, one call per form.  A refusal is cleared here: left in
+// hipGetLastError it would be returned by the launcher as if its launch had
+// failed, after the kernels ran.  A launch that then asks for more LDS than the
+// kernel may have fails with its own error.
+inline bool raise_dyn_lds(const void *kernel, int bytes) {
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) ==
+      hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  return false;
+}
+
 // LDS of the tap table for Kdim (0: it does not fit beside the images)
 int tab_bytes(const ConvGeom &g, bool padded) {
   const int KT = (g.Kdim + BK - 1) / BK * BK;
@@ -1386,9 +1399,18 @@ void launch_t(const ConvGeom &g, unsigned blocks, const float *X, int xs, const 
               int ks, const float *bias, float *out, int os, int relu, hipStream_t st,
               PoolOut po, F16Aux fx) {
   const int lds = img_bytes(F16) + (TAB ? tab_bytes(g, PADDED) : 0) + (F16 ? kAuxBytes : 0);
-  static bool attr = hipFuncSetAttribute(
-      reinterpret_cast<const void *>(&conv_igemm_x6_kernel<BG, PADDED, TAB, POOL, F16>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) == hipSuccess;
+  // The most this form asks for: its images, the largest table tab_bytes
+  // grants and the f16x3 scales (117,760 B for the f16x3 forms, kLdsMax for
+  // the bf16x6 ones).  Not kLdsMax for every form: the f16x3 forms also hold
+  // static LDS (256 B), so the runtime refused kLdsMax for them and the first
+  // call of each f16x3 form in a process ran its kernels and then returned
+  // that refusal (the unfused convolution ran again on the fp32 MFMAs, the
+  // pooled entry answered "declined" after writing its outputs).
+  constexpr int kDynMax =
+      img_bytes(F16) + (kLdsMax - img_bytes(false)) + (F16 ? kAuxBytes : 0);
+  static_assert(kDynMax <= kLdsMax, "the form's LDS request");
+  static const bool attr = raise_dyn_lds(
+      reinterpret_cast<const void *>(&conv_igemm_x6_kernel<BG, PADDED, TAB, POOL, F16>), kDynMax);
   (void)attr;
   hipLaunchKernelGGL((conv_igemm_x6_kernel<BG, PADDED, TAB, POOL, F16>), dim3(blocks),
                      dim3(NT), lds, st, g, X, xs, K, ks, bias, out, os, relu, po, fx);
@@ -1653,9 +1675,8 @@ int kcnn_conv_wgrad_x6(const ConvGeom &g, const float *X, int xs, const float *d
     }
 #define KCNN_WX6W(P_, F_, L_)                                                               \
   do {                                                                                      \
-    static bool attr = hipFuncSetAttribute(                                                 \
-        reinterpret_cast<const void *>(&conv_wgrad_x6w_kernel<P_, F_>),                     \
-        hipFuncAttributeMaxDynamicSharedMemorySize, L_) == hipSuccess;                       \
+    static const bool attr = raise_dyn_lds(                                                 \
+        reinterpret_cast<const void *>(&conv_wgrad_x6w_kernel<P_, F_>), L_);                \
     (void)attr;                                                                             \
     hipLaunchKernelGGL((conv_wgrad_x6w_kernel<P_, F_>), grid, dim3(NT), L_, st, g, X, xs,  \
                        dY, dys, ws, fps, ktiles, nblocks, wf);                              \
@@ -1675,9 +1696,8 @@ int kcnn_conv_wgrad_x6(const ConvGeom &g, const float *X, int xs, const float *d
   constexpr int lds = 2 * 3 * 384 * ROWB;
 #define KCNN_WX6(P_)                                                                      \
   do {                                                                                    \
-    static bool attr = hipFuncSetAttribute(                                               \
-        reinterpret_cast<const void *>(&conv_wgrad_x6_kernel<P_>),                        \
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;                    \
+    static const bool attr = raise_dyn_lds(                                               \
+        reinterpret_cast<const void *>(&conv_wgrad_x6_kernel<P_>), lds);                  \
     (void)attr;                                                                           \
     hipLaunchKernelGGL((conv_wgrad_x6_kernel<P_>), grid, dim3(NT), lds, st, g, X, xs,     \
                        dY, dys, ws, fps, ktiles, nblocks);                                \

@@ -10,7 +10,13 @@
 // library replace the built-in sweep by a list of geometries, each
 // "H,W,C,kh,kw,G,pad_h,pad_w[,rows]" (9 rows when left out); "-" reads them
 // from standard input, one per line (tests/test_conv_routes.py pins the
-// routes of single shapes this way).  Two builds dispatch
+// routes of single shapes this way).  An argument or line that starts with a
+// letter is a case of one pooled entry point instead (scripts/README.md has
+// the syntax; tests/test_conv_pool_routes.py pins tests/conv_pool_cases.py's
+// table this way):
+//   ENTRY H,W,C,kh,kw,G,pad_h,pad_w,rows PHxPWxPC OUTS [OPERAND=stride:lead ...]
+// and prints "case <k> <entry>", its launches and " rc <return code>" (the
+// statistics entry " rc <return code> produced <0 | 1>").  Two builds dispatch
 // alike when their logs are equal after scripts/conv_launch_names.py has
 // replaced the handle offsets by symbol names (profiles/conv_dispatch.md):
 //   g++ -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
@@ -20,6 +26,7 @@
 //   python scripts/conv_launch_names.py kaldi-cnn_amd/libkcnn.so new.raw > new.txt
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "cnsl-hip-kernels.h"
@@ -43,13 +50,168 @@ static bool parse_job(const char *txt, Job &j) {
   return n >= 8;
 }
 
+// ---- cases of the pooled entry points -------------------------------------------------------
+// PoolStatsOut of src/cnslmat/pool-stats.h (the logger builds against include/ alone)
+struct StatsOut {
+  uint32_t *rowmax, *colmax, *partials;
+  size_t partial_words;
+  int produced;
+};
+typedef int (*maxpool_stats_fn)(const float *, MatrixDim, int, int, int, int, int, const float *,
+                                MatrixDim, int, int, int, const float *, float *, MatrixDim,
+                                float *, MatrixDim, unsigned char *, int, int, kcnn_stream_t,
+                                StatsOut *);
+typedef size_t (*stats_words_fn)(int, int, int, int, int, int, int, int);
+
+// an operand's row stride (-1: its columns) and lead, in its own elements
+struct Lay {
+  int stride = -1, lead = 0;
+};
+
+static const char *const kOperands[] = {"x", "w", "y", "p", "m", "dx", "gw"};
+enum { OP_X, OP_W, OP_Y, OP_P, OP_M, OP_DX, OP_GW, OP_N };
+
+static int g_case = 0;
+
+// One case line; false (with a message) when it does not parse.
+static bool run_case(const char *txt) {
+  std::vector<std::string> tok;
+  for (const char *p = txt; *p;) {
+    p += strspn(p, " \t\r\n");
+    const size_t n = strcspn(p, " \t\r\n");
+    if (n) tok.emplace_back(p, n);
+    p += n;
+  }
+  int s[9], ph, pw, pc;
+  if (tok.size() < 4 ||
+      sscanf(tok[1].c_str(), "%d,%d,%d,%d,%d,%d,%d,%d,%d", s, s + 1, s + 2, s + 3, s + 4, s + 5,
+             s + 6, s + 7, s + 8) != 9 ||
+      sscanf(tok[2].c_str(), "%dx%dx%d", &ph, &pw, &pc) != 3) {
+    fprintf(stderr, "bad case: %s\n", txt);
+    return false;
+  }
+  const std::string &entry = tok[0], &outs = tok[3];
+  const bool fwd = entry == "maxpool" || entry == "maxpool_stats" || entry == "maxpool_stats0" ||
+                   entry == "maxpool3d";
+  const bool bwd = entry == "bpool" || entry == "bpool3d" || entry == "backward" ||
+                   entry == "dgrad";
+  if (!(fwd || bwd) || !(fwd ? outs == "Y" || outs == "noY"
+                             : outs == "both" || outs == "nodx" || outs == "nogw")) {
+    fprintf(stderr, "bad case: %s\n", txt);
+    return false;
+  }
+  Lay lay[OP_N];
+  for (size_t t = 4; t < tok.size(); t++) {
+    char name[8];
+    int st, ld, k = 0;
+    if (sscanf(tok[t].c_str(), "%7[a-z]=%d:%d", name, &st, &ld) != 3) k = OP_N;
+    while (k < OP_N && strcmp(name, kOperands[k])) k++;
+    if (k == OP_N) {
+      fprintf(stderr, "bad operand %s: %s\n", tok[t].c_str(), txt);
+      return false;
+    }
+    lay[k].stride = st;
+    lay[k].lead = ld;
+  }
+  const int H = s[0], Wd = s[1], C = s[2], kh = s[3], kw = s[4], G = s[5], pad_h = s[6],
+            pad_w = s[7], R = s[8];
+  const int oh = H + 2 * pad_h - kh + 1, ow = Wd + 2 * pad_w - kw + 1, P = oh * ow;
+  const int Kd = kh * kw * C, win = ph * pw * pc;
+  const int pcols = win > 0 ? (int)((int64_t)P * G / win) : 0;
+  auto dim = [&](int k, int rows, int cols) {
+    return MatrixDim{rows, cols, lay[k].stride < 0 ? cols : lay[k].stride};
+  };
+  // each operand in its own 4 GiB of fake address space, 4096-byte aligned
+  auto at = [&](int k, size_t elem) {
+    return (char *)(0x100000000ull * (uintptr_t)(k + 1)) + (int64_t)lay[k].lead * (int64_t)elem;
+  };
+  float *X = (float *)at(OP_X, 4), *W = (float *)at(OP_W, 4), *Y = (float *)at(OP_Y, 4);
+  float *PL = (float *)at(OP_P, 4), *DX = (float *)at(OP_DX, 4), *GW = (float *)at(OP_GW, 4);
+  const bool m16 = entry == "maxpool3d" || entry == "bpool3d";
+  unsigned char *MK = (unsigned char *)at(OP_M, m16 ? 2 : 1);
+  float *B = (float *)0x900000000ull, *GB = (float *)0x980000000ull;
+  void *WS = (void *)0xa00000000ull;
+  const size_t big = (size_t)1 << 40;
+  const MatrixDim xd = dim(OP_X, R, H * Wd * C), kd = dim(OP_W, Kd, G), yd = dim(OP_Y, R, P * G);
+  const MatrixDim pd = dim(OP_P, R, pcols), dxd = dim(OP_DX, R, H * Wd * C);
+  const MatrixDim gwd = dim(OP_GW, Kd, G);
+  const int ms = lay[OP_M].stride < 0 ? pcols : lay[OP_M].stride;
+  printf("case %d %s\n", g_case++, entry.c_str());
+  int rc;
+  if (fwd) {
+    float *Yp = outs == "Y" ? Y : nullptr;
+    if (entry == "maxpool") {
+      auto f = sym<decltype(&hipF_conv2d_maxpool)>("hipF_conv2d_maxpool");
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, W, kd, kh, kw, G, B, Yp, yd, PL, pd, MK, ms, pc,
+             nullptr);
+    } else if (entry == "maxpool3d") {
+      auto f = sym<decltype(&hipF_conv2d_maxpool3d)>("hipF_conv2d_maxpool3d");
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, W, kd, kh, kw, G, B, Yp, yd, PL, pd,
+             (unsigned short *)MK, ms, ph, pw, pc, nullptr);
+    } else {
+      auto f = sym<maxpool_stats_fn>("kcnn_conv2d_maxpool_stats");
+      auto words = sym<stats_words_fn>("kcnn_conv2d_maxpool_stats_words");
+      StatsOut st{(uint32_t *)0xb00000000ull, (uint32_t *)0xb80000000ull, nullptr, 0, 0};
+      if (entry == "maxpool_stats") {
+        st.partials = (uint32_t *)0xc00000000ull;
+        st.partial_words = words(R, H, Wd, C, kh, kw, G, pc);
+      }
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, W, kd, kh, kw, G, B, Yp, yd, PL, pd, MK, ms, pc,
+             nullptr, &st);
+      printf(" rc %d produced %d\n", rc, st.produced);
+      return true;
+    }
+  } else {
+    float *DXp = outs == "nodx" ? nullptr : DX, *GWp = outs == "nogw" ? nullptr : GW;
+    float *GBp = outs == "nogw" ? nullptr : GB;
+    if (entry == "bpool") {
+      auto f = sym<decltype(&hipF_conv2d_backward_pooled)>("hipF_conv2d_backward_pooled");
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, MK, ms, PL, pd, pc, W, kd, kh, kw, G, DXp, dxd, GWp,
+             gwd, GBp, WS, big, nullptr);
+    } else if (entry == "bpool3d") {
+      auto f = sym<decltype(&hipF_conv2d_backward_pooled3d)>("hipF_conv2d_backward_pooled3d");
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, (const unsigned short *)MK, ms, PL, pd, ph, pw, pc, W,
+             kd, kh, kw, G, DXp, dxd, GWp, gwd, GBp, WS, big, nullptr);
+    } else if (entry == "backward") {  // the unpooled backward on the same operands (dY in Y's place)
+      auto f = sym<decltype(&hipF_conv2d_backward)>("hipF_conv2d_backward");
+      rc = f(X, xd, H, Wd, C, pad_h, pad_w, Y, yd, W, kd, kh, kw, G, DXp, dxd, GWp, gwd, GBp, WS,
+             big, nullptr);
+    } else {  // and the data gradient alone (OUTS nogw)
+      auto f = sym<decltype(&hipF_conv2d_dgrad)>("hipF_conv2d_dgrad");
+      rc = f(Y, yd, H, Wd, C, pad_h, pad_w, W, kd, kh, kw, G, DX, dxd, WS, big, nullptr);
+    }
+  }
+  printf(" rc %d\n", rc);
+  return true;
+}
+
+static bool is_case(const char *txt) {
+  const char c = txt[strspn(txt, " \t")];
+  return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z');
+}
+
 int main(int argc, char **argv) {
   setvbuf(stdout, nullptr, _IONBF, 0);
   if (argc < 2) {
-    fprintf(stderr, "usage: %s libkcnn.so [H,W,C,kh,kw,G,pad_h,pad_w[,rows] ... | -]\n", argv[0]);
+    fprintf(stderr, "usage: %s libkcnn.so [H,W,C,kh,kw,G,pad_h,pad_w[,rows] | 'CASE' ... | -]\n",
+            argv[0]);
     return 2;
   }
   open_lib(argv[1]);
+  // the arguments, or the lines of standard input: all cases or all shapes
+  std::vector<std::string> items;
+  if (argc == 3 && strcmp(argv[2], "-") == 0) {
+    char line[512];
+    while (fgets(line, sizeof line, stdin))
+      if (line[strspn(line, " \t\r\n")] != 0) items.emplace_back(line);
+  } else {
+    for (int a = 2; a < argc; a++) items.emplace_back(argv[a]);
+  }
+  if (!items.empty() && is_case(items[0].c_str())) {
+    for (auto &it : items)
+      if (!is_case(it.c_str()) || !run_case(it.c_str())) return 2;
+    return 0;
+  }
   auto conv2d = sym<decltype(&hipF_conv2d)>("hipF_conv2d");
   auto relu = sym<decltype(&hipF_conv2d_relu)>("hipF_conv2d_relu");
   auto maxpool = sym<decltype(&hipF_conv2d_maxpool)>("hipF_conv2d_maxpool");
@@ -103,18 +265,10 @@ int main(int argc, char **argv) {
       memcpy(j.s, s, sizeof j.s);
       jobs.push_back(j);
     }
-  } else if (argc == 3 && strcmp(argv[2], "-") == 0) {
-    char line[256];
-    while (fgets(line, sizeof line, stdin)) {
-      Job j;
-      if (line[strspn(line, " \t\r\n")] == 0) continue;
-      if (!parse_job(line, j)) return 2;
-      jobs.push_back(j);
-    }
   } else {
-    for (int a = 2; a < argc; a++) {
+    for (auto &it : items) {
       Job j;
-      if (!parse_job(argv[a], j)) return 2;
+      if (!parse_job(it.c_str(), j)) return 2;
       jobs.push_back(j);
     }
   }
