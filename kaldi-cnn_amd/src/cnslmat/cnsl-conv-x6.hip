@@ -9,7 +9,7 @@
 // = dX by Conv2D of the padded dY with the flipped kernel (:489-540) and the
 // update gradient of Update (:738-777: TpBlock(X) conv TpInsideBlock(dY),
 // ModPermuteRow, bias = row sum of dY).  Here both come out of one pass over
-// dY, as in conv_bwd_dma_kernel (cnsl-conv-frame.hip), whose fp32 MFMA
+// dY, as in conv_bwd_dma_kernel (cnsl-conv-frame-bwd.hip), whose fp32 MFMA
 // (v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD) holds the SIMD's vector issue
 // for all of its 64 cycles.  v_mfma_f32_32x32x16_bf16 does 8x the work in
 // half the cycles; six of them replace eight fp32 MFMAs of the same tile at

@@ -6,10 +6,12 @@
 // family's launcher (conv-geom.h): 0 launched, -1 declined with nothing
 // launched, > 0 a HIP error.  The limits a route depends on are predicates of
 // conv-geom.h or of the family's own file, each written once.  Host code
-// only; the kernels are in cnsl-conv-frame.hip (frame-resident),
-// cnsl-conv-x6.hip (bf16x6 fused backward), cnsl-conv-igemm-x6.hip (bf16x6 /
-// f16x3 implicit GEMM and weight gradient) and cnsl-conv-mfma.hip (fp32 MFMA,
-// direct).  profiles/conv_dispatch.md has the ladders as tables.
+// only; the kernels are in cnsl-conv-frame.hip (frame-resident forward),
+// cnsl-conv-frame-bwd.hip (frame-resident fp32 backward), cnsl-conv-x6.hip
+// (bf16x6 fused backward), cnsl-conv-igemm-x6.hip (bf16x6 / f16x3 implicit
+// GEMM and weight gradient), cnsl-conv-mfma.hip (fp32 MFMA, direct) and
+// cnsl-conv-reduce.hip (the weight gradients' split reduction).
+// profiles/conv_dispatch.md has the ladders as tables.
 #include <stdint.h>
 
 #include <algorithm>

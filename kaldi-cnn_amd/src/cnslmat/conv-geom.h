@@ -75,8 +75,11 @@ __device__ __forceinline__ int mfma32_row(int r, int lane) {
 
 }  // namespace kcnn
 
-// Frame-resident kernels (cnsl-conv-frame.hip).  Each returns -1 when the
-// shape is not eligible (caller falls back to the implicit-GEMM path).
+struct ConvUpdateEpi;  // conv-update.h
+
+// Frame-resident kernels.  Each returns -1 when the shape is not eligible
+// (caller falls back to the implicit-GEMM path).
+// The forward, alone or with the max pool behind it (cnsl-conv-frame.hip).
 int kcnn_conv_fwd_frame(const kcnn::ConvGeom &g, const float *X, int xs,
                         const float *K, int ks, const float *bias, float *out,
                         int os, hipStream_t st);
@@ -88,11 +91,17 @@ int kcnn_conv_fwd_frame_pool(const kcnn::ConvGeom &g, const float *X, int xs,
                              unsigned char *mask, int ms, int pc,
                              hipStream_t st, int ph = 1, int pw = 1,
                              PoolStatsOut *stats = nullptr);
+// The fp32 backward (cnsl-conv-frame-bwd.hip): the data gradient, the weight
+// gradient (ws of kcnn_conv_wgrad_frame_ws(g) bytes, 0 = not eligible) ...
 int kcnn_conv_dgrad_frame(const kcnn::ConvGeom &g, const float *dY, int dys,
                           const float *K, int ks, float *dX, int dxs,
                           hipStream_t st);
-// Fused backward (one pass over dY): dX (nullable) and gW/gb.  ws must hold
-// kcnn_conv_bwd_frame_ws(g) bytes (0 = shape not eligible).
+size_t kcnn_conv_wgrad_frame_ws(const kcnn::ConvGeom &g);
+int kcnn_conv_wgrad_frame(const kcnn::ConvGeom &g, const float *X, int xs,
+                          const float *dY, int dys, float *gW, int gws,
+                          float *gb, void *ws, size_t ws_bytes, hipStream_t st);
+// ... and the fused backward (one pass over dY): dX (nullable) and gW/gb.
+// ws must hold kcnn_conv_bwd_frame_ws(g) bytes (0 = shape not eligible).
 size_t kcnn_conv_bwd_frame_ws(const kcnn::ConvGeom &g);
 // pc > 0: dY / dys are instead the derivative of a ph x 1 x pc Maxpool over
 // Y and pmask / pms its routing mask (hipF_conv2d_maxpool[3d]: 1 byte per
@@ -131,21 +140,27 @@ bool kcnn_conv_wgrad_x6_plan(const kcnn::ConvGeom &g, int xs, int dys, int &S, i
                              size_t &ws_bytes);
 int kcnn_conv_wgrad_x6(const kcnn::ConvGeom &g, const float *X, int xs, const float *dY,
                        int dys, float *ws, int S, int fps, hipStream_t st);
-size_t kcnn_conv_wgrad_frame_ws(const kcnn::ConvGeom &g);
-int kcnn_conv_wgrad_frame(const kcnn::ConvGeom &g, const float *X, int xs,
-                          const float *dY, int dys, float *gW, int gws,
-                          float *gb, void *ws, size_t ws_bytes, hipStream_t st);
-// Deterministic column sums of a [S x E] fp32 slab, out[e] = sum_s in[s][e]
-// in a fixed order: pass 1 sums groups of 32 rows into tmp [ceil(S/32) x E],
-// pass 2 sums the groups (cnsl-conv-frame.hip).
-size_t kcnn_reduce_splits_ws(int S, int E);
-int kcnn_reduce_splits(const float *in, int S, int E, float *out, hipStream_t st);
-int kcnn_reduce_splits_pass1(const float *in, int S, int E, float *tmp,
-                             hipStream_t st);
-// one pass into the implicit-GEMM wgrad layout: e = g*inner + k (e < nw) ->
-// gW[k][g]; e >= nw -> gb[e - nw].
+
+// The split reduction (cnsl-conv-reduce.hip): deterministic column sums of a
+// [S x E] fp32 slab of workgroup partials, sum[e] = sum_s in[s][e], in one
+// pass (reduce_splits_kernel): a block takes 64 columns, its four waves sum
+// interleaved rows and their sums are added in a fixed order.  e < nw goes
+// to gW[row][col], (row, col) = gk_layout ? (e % inner, e / inner) :
+// (e / inner, e % inner), and e >= nw to gb[e - nw]; with u.W set
+// (conv-update.h) the sums step W / prev / b instead.
+int kcnn_reduce_splits_epi(const float *in, int S, int E, int nw, int inner, int gk_layout,
+                           float *gW, int gws, float *gb, const ConvUpdateEpi &u,
+                           hipStream_t st);
+// the implicit-GEMM wgrad layout (gk_layout 1: e = g*inner + k -> gW[k][g])
+// under the current thread's update request, marked applied when taken
 int kcnn_reduce_splits_wgrad(const float *in, int S, int E, int nw, int inner, float *gW,
                              int gws, float *gb, hipStream_t st);
+// The bytes callers reserve behind their partials, and the first pass of the
+// implicit-GEMM v1 split-K reduction (groups of 32 rows into tmp
+// [ceil(S/32) x E]; conv_splitk_reduce_kernel adds the groups).
+size_t kcnn_reduce_splits_ws(int S, int E);
+int kcnn_reduce_splits_pass1(const float *in, int S, int E, float *tmp,
+                             hipStream_t st);
 
 // The fp32-MFMA family (cnsl-conv-mfma.hip), same contract as the launchers
 // above: 0 launched, -1 declined with nothing launched, > 0 a HIP error.

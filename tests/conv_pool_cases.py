@@ -58,7 +58,8 @@ class Geom:
         self.padded = self.pad_h > 0 or self.pad_w > 0
 
 
-# ---- the launchers, modelled (cnsl-conv-frame.hip, cnsl-conv-x6.hip, cnsl-conv-igemm-x6.hip) --
+# ---- the launchers, modelled (cnsl-conv-frame.hip, cnsl-conv-frame-bwd.hip, cnsl-conv-x6.hip,
+# cnsl-conv-igemm-x6.hip) --
 FRAME_LDS_MAX = 96 * 1024
 BIG_LDS_MAX = 160 * 1024
 

@@ -13,7 +13,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "kaldi-cnn_amd", "src")
-DMA_FILES = {"cnslmat/cnsl-conv-x6.hip", "cnslmat/cnsl-conv-frame.hip",
+DMA_FILES = {"cnslmat/cnsl-conv-x6.hip", "cnslmat/cnsl-conv-frame-bwd.hip",
              "kaldi-lite/cu-gemm-x6.hip"}
 
 
