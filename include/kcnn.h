@@ -608,6 +608,30 @@ int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
 typedef struct kcnn_online kcnn_online;
 kcnn_online *kcnn_online_new(kcnn_nnet *n, int num_streams, int max_chunk, const float *priors,
                              int num_priors, float prior_scale, int apply_log);
+/* kcnn_online_new with share_time != 0: a step whose network kcnn_nnet_compute_
+ * shared's plan accepts (kcnn_online_shared_prefix > 0) runs the leading Splice
+ * -> {Convolution | Maxpool | ReLU}... components once per time step instead of
+ * once per emitted frame's window.  Each slot that emits k frames gives a
+ * segment of k + L + R rows of the frames it holds (clamped at the utterance's
+ * ends); the packed segments are a small unpadded whole-utterance input, every
+ * Convolution level of it one launch (fp32 products on the bf16 matrix cores
+ * with bias and ReLU in the store), the pools, ReLUs and the gather those of
+ * kcnn_nnet_compute_shared; the components above the prefix run as without
+ * share_time.  To the error bar of the products, not the bits, the same
+ * values.  The level maps are the computer's own, allocated once by the first
+ * accepted step for the most rows a step can have, num_streams x (max_chunk +
+ * L + 2 R); nothing is carried from step to step beyond what kcnn_online_new
+ * keeps, and a step takes either route whatever the last one took.  A step of
+ * a network the plan declines is kcnn_online_new's, bit for bit.  After a
+ * time-shared step kcnn_nnet_output below prefix - 1 is an error.
+ * share_time = 0: kcnn_online_new. */
+kcnn_online *kcnn_online_new_shared(kcnn_nnet *n, int num_streams, int max_chunk,
+                                    const float *priors, int num_priors, float prior_scale,
+                                    int apply_log, int share_time);
+/* The number of leading components the next step would run as time maps: the
+ * network's kcnn_nnet_time_shared_prefix as the literal path now stands for a
+ * computer made with share_time, else 0.  -1 on error.  Touches no device. */
+int kcnn_online_shared_prefix(const kcnn_online *o);
 void kcnn_online_free(kcnn_online *o);
 /* One step.  For i < num (HOST arrays), slot streams[i] -- each slot named at
  * most once -- gets num_new[i] frames, 0 <= num_new[i] <= max_chunk: the next

@@ -97,6 +97,12 @@ def lib():
                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                           ctypes.c_int]
             L.kcnn_online_free.argtypes = [ctypes.c_void_p]
+        if hasattr(L, "kcnn_online_new_shared"):  # (absent from builds before share_time)
+            L.kcnn_online_new_shared.restype = ctypes.c_void_p
+            L.kcnn_online_new_shared.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
+                                                 ctypes.c_int, ctypes.c_int]
+            L.kcnn_online_shared_prefix.argtypes = [ctypes.c_void_p]
             L.kcnn_online_accept.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, MatrixDim, ctypes.c_void_p, ctypes.c_void_p,
                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -1052,10 +1058,14 @@ class OnlineComputer:
     are Compute's.  `net` (the test model) is borrowed and kept alive here; the
     streams' history lives in device buffers of the computer's own, allocated
     by the first accepted step, so other forward calls of `net` between steps
-    disturb nothing."""
+    disturb nothing.  With `share_time` (kcnn_online_new_shared) a step runs
+    the leading Splice -> Convolution / Maxpool / ReLU components once per time
+    step of the frames its slots hold instead of once per emitted frame's
+    window, where the network allows it (TimeSharedPrefix() > 0): the same
+    rows to the error bar of the products, not the bits."""
 
     def __init__(self, net: Nnet, num_streams: int, max_chunk: int, priors=None,
-                 prior_scale=1.0, apply_log=False):
+                 prior_scale=1.0, apply_log=False, share_time=False):
         import numpy as np
         self._h = None
         self.net = net
@@ -1063,8 +1073,13 @@ class OnlineComputer:
         if priors is not None:
             pr = np.ascontiguousarray(priors, np.float32).ravel()
             pp, np_ = pr.ctypes.data_as(ctypes.c_void_p), len(pr)
-        h = lib().kcnn_online_new(net._h, int(num_streams), int(max_chunk), pp, np_,
-                                  ctypes.c_float(prior_scale), int(bool(apply_log)))
+        if share_time:
+            h = lib().kcnn_online_new_shared(net._h, int(num_streams), int(max_chunk), pp, np_,
+                                             ctypes.c_float(prior_scale), int(bool(apply_log)),
+                                             1)
+        else:
+            h = lib().kcnn_online_new(net._h, int(num_streams), int(max_chunk), pp, np_,
+                                      ctypes.c_float(prior_scale), int(bool(apply_log)))
         if not h:
             raise KcnnError(lib().kcnn_last_error().decode(errors="replace"))
         self._h = ctypes.c_void_p(h)
@@ -1107,6 +1122,17 @@ class OnlineComputer:
             nn.ctypes.data_as(ctypes.c_void_p), fi.ctypes.data_as(ctypes.c_void_p), len(st),
             counts.ctypes.data_as(ctypes.c_void_p), ctypes.byref(p), ctypes.byref(od)))
         return _device_view(p.value, od), [int(c) for c in counts]
+
+    def TimeSharedPrefix(self):
+        """The number of leading components the next step would run as time
+        maps (kcnn_online_shared_prefix): 0 without share_time, or when the
+        network's plan declines as the literal path now stands."""
+        if not hasattr(lib(), "kcnn_online_shared_prefix"):
+            return 0
+        n = lib().kcnn_online_shared_prefix(self._h)
+        if n < 0:
+            raise KcnnError(lib().kcnn_last_error().decode(errors="replace"))
+        return int(n)
 
     def Reset(self, stream: int):
         """Abandons the slot's utterance (kcnn_online_reset)."""

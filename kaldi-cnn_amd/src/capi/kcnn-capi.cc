@@ -891,6 +891,24 @@ kcnn_online *kcnn_online_new(kcnn_nnet *n, int num_streams, int max_chunk, const
   });
   return o;
 }
+kcnn_online *kcnn_online_new_shared(kcnn_nnet *n, int num_streams, int max_chunk,
+                                    const float *priors, int num_priors, float prior_scale,
+                                    int apply_log, int share_time) {
+  kcnn_online *o = nullptr;
+  guard([&] {
+    o = new kcnn_online(n ? &n->stack : nullptr, num_streams, max_chunk, priors, num_priors,
+                        prior_scale, apply_log != 0, share_time != 0);
+  });
+  return o;
+}
+int kcnn_online_shared_prefix(const kcnn_online *o) {
+  int prefix = -1;
+  guard([&] {
+    if (o == nullptr) KALDI_ERR << "kcnn_online_shared_prefix: no computer";
+    prefix = o->computer.TimeSharedPrefix();
+  });
+  return prefix;
+}
 void kcnn_online_free(kcnn_online *o) { delete o; }
 
 int kcnn_online_accept(kcnn_online *o, const float *chunk, MatrixDim dim, const int32_t *streams,

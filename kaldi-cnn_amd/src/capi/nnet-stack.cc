@@ -292,6 +292,7 @@ void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count,
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   ForgetMinibatch();
   prob_forward_ = whole_utts_ = frames_fused_ = time_shared_ = false;
+  examples_first_ = 0;
   int first = 0;  // the component the loop starts at
   if (fl != nullptr) {
     // the offset of the input chunk's first frame from an example's own
@@ -411,9 +412,50 @@ const CuMatrix<BaseFloat> &NnetStack::ComputeExamples(const float *feats, Matrix
   return Loglikes(apply_log, prior_offsets, num);
 }
 
+CuMatrix<BaseFloat> &NnetStack::ExamplesInput(int first, int num) {
+  KALDI_ASSERT(first > 0 && first < NumComponents() && num > 0);
+  CuMatrix<BaseFloat> &y = out(first - 1).value;
+  const int rows = num * (int)out(first - 1).offsets.size(),
+            cols = comps_[first - 1].c->OutputDim();
+  if (y.NumRows() != rows || y.NumCols() != cols) y.Resize(rows, cols, kUndefined);
+  return y;
+}
+
+const CuMatrix<BaseFloat> &NnetStack::ComputeExamplesFrom(int first, const float *feats,
+                                                          MatrixDim dim, int num,
+                                                          bool apply_log,
+                                                          const double *prior_offsets) {
+  const int nc = NumComponents();
+  KALDI_ASSERT(first > 0 && first < nc && comps_[0].splice != nullptr &&
+               !cnsl::nnet0::LiteralPath());
+  const int count = FusedLoglikes(apply_log) ? nc - 1 : nc;
+  for (int i = first; i < count; i++) {  // sized as ComputeExamples sizes them
+    CuMatrix<BaseFloat> &y = out(i).value;
+    const int rows = num * (int)out(i).offsets.size(), cols = comps_[i].c->OutputDim();
+    if (y.NumRows() != rows || y.NumCols() != cols) y.Resize(rows, cols, kUndefined);
+  }
+  num_chunks_ = num;
+  acts_[0].value.Borrow(const_cast<float *>(feats), dim.rows, dim.cols, dim.stride);
+  ForgetMinibatch();
+  whole_utts_ = time_shared_ = false;
+  frames_fused_ = true;  // as after ComputeExamples through a first Splice
+  examples_first_ = first;
+  for (int i = first; i < count; i++) {
+    if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
+    ChunkInfo ii = in_info(i), oi = out_info(i);
+    auto hint = input_stats(i);
+    comps_[i].c->Propagate(ii, oi, in(i).value, &out(i).value);
+  }
+  prob_forward_ = true;
+  return Loglikes(apply_log, prior_offsets, num);
+}
+
 const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
   KALDI_ASSERT(i >= -1 && i < NumComponents());
   Activation &a = out(i);
+  if (examples_first_ > 0 && i >= 0 && i + 1 < examples_first_)
+    KALDI_ERR << "output of component " << i << " was not formed: the streaming step ran "
+              << "components 0 to " << examples_first_ - 1 << " as time maps";
   if (time_shared_ && i >= 0 && i + 1 < (int)time_views_.size())
     KALDI_ERR << "output of component " << i << " was not formed: kcnn_nnet_compute_shared ran "
               << "components 0 to " << time_views_.size() - 1 << " as time maps; see "
@@ -759,6 +801,7 @@ void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
   ForgetMinibatch();
   prob_forward_ = whole_utts_ = true;
   frames_fused_ = false;
+  examples_first_ = 0;
   time_shared_ = first > 0;
   if (first > 0) {
     // the time maps have run and the gather has written component first's input

@@ -246,6 +246,23 @@ class NnetStack {
   const CuMatrix<BaseFloat> &ComputeExamples(const float *feats, MatrixDim dim,
                                              const int32_t *examples, int num, bool apply_log,
                                              const double *prior_offsets);
+  // The upper part of ComputeExamples, for a caller that has formed component
+  // `first`'s input itself (an OnlineComputer with share_time: its time maps,
+  // gathered into ExamplesInput): components first .. of a pass of `num`
+  // examples, then ComputeExamples' result.  0 < first < NumComponents(), and
+  // component 0 is a Splice (the plan's condition).  ExamplesInput sizes
+  // Output(first - 1) to its `num` rows, without the fill, and returns it to
+  // be written whole.  (feats, dim) is what Output(-1) then names, as after
+  // ComputeExamples; Output(i) below first - 1 throws afterwards: those
+  // activations were never formed.  Same state otherwise.
+  CuMatrix<BaseFloat> &ExamplesInput(int first, int num);
+  const CuMatrix<BaseFloat> &ComputeExamplesFrom(int first, const float *feats, MatrixDim dim,
+                                                 int num, bool apply_log,
+                                                 const double *prior_offsets);
+  // component i when it is a ConvolutionComponent, else NULL
+  cnsl::nnet0::ConvolutionComponent *ConvAt(int i) const {
+    return i >= 0 && i < NumComponents() ? comps_[i].conv : nullptr;
+  }
   int InputDim() const { return comps_.front().c->InputDim(); }
   int OutputDim() const { return comps_.back().c->OutputDim(); }
 
@@ -419,7 +436,10 @@ class NnetStack {
   // the last forward was PropagateFrames' through a first Splice: component
   // 0's input is the corpus, not a window matrix, and it has no Backprop
   bool frames_fused_ = false;
-  LabelStaging frames_;                 // PropagateFrames' example triples
+  // the last forward was ComputeExamplesFrom's: the outputs of components
+  // below examples_first_ - 1 were not formed (0: all were)
+  int examples_first_ = 0;
+  LabelStaging frames_;                // PropagateFrames' example triples
   // its window matrix when laid out, contiguous as a caller's would be
   kaldi::CuBuffer frames_input_;
 };

@@ -24,8 +24,9 @@ StreamState checked_state(const NnetStack *net, int num_streams, int max_chunk) 
 
 OnlineComputer::OnlineComputer(NnetStack *net, int num_streams, int max_chunk,
                                const float *priors, int num_priors, float prior_scale,
-                               bool apply_log)
-    : net_(net),
+                               bool apply_log, bool share_time)
+    : share_time_(share_time),
+      net_(net),
       state_(checked_state(net, num_streams, max_chunk)),
       apply_log_(apply_log) {
   net_->CheckPriors(priors, num_priors, apply_log, "kcnn_online_new");
@@ -59,6 +60,21 @@ const CuMatrix<BaseFloat> &OnlineComputer::Accept(const float *chunk, MatrixDim 
   if (!bad.empty()) KALDI_ERR << who << ": " << bad;
   if (totals.out_rows > 0) net_->CheckExamples(totals.out_rows, who);
   if (num == 0) return empty_;
+  // the time maps' rows, when the step runs the leading components as such
+  TimePlan plan;
+  TimeRows rows;
+  if (share_time_ && totals.out_rows > 0) plan = net_->TimeSharedPlan();
+  if (plan.prefix() > 0) {
+    state_.Segments(step, &segs_);
+    const std::string no = plan_time_rows(plan, segs_.lengths.data(), segs_.num, false, &rows);
+    if (!no.empty()) KALDI_ERR << who << ": " << no;
+    KALDI_ASSERT(rows.result_rows == totals.out_rows && rows.input_rows == segs_.map_rows &&
+                 rows.input_rows <= state_.max_map_rows());
+    for (const TimeLevel &lev : plan.levels)
+      if (state_.max_map_rows() * lev.width >= kStreamLimit)
+        KALDI_ERR << who << ": a time map of " << state_.max_map_rows() << " rows of "
+                  << lev.width << " columns reaches 2^31 elements";
+  }
 
   hipStream_t st = CuDevice::Instantiate().Stream();
   const MatrixDim arena_dim = {state_.arena_rows(), cols, cols};
@@ -71,11 +87,19 @@ const CuMatrix<BaseFloat> &OnlineComputer::Accept(const float *chunk, MatrixDim 
     }
   }
   // the step's image -> the device, before the launches; the slots advance
+  // (a time-shared step's segment descriptors and result starts behind it)
   const StepLayout lay = step_layout(num, totals);
-  char *image = staging_.Begin(lay.bytes);
+  const size_t seg_ints =
+      plan.prefix() > 0 ? segs_.desc.size() + segs_.out_start.size() : (size_t)0;
+  const size_t bytes = lay.bytes + sizeof(int32_t) * seg_ints;
+  char *image = staging_.Begin(bytes);
   state_.Plan(step, totals, image, num_out);
-  const int32_t *d_image =
-      reinterpret_cast<const int32_t *>(staging_.Commit(lay.bytes, st));
+  if (seg_ints > 0) {
+    int32_t *seg = reinterpret_cast<int32_t *>(image + lay.bytes);
+    std::copy(segs_.desc.begin(), segs_.desc.end(), seg);
+    std::copy(segs_.out_start.begin(), segs_.out_start.end(), seg + segs_.desc.size());
+  }
+  const int32_t *d_image = reinterpret_cast<const int32_t *>(staging_.Commit(bytes, st));
   float *arena = static_cast<float *>(arena_.p);
   if (totals.copy_rows > 0) {
     CuProfileScope prof("kn_stream_assemble");
@@ -85,9 +109,95 @@ const CuMatrix<BaseFloat> &OnlineComputer::Accept(const float *chunk, MatrixDim 
                                       totals.copy_rows, reinterpret_cast<kcnn_stream_t>(st)));
   }
   if (totals.out_rows == 0) return empty_;
+  if (plan.prefix() > 0) {
+    const int32_t *d_seg = d_image + lay.bytes / sizeof(int32_t);
+    return AcceptShared(plan, rows, segs_, arena, arena_dim, d_seg, d_seg + segs_.desc.size());
+  }
   return net_->ComputeExamples(arena, arena_dim, d_image + lay.triples, totals.out_rows,
                                apply_log_,
                                static_cast<const double *>(d_offsets_.p));
+}
+
+// The step's time maps, the gather into component prefix's input, and the
+// net's pass from there; `rows` has been checked against `plan`.
+const CuMatrix<BaseFloat> &OnlineComputer::AcceptShared(const TimePlan &plan,
+                                                        const TimeRows &rows,
+                                                        const StepSegments &segs,
+                                                        const float *arena, MatrixDim arena_dim,
+                                                        const int32_t *d_desc,
+                                                        const int32_t *d_out_start) {
+  const int p = plan.prefix();
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  if (maps_.size() < (size_t)p) maps_.resize((size_t)p);
+  // the first rows.computed[l] rows of level l's buffer
+  auto map_of = [&](int l, MatrixDim *dim) {
+    const int width = plan.levels[l].width;
+    *dim = MatrixDim{(int)rows.computed[l], width, width};
+    return static_cast<float *>(
+        maps_[l].reserve(sizeof(float) * (size_t)state_.max_map_rows() * (size_t)width));
+  };
+  MatrixDim in_dim;
+  const float *in = nullptr;
+  {
+    float *m0 = map_of(0, &in_dim);
+    CuProfileScope prof("kn_stream_segments");
+    CNSL_SAFE_CALL(kn_stream_segments(arena, arena_dim, m0, in_dim, d_desc, segs.num, st));
+    in = m0;
+  }
+  for (int l = 1; l < p; l++) {
+    const TimeLevel &lev = plan.levels[l], &below = plan.levels[l - 1];
+    const int nrows = (int)rows.computed[l];
+    const bool relu_next = l + 1 < p && plan.levels[l + 1].kind == TimeComp::kRelu;
+    MatrixDim out_dim;
+    if (lev.kind == TimeComp::kConv) {
+      cnsl::nnet0::ConvolutionComponent *conv = net_->ConvAt(l);
+      KALDI_ASSERT(conv != nullptr);
+      const CuMatrix<BaseFloat> &W = conv->LinearParams();
+      const bool on_splice = below.kind == TimeComp::kSplice;
+      // weight row i + d kh + c kh kw: a whole frame's block a tap on the Splice
+      // (c = 0, kh = the frame), every kw-th row from d above (kh = 1)
+      const int wc = on_splice ? 1 : lev.taps, wd = on_splice ? below.width : 1;
+      // the ReLU on it in the store: the conv's own level is then never formed
+      float *m = map_of(relu_next ? l + 1 : l, &out_dim);
+      CuProfileScope prof("kn_timemap_conv");
+      CNSL_SAFE_CALL(kn_timemap_conv(in, in_dim, W.Data(), W.Dim(), conv->BiasParams().Data(), m,
+                                     out_dim, nrows, lev.taps, below.dilation, wc, wd,
+                                     relu_next ? 1 : 0, st));
+      in = m;
+      in_dim = out_dim;
+      if (relu_next) l++;
+      continue;
+    }
+    // a pool, a ReLU, or a pool and the ReLU on it in one pass
+    const bool pool = lev.kind == TimeComp::kPool, both = pool && relu_next;
+    MatrixDim act_dim = {0, 0, 0};
+    float *m = map_of(l, &out_dim);
+    float *act = both ? map_of(l + 1, &act_dim) : nullptr;
+    if (!pool) { act = m; act_dim = out_dim; }
+    CuProfileScope prof("kn_timemap_epilogue");
+    CNSL_SAFE_CALL(kn_timemap_epilogue(in, in_dim, pool ? m : nullptr,
+                                       pool ? out_dim : MatrixDim{0, 0, 0}, act, act_dim, nrows,
+                                       pool ? lev.taps : 1, pool ? lev.pool_channel : 1,
+                                       below.dilation, st));
+    in = both || !pool ? act : m;
+    in_dim = both || !pool ? act_dim : out_dim;
+    if (both) l++;
+  }
+  const TimeLevel &top = plan.levels[p - 1];
+  const int context = plan.levels[0].positions - 1;
+  CuMatrix<BaseFloat> &y = net_->ExamplesInput(p, segs.out_rows);
+  KALDI_ASSERT(y.NumCols() == top.channels * top.positions && y.NumRows() == segs.out_rows);
+  {
+    CuProfileScope prof("kn_timemap_gather");
+    CNSL_SAFE_CALL(kn_timemap_gather(in, in_dim, y.Data(), y.Dim(), d_out_start, segs.num,
+                                     context, top.positions, top.dilation, st));
+  }
+  return net_->ComputeExamplesFrom(p, arena, arena_dim, segs.out_rows, apply_log_,
+                                   static_cast<const double *>(d_offsets_.p));
+}
+
+int OnlineComputer::TimeSharedPrefix() const {
+  return share_time_ ? net_->TimeSharedPlan().prefix() : 0;
 }
 
 void OnlineComputer::Reset(int stream) {

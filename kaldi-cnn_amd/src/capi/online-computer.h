@@ -13,6 +13,20 @@
 // stream, and its other forward calls between steps disturb none.  A network
 // with a Splice above component 0 is recomputed per example, as
 // PropagateFrames does: nothing deeper than the input is cached.
+//
+// With share_time, a step of a network the time plan accepts (time-plan.h) is
+// a small whole-utterance pass over time maps instead: each emitting slot's
+// frames [e0 - L, e0 + k + R), clamped, are one segment of the level-0 map
+// (kn_stream_segments from the arena; stream-state.h StepSegments), the packed
+// segments an unpadded ComputeShared input.  Every Convolution level is one
+// kn_timemap_conv, the ReLU on it fused; pools and the gather are
+// ComputeShared's kernels; the components above the prefix run as in any other
+// step (NnetStack::ComputeExamplesFrom).  The maps are the computer's own, one
+// buffer a level allocated once for the most rows a step can have, so a step
+// of another size allocates nothing below the first FC and the net's other
+// forward calls, ComputeShared included, disturb nothing.  Nothing is carried
+// between steps: Reset, final and slot reuse are what they were, and a step
+// takes either route whatever the last one took.
 // Errors are thrown; kcnn-capi.cc turns them into error codes.
 #ifndef KCNN_CAPI_ONLINE_COMPUTER_H_
 #define KCNN_CAPI_ONLINE_COMPUTER_H_
@@ -31,7 +45,7 @@ class OnlineComputer {
   // (OutputDim host floats, finite and > 0, only with apply_log; or NULL).
   // Allocates nothing on the device; throws on numbers no arena can have.
   OnlineComputer(NnetStack *net, int num_streams, int max_chunk, const float *priors,
-                 int num_priors, float prior_scale, bool apply_log);
+                 int num_priors, float prior_scale, bool apply_log, bool share_time = false);
 
   // One step: slot streams[i] gets num_new[i] frames (0 .. max_chunk; 0 only
   // with final[i]), rows of `chunk` ([sum of num_new x InputDim], device) in
@@ -47,8 +61,21 @@ class OnlineComputer {
                                     int32_t *num_out);
   void Reset(int stream);                          // abandons the slot's utterance
   void Frames(int stream, int64_t out[2]) const;  // {seen, emitted}
+  // The components the next step would run as time maps: the net's plan as
+  // the literal path now stands, 0 without share_time or when it declines.
+  int TimeSharedPrefix() const;
 
  private:
+  // the time-shared route of a step whose image is staged and arena assembled
+  const CuMatrix<BaseFloat> &AcceptShared(const TimePlan &plan, const TimeRows &rows,
+                                          const StepSegments &segs, const float *arena,
+                                          MatrixDim arena_dim, const int32_t *d_desc,
+                                          const int32_t *d_out_start);
+  bool share_time_;
+  StepSegments segs_;
+  // level l's map, [state_.max_map_rows() x its width], allocated once by the
+  // first time-shared step (a level a fused ReLU skips is never allocated)
+  std::vector<kaldi::CuBuffer> maps_;
   NnetStack *net_;
   StreamState state_;
   bool apply_log_;

@@ -16,6 +16,12 @@
 // writes, into the slot's other buffer, the tail it still needs -- frames
 // [max(0, emitted - L), seen), at most L + R of them -- and behind it the new
 // frames; then the slot flips.  Nothing is copied in place.
+//
+// A computer made with share_time reads a checked step a second way (Segments):
+// as the packed level-0 rows of a small whole-utterance pass over time maps,
+// one segment per emitting slot, out of the buffers the step writes
+// (kn_stream_segments; scripts/stream_segments_check.cc).  It keeps no state
+// of its own.
 #ifndef KCNN_CAPI_STREAM_STATE_H_
 #define KCNN_CAPI_STREAM_STATE_H_
 
@@ -84,6 +90,24 @@ inline StepLayout step_layout(int num, const StepTotals &t) {
   l.bytes = sizeof(int32_t) * (l.triples + 3 * (size_t)t.out_rows);
   return l;
 }
+
+// ints of a segment's descriptor (kn_stream_segments): {first source arena row,
+// which may lie below lo; lo; hi; first map row; rows}
+constexpr int kStreamSegmentInts = 5;
+
+// A checked step as a small whole-utterance pass over time maps (time-plan.h):
+// each slot that emits k > 0 frames e0 .. e0 + k - 1 gives one segment of k + L
+// + R level-0 map rows, row j being the slot's frame clamp(e0 - L + j, 0, its
+// newest frame), read from the buffer the step's assembly writes.  The
+// segments are packed in the step's order: an unpadded input of `lengths` with
+// k_i result rows each, out_start their prefix (num + 1 entries).
+struct StepSegments {
+  int num = 0;
+  int map_rows = 0, out_rows = 0;
+  std::vector<int32_t> desc;       // kStreamSegmentInts a segment
+  std::vector<int32_t> lengths;    // k_i + L + R
+  std::vector<int32_t> out_start;  // 0, k_0, k_0 + k_1, ...
+};
 
 class StreamState {
  public:
@@ -187,6 +211,42 @@ class StreamState {
       if (final) sl = Slot();
     }
     row_start[step.num] = copy;
+  }
+
+  // The most map rows a step can need: every slot emitting its most, max_chunk
+  // + R frames (a final step of a slot whose last R frames were waiting).
+  int64_t max_map_rows() const {
+    return (int64_t)num_streams() * ((int64_t)max_chunk_ + left_ + 2 * (int64_t)right_);
+  }
+
+  // The segments of a CHECKED step, BEFORE Plan advances the slots (which this
+  // does not): what Plan will leave in the arena, read as time-map rows.
+  void Segments(const StreamStep &step, StepSegments *segs) const {
+    segs->num = segs->map_rows = segs->out_rows = 0;
+    segs->desc.clear();
+    segs->lengths.clear();
+    segs->out_start.assign(1, 0);
+    for (int i = 0; i < step.num; i++) {
+      const Slot &sl = slots_[step.streams[i]];
+      const int32_t n = step.num_new[i];
+      const int64_t seen = sl.seen + n;
+      const int64_t k = Ready(seen, step.final[i] != 0) - sl.emitted;
+      if (k <= 0) continue;
+      // Plan writes frames [base, seen) to the slot's other buffer from row 0
+      const int64_t base = sl.seen - Tail(sl);
+      const int32_t dst = BufferRow(step.streams[i], sl.cur ^ 1);
+      const int32_t rows = (int32_t)(k + left_ + right_);
+      segs->desc.push_back(dst + (int32_t)(sl.emitted - left_ - base));
+      segs->desc.push_back(dst);
+      segs->desc.push_back(dst + (int32_t)(seen - base) - 1);
+      segs->desc.push_back(segs->map_rows);
+      segs->desc.push_back(rows);
+      segs->lengths.push_back(rows);
+      segs->map_rows += rows;
+      segs->out_rows += (int32_t)k;
+      segs->out_start.push_back(segs->out_rows);
+      segs->num++;
+    }
   }
 
   // Abandons the slot's utterance; false for a slot out of range.

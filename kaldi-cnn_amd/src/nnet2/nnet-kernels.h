@@ -119,6 +119,18 @@ int kn_stream_assemble(float *arena, MatrixDim arena_dim, const float *chunk, Ma
                        const int *row_start, const int *desc, int num_slots, int total_rows,
                        kcnn_stream_t st);
 
+/* The level-0 time map of a time-shared streaming step (capi/stream-state.h,
+ * StepSegments): desc (DEVICE, 5 ints a segment, first destination rows
+ * ascending) holds {src, lo, hi, dst, rows}: map row dst + j, j < rows, is
+ * arena row clamp(src + j, lo, hi); src may lie below lo (the frames before an
+ * utterance's first repeat it) and src + rows - 1 above hi (those after its
+ * last).  Map rows that no segment covers are not written.  A source row is
+ * clamped into the arena at last, so descriptors that disagree with the
+ * matrices still read inside it; a destination row is a row of `map` by the
+ * search.  16-byte lanes where the strides and bases allow. */
+int kn_stream_segments(const float *arena, MatrixDim arena_dim, float *map, MatrixDim map_dim,
+                       const int *desc, int num_segs, kcnn_stream_t st);
+
 /* fp64 stat vectors of NonlinearComponent (Scale/Add/UpdateStats):
  * y = beta * y + alpha * x  (x may be NULL: y = beta * y). */
 int kn_dvec_update(double *y, const double *x, double alpha, double beta, int n,
@@ -267,6 +279,25 @@ int kn_timemap_epilogue(const float *in, MatrixDim in_dim, float *pooled, Matrix
 int kn_timemap_gather(const float *map, MatrixDim map_dim, float *out, MatrixDim out_dim,
                       const int *utt_start, int num_utts, int ext, int positions, int dilation,
                       kcnn_stream_t st);
+
+/* ---- nnet-timemap-conv.hip: a Convolution level of the time maps, one launch ---- */
+
+/* out(s, g) = act(bias[g] + sum_{d < kernel_width} sum_{c < C} in(s + delta d, c)
+ * * w(c wc + d wd, g)) for s < rows, g < group: C = in_dim.cols, group =
+ * w_dim.cols = out_dim.cols, w the component's LinearParams() read as fp32.
+ * (wc, wd) = (1, C) directly on the Splice, where a filter spans the frame;
+ * (kernel_width, 1) above it.  act: the identity, or with relu != 0 x < 0 -> 0
+ * (NaN and -0 stay).  The products are bf16x6 (x6::mfma6 on the truncating
+ * three-way split of both operands, made in the kernel on every call), the
+ * accumulation fp32, the bias added in fp32 at the store.  Any rows, C and
+ * group >= 1, any strides >= the columns; a base or a stride of `in` that is
+ * not 16-byte aligned, or C % 4 != 0, takes 4-byte loads.  Refused with
+ * hipErrorInvalidValue before any launch: a highest tap rows - 1 + delta
+ * (kernel_width - 1) that is not a row of `in`, a highest weight row (C - 1)
+ * wc + (kernel_width - 1) wd that is not one of `w`, out_dim.rows < rows. */
+int kn_timemap_conv(const float *in, MatrixDim in_dim, const float *w, MatrixDim w_dim,
+                    const float *bias, float *out, MatrixDim out_dim, int rows, int kernel_width,
+                    int delta, int wc, int wd, int relu, kcnn_stream_t st);
 
 #ifdef __cplusplus
 }

@@ -356,6 +356,59 @@ __global__ __launch_bounds__(256) void stream_assemble_kernel(
   }
 }
 
+// A time-shared streaming step's level-0 map (kn_stream_segments), shaped as
+// the kernel above: groups of `rpb` consecutive map rows to a block; one
+// thread per row finds the row's segment (a binary search over the segments'
+// first destination rows, ascending) and leaves the arena row it copies --
+// clamped to the segment's [lo, hi], then into the arena -- in LDS; then all
+// 256 threads copy the group's V-float units.  A map row no segment covers is
+// not written.
+struct SegmentArgs {
+  int num_segs, map_rows, arena_rows, rpb;
+  FastDiv div_units;
+};
+
+template <int V>
+__global__ __launch_bounds__(256) void stream_segments_kernel(
+    const float *__restrict__ arena, int64_t as, float *__restrict__ map, int64_t ms,
+    const int *__restrict__ desc, SegmentArgs a, int units) {
+  __shared__ int s_src[kRaggedMaxRows];  // < 0: nothing to copy
+  const int ngroups = (a.map_rows + a.rpb - 1) / a.rpb;
+  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+    const int r0 = grp * a.rpb;
+    const int nr = min(a.rpb, a.map_rows - r0);
+    __syncthreads();  // the last group's readers are done
+    if ((int)threadIdx.x < nr) {
+      const int r = r0 + (int)threadIdx.x;
+      int lo = 0, hi = a.num_segs;  // dst(lo) <= r < dst(hi)
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (desc[5 * (int64_t)mid + 3] <= r) lo = mid; else hi = mid;
+      }
+      const int *d = desc + 5 * (int64_t)lo;
+      const int k = r - d[3];
+      // (k < 2^31 - src0 by k < rows; the host keeps src0 + rows inside an int)
+      const bool ok = k >= 0 && k < d[4] && d[1] <= d[2];
+      const int src = ok ? max(0, min(max(d[1], min(d[0] + k, d[2])), a.arena_rows - 1)) : -1;
+      s_src[threadIdx.x] = src;
+    }
+    __syncthreads();
+    const int n = nr * units;
+    for (int e = threadIdx.x; e < n; e += 256) {
+      uint32_t lr, cu;
+      a.div_units.divmod((uint32_t)e, lr, cu);
+      if (s_src[lr] < 0) continue;
+      const int col = (int)cu * V;
+      const float *src = arena + (int64_t)s_src[lr] * as + col;
+      float *dst = map + (int64_t)(r0 + (int)lr) * ms + col;
+      if constexpr (V == 4)
+        *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
+      else
+        *dst = *src;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void splice_backprop_kernel(
     const float *__restrict__ od, int64_t ods, float *__restrict__ id, int64_t ids,
     SpliceArgs a, int64_t total) {
@@ -628,6 +681,36 @@ int kn_stream_assemble(float *arena, MatrixDim arena_dim, const float *chunk, Ma
     hipLaunchKernelGGL(stream_assemble_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), arena,
                        (int64_t)arena_dim.stride, chunk, (int64_t)chunk_dim.stride, row_start,
                        desc, a, units);
+  return kcnn::launch_status();
+}
+
+int kn_stream_segments(const float *arena, MatrixDim arena_dim, float *map, MatrixDim map_dim,
+                       const int *desc, int num_segs, kcnn_stream_t st) {
+  const int cols = arena_dim.cols;
+  if (arena == nullptr || map == nullptr || desc == nullptr || num_segs <= 0 ||
+      arena_dim.rows <= 0 || map_dim.rows <= 0 || cols <= 0 || map_dim.cols != cols ||
+      arena_dim.stride < cols || map_dim.stride < cols)
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)arena_dim.rows * cols >= ((int64_t)1 << 31) ||
+      (int64_t)map_dim.rows * cols >= ((int64_t)1 << 31))
+    return (int)hipErrorInvalidValue;
+  const bool vec4 = cols % 4 == 0 && arena_dim.stride % 4 == 0 && map_dim.stride % 4 == 0 &&
+                    (uintptr_t)arena % 16 == 0 && (uintptr_t)map % 16 == 0;
+  const int units = cols / (vec4 ? 4 : 1);
+  SegmentArgs a;
+  a.num_segs = num_segs;
+  a.map_rows = map_dim.rows;
+  a.arena_rows = arena_dim.rows;
+  a.rpb = std::max(1, std::min(kRaggedMaxRows, 1024 / units));
+  a.div_units = FastDiv((uint32_t)units);
+  const int ngroups = (map_dim.rows + a.rpb - 1) / a.rpb;
+  const dim3 grid((unsigned)std::min(ngroups, kAssembleMaxBlocks));
+  if (vec4)
+    hipLaunchKernelGGL(stream_segments_kernel<4>, grid, dim3(256), 0, kcnn::as_stream(st), arena,
+                       (int64_t)arena_dim.stride, map, (int64_t)map_dim.stride, desc, a, units);
+  else
+    hipLaunchKernelGGL(stream_segments_kernel<1>, grid, dim3(256), 0, kcnn::as_stream(st), arena,
+                       (int64_t)arena_dim.stride, map, (int64_t)map_dim.stride, desc, a, units);
   return kcnn::launch_status();
 }
 

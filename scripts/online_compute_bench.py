@@ -27,6 +27,12 @@ scripts/compute_bench.py times its cases.  Prints one JSON line.
 library's own per-function hipEvent profile and prints it: the kernels of one
 step.  (Profiling synchronises around every scope: not a step time.)
 
+--share-time makes every computer with share_time=True (the leading Splice ->
+Convolution / Maxpool / ReLU components once per time step of the frames the
+slots hold), also under --kernels, and reports the largest
+difference of its log-likelihoods from the default computer's on the same
+steps.
+
   python scripts/online_compute_bench.py --steps 20 --warmup 3
 """
 import argparse
@@ -53,6 +59,7 @@ def main():
     ap.add_argument("--seed", type=int, default=20261020)
     ap.add_argument("--no-log", action="store_true")
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--share-time", action="store_true")
     ap.add_argument("--config", default=os.path.join(ROOT, "tests", "golden", "nnet.config"))
     ap.add_argument("--scales", default=os.path.join(ROOT, "tests", "golden",
                                                      "dropout_scale.config"))
@@ -84,6 +91,8 @@ def main():
     slots, num_new, final = list(range(n)), [c] * n, [False] * n
 
     def new_online():
+        if args.share_time:
+            return kcnn.OnlineComputer(net, n, c, share_time=True, **kw)
         return kcnn.OnlineComputer(net, n, c, **kw)
 
     def new_history():
@@ -110,6 +119,16 @@ def main():
         want = net.Compute(whole, [c * spr] * n, pad_input=False, **kw)
         streamed = torch.cat([torch.cat(g)[left:] for g in got])
         worst = float((streamed - want).abs().max())
+    worst_shared = None
+    if args.share_time:
+        assert oc.TimeSharedPrefix() > 0, "the plan declines this network"
+        own = kcnn.OnlineComputer(net, n, c, **kw)
+        worst_shared = 0.0
+        for k in range(spr):
+            out, _ = own.Accept(chunks[k], slots, num_new, final)
+            if out.shape[0]:
+                theirs = torch.cat([g[k] for g in got])
+                worst_shared = max(worst_shared, float((out - theirs).abs().max()))
 
     if args.kernels:
         oc = new_online()
@@ -123,7 +142,7 @@ def main():
         torch.cuda.synchronize()
         kcnn.set_profiling(False)
         print(f"per-function hipEvent profile of {args.steps} steady-state Accept steps "
-              f"({n} streams x {c} frames):")
+              f"({n} streams x {c} frames{', share_time' if args.share_time else ''}):")
         print(kcnn.profile_string())
         return 0
 
@@ -146,11 +165,13 @@ def main():
         "streams": n, "chunk": c, "steps_per_round": spr, "frames_per_round": frames,
         "left_context": left, "right_context": right, "seed": args.seed,
         "apply_log_and_priors": not args.no_log, "steps": args.steps, "warmup": args.warmup,
+        "share_time": args.share_time,
         **{name: summary(v) for name, v in ms.items()},
         **{"ms_per_step_" + name: round(float(np.median(v)) / spr, 4) for name, v in ms.items()},
         **{"frames_per_s_" + name: round(frames / (np.median(v) * 1e-3), 1)
            for name, v in ms.items()},
         "max_abs_diff_online_vs_unpadded_compute": worst,
+        "max_abs_diff_shared_vs_default_computer": worst_shared,
         "note": "host clock around one round (steps_per_round steps, one device synchronise); "
                 "each case in blocks of its own, twice over; compute_whole is one call a "
                 "round on the round's frames as whole utterances (ms_per_step is that call "
