@@ -501,51 +501,69 @@ int kcnn_nnet_compute(kcnn_nnet *n, const float *in, MatrixDim in_dim, const int
 /* kcnn_nnet_compute with the convolutional layers run once per time step
  * instead of once per window (opt-in; kcnn_nnet_compute is the default and the
  * yardstick).  For a stack that starts SpliceComponent -> {Convolution |
- * Maxpool | RectifiedLinear}..., every convolution 1-D along time (in-channel
- * 1 and kernel-height = in-height on the Splice, in-height 1 above; stride 1,
- * no padding, out-height 1) and every pool 1 x pw x pc, not overlapping and
- * dividing evenly, frames t and t + 1 share all but one column of each such
- * layer.  Those leading components (the prefix; kcnn_nnet_time_shared_prefix
- * of them) then run as TIME MAPS, one row per row of the input (with pad_input
- * laid out clamped, T + L + R rows an utterance) and one column per channel:
- * a convolution's taps as GEMMs of the library's engine on row-shifted views,
- * a pool as the reference's fold over dilated rows.  A level is (channels C,
- * positions n, dilation d): element (position k, channel c) of the window-
- * layout row of result frame t of utterance u, column k + c n, is row base_u +
- * t + d k, column c of the map, base_u the utterance's first input row.  A
- * gather then writes the output of component prefix - 1 in the window layout,
- * and from component prefix upwards the pass is kcnn_nnet_compute's own.
- * Same arguments, checks, errors (under this function's name), result layout
- * and state as kcnn_nnet_compute.  The values agree with kcnn_nnet_compute's
- * to the error bar of the GEMMs (both are fp32-exact products under the same
- * bar), not to the bit: the sums are taken in another order.  Afterwards
- * kcnn_nnet_output(n, i) fails for i in [0, prefix - 2] -- those activations
- * are never formed -- and kcnn_nnet_time_map gives the maps.  When the prefix
- * is 0 this IS kcnn_nnet_compute (the same bits).  Not offered for the
- * streaming computer. */
+ * Maxpool | RectifiedLinear}..., every column of a window's convolution output
+ * is a function of the frames under that column alone, so frames t and t + 1
+ * share all but one column of each such layer.  Those leading components (the
+ * prefix; kcnn_nnet_time_shared_prefix of them) then run as TIME MAPS, one row
+ * per row of the input (with pad_input laid out clamped, T + L + R rows an
+ * utterance).  A level is (channels C, height H, positions n, dilation d): a
+ * map row holds H C floats, element (h, c) at column h + c H, and element
+ * (h, position k, channel c) of the window-layout row of result frame t of
+ * utterance u, column h + k H + c H n, is row base_u + t + d k, column h + c H
+ * of the map, base_u the utterance's first input row.  Level 0, the Splice's
+ * output, is (1, input-dim, L + R + 1, 1).  Covered:
+ *   - a Convolution of its level's geometry (in-channel C, in-height H,
+ *     in-width n) with stride 1 and no padding, kernel-height <= H and
+ *     kernel-width <= n: (group, H - kh + 1, n - kw + 1, d).  Along time alone
+ *     (the whole frame on the Splice, H = 1 above) its taps are GEMMs of the
+ *     library's engine on row-shifted views; along frequency too (kh < H, or a
+ *     level with H > 1 below) it is one implicit GEMM over (tap, channel,
+ *     kernel row) on the bf16 matrix cores;
+ *   - a Maxpool ph x pw x pc of its level's geometry, not overlapping and
+ *     dividing evenly: (C / pc, H / ph, n / pw, d pw), the reference's fold
+ *     over channels, dilated rows and heights;
+ *   - a RectifiedLinear of dim C H n.
+ * A gather then writes the output of component prefix - 1 in the window
+ * layout, and from component prefix upwards the pass is kcnn_nnet_compute's
+ * own.  Same arguments, checks, errors (under this function's name), result
+ * layout and state as kcnn_nnet_compute.  The values agree with
+ * kcnn_nnet_compute's to the error bar of the GEMMs (both are fp32-exact
+ * products under the same bar), not to the bit: the sums are taken in another
+ * order.  Afterwards kcnn_nnet_output(n, i) fails for i in [0, prefix - 2] --
+ * those activations are never formed -- and kcnn_nnet_time_map gives the maps.
+ * When the prefix is 0 this IS kcnn_nnet_compute (the same bits). */
 int kcnn_nnet_compute_shared(kcnn_nnet *n, const float *in, MatrixDim in_dim,
                              const int32_t *lengths, int num_utts, int pad_input,
                              const float *priors, int num_priors, float prior_scale,
                              int apply_log, const float **data, MatrixDim *dim);
 /* The number of leading components kcnn_nnet_compute_shared runs as time maps
- * (14 for nnet.config, 4 for train_conv.config), 0 when it would run
- * kcnn_nnet_compute instead: component 0 is not a SpliceComponent with a
- * contiguous context and const-component-dim = 0, component 1 is not a
- * Convolution, a Convolution or Maxpool of the run is not of the shape above,
+ * (14 for nnet.config, 4 for train_conv.config and for freq_conv.config), 0
+ * when it would run kcnn_nnet_compute instead: component 0 is not a
+ * SpliceComponent with a contiguous context and const-component-dim = 0, no
+ * Convolution follows it before another kind of component (a pool or a ReLU
+ * of the Splice's output itself has no prefix), a Convolution or Maxpool of
+ * the run is not of the shape above (in-pad-height or in-pad-width set, a
+ * stride, in-channel != 1 on the Splice, a geometry that is not its level's,
+ * an overlapping or uneven pool, more filters or rows than one launch takes),
  * a component above component 0 has a context of its own, or
  * kcnn_set_literal_path(1) is in force.  Touches no device. */
 int kcnn_nnet_time_shared_prefix(const kcnn_nnet *n);
 /* Level `level` in [0, prefix) of the last kcnn_nnet_compute_shared (level i
  * is the output of component i; level 0 the input, clamped when padded): a
  * borrowed device view *data / *dim of its computed rows -- all of level 0's,
- * fewer above by the taps' reach -- of *channels columns (level 0: channels =
- * 1 and dim->cols = InputDim), with the level's positions and dilation.  Rows
+ * fewer above by the taps' reach -- of *channels channels (dim->cols is the
+ * level's height times *channels, kcnn_nnet_time_map_height; level 0: channels
+ * = 1 and dim->cols = InputDim), with the level's positions and dilation.  Rows
  * whose taps cross from one utterance into the next are computed and read by
  * nothing.  Valid until the next forward call; an error when the last forward
  * call was not a kcnn_nnet_compute_shared over time maps.  For tests and
  * debugging. */
 int kcnn_nnet_time_map(const kcnn_nnet *n, int level, const float **data, MatrixDim *dim,
                        int *channels, int *positions, int *dilation);
+/* The height H of that level: dim->cols of kcnn_nnet_time_map is H *channels,
+ * element (h, c) at column h + c H (level 0: H = InputDim, one channel; 1 for
+ * a level without a frequency axis).  The same errors. */
+int kcnn_nnet_time_map_height(const kcnn_nnet *n, int level, int *height);
 
 /* ---- training from a corpus that stays on the device --------------------- */
 /* What nnet-get-egs and nnet-shuffle-egs do for nnet-train, without the

@@ -934,7 +934,8 @@ class Nnet:
     def TimeMap(self, level):
         """Level `level` of the last Compute(share_time=True)
         (kcnn_nnet_time_map): (torch view of its computed rows, one per input
-        row, by channels; channels; positions; dilation).  Valid until the
+        row, by height * channels (TimeMapHeight); channels; positions;
+        dilation).  Valid until the
         next forward call; for tests and debugging."""
         p = ctypes.c_void_p()
         d = MatrixDim()
@@ -942,6 +943,14 @@ class Nnet:
         check(lib().kcnn_nnet_time_map(self._h, int(level), ctypes.byref(p), ctypes.byref(d),
                                        ctypes.byref(c), ctypes.byref(n), ctypes.byref(dil)))
         return _device_view(p.value, d), c.value, n.value, dil.value
+
+    def TimeMapHeight(self, level):
+        """The height H of that level (kcnn_nnet_time_map_height): a row of
+        TimeMap(level)'s view holds H * channels floats, element (h, c) at
+        column h + c * H; 1 for a level without a frequency axis."""
+        h = ctypes.c_int()
+        check(lib().kcnn_nnet_time_map_height(self._h, int(level), ctypes.byref(h)))
+        return h.value
 
     def Compute(self, feats, lengths=None, pad_input=True, priors=None, prior_scale=1.0,
                 apply_log=False, share_time=False):
@@ -957,7 +966,8 @@ class Nnet:
         valid until the next forward call; changes nothing in the network and
         does not synchronise; Backprop* raise until the next Propagate.
         share_time (kcnn_nnet_compute_shared): the leading Splice ->
-        {Convolution | Maxpool | ReLU}... components run once per time step
+        {Convolution | Maxpool | ReLU}... components (convolutions along time,
+        along frequency or both; stride 1, no padding) run once per time step
         instead of once per window -- the same values to the error bar of the
         GEMMs, not the same bits; Output(i) of those components but the last
         then raises, TimeMap gives their maps.  A network this does not cover

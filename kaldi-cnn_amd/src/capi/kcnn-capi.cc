@@ -842,6 +842,12 @@ int kcnn_nnet_time_map(const kcnn_nnet *n, int level, const float **data, Matrix
     *dilation = m.dilation;
   });
 }
+int kcnn_nnet_time_map_height(const kcnn_nnet *n, int level, int *height) {
+  return guard([&] {
+    if (height == nullptr) KALDI_ERR << "kcnn_nnet_time_map_height: no result pointer";
+    *height = n->stack.TimeMap(level).height;
+  });
+}
 
 // ---- training from a device-resident corpus ----------------------------------------
 kcnn_corpus *kcnn_corpus_new(const float *feats, MatrixDim dim, const int32_t *lengths,

@@ -964,7 +964,7 @@ TimePlan NnetStack::TimeSharedPlan() const {
       t.kind = TimeComp::kRelu;
     }
   }
-  return make_time_plan(desc, cnsl::nnet0::LiteralPath());
+  return make_time_plan(desc, cnsl::nnet0::LiteralPath(), true);
 }
 
 NnetStack::TimeMapInfo NnetStack::TimeMap(int level) const {
@@ -994,6 +994,7 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     v.channels = lev.channels;
     v.positions = lev.positions;
     v.dilation = lev.dilation;
+    v.height = lev.height;
   };
   // a level's own map, sized as Compute sizes its outputs: without the fill
   auto map_of = [&](int l) -> CuMatrix<BaseFloat> & {
@@ -1015,6 +1016,21 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     const TimeLevel &lev = plan.levels[l], &below = plan.levels[l - 1];
     const TimeMapInfo in = time_views_[l - 1];
     const int nrows = (int)rows.computed[l];
+    if (lev.kind == TimeComp::kConv && time_level_2d(plan, l)) {
+      // a filter shorter than its input is high, or a level with a height below
+      cnsl::nnet0::ConvolutionComponent *conv = comps_[l].conv;
+      const CuMatrix<BaseFloat> &W = conv->LinearParams();
+      CuMatrix<BaseFloat> &m = map_of(l);
+      MatrixDim in_rows = in.dim;
+      in_rows.rows = (int)rows.computed[l - 1];
+      CuProfileScope prof("kn_timemap_conv2d");
+      CNSL_SAFE_CALL(kn_timemap_conv2d(in.data, in_rows, W.Data(), W.Dim(),
+                                       conv->BiasParams().Data(), m.Data(), m.Dim(), nrows,
+                                       below.height, below.channels,
+                                       below.height - lev.height + 1, lev.taps, below.dilation,
+                                       0, st));
+      continue;
+    }
     if (lev.kind == TimeComp::kConv) {
       // tap d: map'[rows] (+)= map[rows + delta d] W_d, GEMMs of the matrix layer
       cnsl::nnet0::ConvolutionComponent *conv = comps_[l].conv;
@@ -1048,6 +1064,16 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     in_rows.rows = (int)rows.computed[l - 1];
     CuMatrix<BaseFloat> &m = map_of(l);
     CuMatrix<BaseFloat> *act = both ? &map_of(l + 1) : (pool ? nullptr : &m);
+    if (pool && time_level_2d(plan, l)) {
+      CuProfileScope prof("kn_timemap_pool2d");
+      CNSL_SAFE_CALL(kn_timemap_pool2d(in.data, in_rows, m.Data(), m.Dim(),
+                                       act ? act->Data() : nullptr,
+                                       act ? act->Dim() : MatrixDim{0, 0, 0}, nrows,
+                                       below.height, lev.pool_height, lev.taps,
+                                       lev.pool_channel, below.dilation, st));
+      if (both) l++;
+      continue;
+    }
     CuProfileScope prof("kn_timemap_epilogue");
     CNSL_SAFE_CALL(kn_timemap_epilogue(
         in.data, in_rows, pool ? m.Data() : nullptr, pool ? m.Dim() : MatrixDim{0, 0, 0},
@@ -1057,11 +1083,19 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
   }
   const TimeLevel &top = plan.levels[p - 1];
   CuMatrix<BaseFloat> &y = out(p - 1).value;
-  KALDI_ASSERT(comps_[p - 1].c->OutputDim() == top.channels * top.positions);
-  if (y.NumRows() != total || y.NumCols() != top.channels * top.positions)
-    y.Resize(total, top.channels * top.positions, kUndefined);  // written whole
+  const int top_dim = top.width * top.positions;
+  KALDI_ASSERT(comps_[p - 1].c->OutputDim() == top_dim);
+  if (y.NumRows() != total || y.NumCols() != top_dim)
+    y.Resize(total, top_dim, kUndefined);  // written whole
   MatrixDim map_dim = time_views_[p - 1].dim;
   map_dim.rows = (int)rows.computed[p - 1];
+  if (top.height > 1) {
+    CuProfileScope prof("kn_timemap_gather2d");
+    CNSL_SAFE_CALL(kn_timemap_gather2d(time_views_[p - 1].data, map_dim, y.Data(), y.Dim(),
+                                       utt_start, num_utts, context, top.height, top.positions,
+                                       top.dilation, st));
+    return;
+  }
   CuProfileScope prof("kn_timemap_gather");
   CNSL_SAFE_CALL(kn_timemap_gather(time_views_[p - 1].data, map_dim, y.Data(), y.Dim(), utt_start,
                                    num_utts, context, top.positions, top.dilation, st));

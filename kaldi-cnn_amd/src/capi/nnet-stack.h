@@ -184,7 +184,11 @@ class NnetStack {
   // pools and ReLUs one pass each (kn_timemap_epilogue) -- and a gather
   // (kn_timemap_gather) then writes Output(prefix - 1) in the window layout
   // Compute gives it; from component `prefix` upwards the pass is Compute's
-  // own.  Same arguments, checks, result and state as Compute; to the error
+  // own.  A level may keep a height (frequency) axis H, its map row H C
+  // floats (time-plan.h): a Convolution with kernel-height < in-height, or on
+  // such a level, is one kn_timemap_conv2d, a Maxpool on one kn_timemap_pool2d
+  // and the gather kn_timemap_gather2d (nnet2/nnet-timemap-2d.hip).
+  // Same arguments, checks, result and state as Compute; to the error
   // bar of the GEMMs, not the bits, the same values.  Output(i) below prefix -
   // 1 throws afterwards (those activations are never formed); TimeMap gives
   // the maps.  A stack the plan declines runs Compute itself.
@@ -203,6 +207,7 @@ class NnetStack {
     const float *data = nullptr;
     MatrixDim dim = {0, 0, 0};
     int channels = 0, positions = 0, dilation = 0;
+    int height = 1;  // dim.cols = height channels, element (h, c) at column h + c height
   };
   TimeMapInfo TimeMap(int level) const;
 

@@ -149,6 +149,22 @@ const CuMatrix<BaseFloat> &OnlineComputer::AcceptShared(const TimePlan &plan,
     const int nrows = (int)rows.computed[l];
     const bool relu_next = l + 1 < p && plan.levels[l + 1].kind == TimeComp::kRelu;
     MatrixDim out_dim;
+    if (lev.kind == TimeComp::kConv && time_level_2d(plan, l)) {
+      // a filter shorter than its input is high, or a level with a height below
+      cnsl::nnet0::ConvolutionComponent *conv = net_->ConvAt(l);
+      KALDI_ASSERT(conv != nullptr);
+      const CuMatrix<BaseFloat> &W = conv->LinearParams();
+      float *m = map_of(relu_next ? l + 1 : l, &out_dim);
+      CuProfileScope prof("kn_timemap_conv2d");
+      CNSL_SAFE_CALL(kn_timemap_conv2d(in, in_dim, W.Data(), W.Dim(), conv->BiasParams().Data(),
+                                       m, out_dim, nrows, below.height, below.channels,
+                                       below.height - lev.height + 1, lev.taps, below.dilation,
+                                       relu_next ? 1 : 0, st));
+      in = m;
+      in_dim = out_dim;
+      if (relu_next) l++;
+      continue;
+    }
     if (lev.kind == TimeComp::kConv) {
       cnsl::nnet0::ConvolutionComponent *conv = net_->ConvAt(l);
       KALDI_ASSERT(conv != nullptr);
@@ -174,11 +190,18 @@ const CuMatrix<BaseFloat> &OnlineComputer::AcceptShared(const TimePlan &plan,
     float *m = map_of(l, &out_dim);
     float *act = both ? map_of(l + 1, &act_dim) : nullptr;
     if (!pool) { act = m; act_dim = out_dim; }
-    CuProfileScope prof("kn_timemap_epilogue");
-    CNSL_SAFE_CALL(kn_timemap_epilogue(in, in_dim, pool ? m : nullptr,
-                                       pool ? out_dim : MatrixDim{0, 0, 0}, act, act_dim, nrows,
-                                       pool ? lev.taps : 1, pool ? lev.pool_channel : 1,
-                                       below.dilation, st));
+    if (pool && time_level_2d(plan, l)) {
+      CuProfileScope prof("kn_timemap_pool2d");
+      CNSL_SAFE_CALL(kn_timemap_pool2d(in, in_dim, m, out_dim, act, act_dim, nrows,
+                                       below.height, lev.pool_height, lev.taps,
+                                       lev.pool_channel, below.dilation, st));
+    } else {
+      CuProfileScope prof("kn_timemap_epilogue");
+      CNSL_SAFE_CALL(kn_timemap_epilogue(in, in_dim, pool ? m : nullptr,
+                                         pool ? out_dim : MatrixDim{0, 0, 0}, act, act_dim,
+                                         nrows, pool ? lev.taps : 1,
+                                         pool ? lev.pool_channel : 1, below.dilation, st));
+    }
     in = both || !pool ? act : m;
     in_dim = both || !pool ? act_dim : out_dim;
     if (both) l++;
@@ -186,8 +209,12 @@ const CuMatrix<BaseFloat> &OnlineComputer::AcceptShared(const TimePlan &plan,
   const TimeLevel &top = plan.levels[p - 1];
   const int context = plan.levels[0].positions - 1;
   CuMatrix<BaseFloat> &y = net_->ExamplesInput(p, segs.out_rows);
-  KALDI_ASSERT(y.NumCols() == top.channels * top.positions && y.NumRows() == segs.out_rows);
-  {
+  KALDI_ASSERT(y.NumCols() == top.width * top.positions && y.NumRows() == segs.out_rows);
+  if (top.height > 1) {
+    CuProfileScope prof("kn_timemap_gather2d");
+    CNSL_SAFE_CALL(kn_timemap_gather2d(in, in_dim, y.Data(), y.Dim(), d_out_start, segs.num,
+                                       context, top.height, top.positions, top.dilation, st));
+  } else {
     CuProfileScope prof("kn_timemap_gather");
     CNSL_SAFE_CALL(kn_timemap_gather(in, in_dim, y.Data(), y.Dim(), d_out_start, segs.num,
                                      context, top.positions, top.dilation, st));

@@ -26,6 +26,20 @@
 // one utterance into the next are computed and never read: utterance u's
 // windows read its rows [base_u, base_u + F_u + delta (n - 1)) only (F_u its
 // result frames), and delta (n - 1) never grows from level to level.
+//
+// With height maps (make_time_plan's third parameter; NnetStack::TimeSharedPlan
+// sets it) a level is (C, H, n, delta): a map row keeps a frequency axis of H
+// floats a channel, `width` = H C floats with element (h, c) at column h + c
+// H; the window-layout element (h, k, c) is at column h + k H + c H n
+// (conv-geom.h: h + w H + c H W) and is map[base_u + t + delta k][h + c H].
+// Level 0 is (1, input-dim, L + R + 1, 1); with H = 1 everything is as above.
+//   Convolution kh x kw on (C, H, n, delta), stride 1, no padding: (G, H - kh
+//     + 1, n - kw + 1, delta);
+//     map'[s][oh + g OH] = b[g] + sum_{d, c, i} map[s + delta d][oh + i + c H]
+//                                               W[i + d kh + c kh kw][g]
+//   Maxpool ph x pw x pc, not overlapping: (C / pc, H / ph, n / pw, delta pw);
+//     map'[s][oh + oc H'] folds map[s + delta w][oh ph + h + (oc pc + c) H]
+//     over c (outer), w, h (inner)
 #ifndef KCNN_CAPI_TIME_PLAN_H_
 #define KCNN_CAPI_TIME_PLAN_H_
 
@@ -40,6 +54,10 @@ namespace kcnn {
 constexpr int64_t kTimeRowLimit = (int64_t)1 << 31;  // rows of a matrix
 // positions per window the gather stages for one channel (its LDS tile)
 constexpr int kTimeMaxPositions = 8192;
+// filters of a height-map Convolution (kn_timemap_conv2d: 32 a block on grid y)
+constexpr int kTimeMaxGroup2d = 65535 * 32;
+// (row, height) pairs of one height map: a 32-bit index in the kernels
+constexpr int64_t kTimeMaxRowHeights = ((int64_t)1 << 31) - 1;
 
 // What the plan reads of a component (NnetStack fills it from the component).
 struct TimeComp {
@@ -64,11 +82,13 @@ struct TimeComp {
 struct TimeLevel {
   TimeComp::Kind kind;
   int channels, positions, dilation;  // (C, n, delta) of this level's map
-  int width;                          // floats a map row holds: C, input-dim at level 0
+  int width;                          // floats a map row holds: H C, input-dim at level 0
   int taps;                           // kw of a Convolution, pw of a Maxpool, else 1
   int pool_channel;                   // pc of a Maxpool, else 1
   int reach;                          // rows past its own that a row reads below: delta_in (taps - 1)
   int sum_reach;                      // the reaches of levels 1 .. this one
+  int height = 1;                     // H: the frequency axis of a map row (height maps)
+  int pool_height = 1;                // ph of a Maxpool, else 1
 };
 
 struct TimePlan {
@@ -78,7 +98,10 @@ struct TimePlan {
   int prefix() const { return (int)levels.size(); }
 };
 
-inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_path) {
+// height_maps: levels may keep a height (frequency) axis; without it a plan
+// covers 1-D convolutions along time only, as before height maps existed.
+inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_path,
+                               bool height_maps = false) {
   TimePlan plan;
   std::ostringstream why;
   auto decline = [&]() {
@@ -117,6 +140,7 @@ inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_
   cur.width = sp.input_dim;
   cur.taps = cur.pool_channel = 1;
   cur.reach = cur.sum_reach = 0;
+  cur.height = sp.input_dim;
   plan.levels.push_back(cur);
   bool conv_seen = false;
   for (size_t i = 1; i < comps.size(); i++) {
@@ -124,8 +148,52 @@ inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_
     const TimeLevel in = plan.levels.back();
     TimeLevel out = in;
     out.kind = c.kind;
-    out.taps = out.pool_channel = 1;
-    if (c.kind == TimeComp::kConv) {
+    out.taps = out.pool_channel = out.pool_height = 1;
+    if (c.kind == TimeComp::kConv && height_maps) {
+      if (c.pad_height != 0 || c.pad_width != 0) {
+        why << "Convolution " << i << " has in-pad-height or in-pad-width set";
+        return decline();
+      }
+      if (c.in_channel != in.channels || c.in_height != in.height ||
+          c.in_width != in.positions || c.stride != 1 || c.kernel_height < 1 ||
+          c.kernel_height > c.in_height || c.kernel_width < 1 || c.kernel_width > c.in_width ||
+          c.out_height != c.in_height - c.kernel_height + 1 ||
+          c.out_width != c.in_width - c.kernel_width + 1 || c.group < 1) {
+        why << "Convolution " << i << " is not an unpadded stride-1 convolution of its input ("
+            << in.channels << " channels, height " << in.height << ", " << in.positions
+            << " positions)";
+        return decline();
+      }
+      if (c.group > kTimeMaxGroup2d || (int64_t)c.group * c.out_height >= kTimeRowLimit) {
+        why << "Convolution " << i << " has " << c.group << " filters of height " << c.out_height;
+        return decline();
+      }
+      out.channels = c.group;
+      out.height = c.out_height;
+      out.width = c.group * c.out_height;
+      out.positions = c.out_width;
+      out.taps = c.kernel_width;
+      conv_seen = true;
+    } else if (c.kind == TimeComp::kPool && height_maps) {
+      if (!conv_seen) break;  // (a pool of the Splice output itself: no prefix)
+      if (c.overlap || c.pool_height < 1 || c.pool_width < 1 || c.pool_channel < 1 ||
+          c.in_height != in.height || c.in_width != in.positions ||
+          c.in_channel != in.channels || c.in_height % c.pool_height != 0 ||
+          c.in_width % c.pool_width != 0 || c.in_channel % c.pool_channel != 0) {
+        why << "Maxpool " << i << " is overlapping or does not divide its input ("
+            << in.channels << " channels, height " << in.height << ", " << in.positions
+            << " positions) evenly";
+        return decline();
+      }
+      out.channels = in.channels / c.pool_channel;
+      out.height = in.height / c.pool_height;
+      out.width = out.channels * out.height;
+      out.positions = in.positions / c.pool_width;
+      out.dilation = in.dilation * c.pool_width;
+      out.taps = c.pool_width;
+      out.pool_channel = c.pool_channel;
+      out.pool_height = c.pool_height;
+    } else if (c.kind == TimeComp::kConv) {
       const bool first = in.kind == TimeComp::kSplice;
       // directly on the Splice a filter spans the whole frame; above, one row
       const int height = first ? in.width : 1, chans = first ? 1 : in.channels;
@@ -138,6 +206,7 @@ inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_
         return decline();
       }
       out.channels = out.width = c.group;
+      out.height = 1;
       out.positions = c.out_width;
       out.taps = c.kernel_width;
       conv_seen = true;
@@ -157,7 +226,8 @@ inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_
       out.pool_channel = c.pool_channel;
     } else if (c.kind == TimeComp::kRelu) {
       if (!conv_seen) break;
-      if (c.input_dim != in.channels * in.positions) break;  // (the stack checks dimensions)
+      // (the stack checks dimensions)
+      if ((int64_t)c.input_dim != (int64_t)in.channels * in.height * in.positions) break;
     } else {
       break;
     }
@@ -170,6 +240,17 @@ inline TimePlan make_time_plan(const std::vector<TimeComp> &comps, bool literal_
     return decline();
   }
   return plan;
+}
+
+// Whether level l (> 0) of a plan runs on the height-map kernels
+// (kn_timemap_conv2d, kn_timemap_pool2d): its input keeps a height, and it is
+// not the Splice's full-frame convolution, which contracts a whole map row a
+// tap as a 1-D level does.  A ReLU is element-wise on H C columns either way.
+inline bool time_level_2d(const TimePlan &plan, int l) {
+  const TimeLevel &lev = plan.levels[(size_t)l], &below = plan.levels[(size_t)l - 1];
+  if (lev.kind == TimeComp::kConv)
+    return below.kind == TimeComp::kSplice ? lev.height > 1 : below.height > 1;
+  return lev.kind == TimeComp::kPool && below.height > 1;
 }
 
 // The rows of one pass: utterance u has len[u] input frames and, with L + R =
@@ -217,6 +298,12 @@ inline std::string plan_time_rows(const TimePlan &plan, const int32_t *lengths, 
     if (computed < 1 || span > context ||
         r.base.back() + r.frames.back() - 1 + span > computed - 1) {
       err << "level " << l << " computes " << computed << " rows, fewer than its windows read";
+      return err.str();
+    }
+    // (level 0 is indexed by rows alone)
+    if (l > 0 && computed * lev.height > kTimeMaxRowHeights) {
+      err << "level " << l << " has " << computed << " rows of height " << lev.height
+          << ": too many";
       return err.str();
     }
     r.computed.push_back(computed);

@@ -299,6 +299,58 @@ int kn_timemap_conv(const float *in, MatrixDim in_dim, const float *w, MatrixDim
                     const float *bias, float *out, MatrixDim out_dim, int rows, int kernel_width,
                     int delta, int wc, int wd, int relu, kcnn_stream_t st);
 
+/* ---- nnet-timemap-2d.hip: time maps that keep a height (frequency) axis ---- */
+
+/* A map row of such a level (capi/time-plan.h, (C, H, n, delta)) holds H C
+ * floats, element (h, c) at column h + c H.  The most (row, height) pairs of
+ * one map: a 32-bit index in the kernels. */
+#define KN_TIMEMAP_MAX_ROW_HEIGHTS 2147483647
+
+/* A Convolution level, kernel_height <= height:
+ *   out(s, oh + g OH) = act(bias[g] + sum_{d < kernel_width} sum_{c < channels}
+ *       sum_{i < kernel_height} in(s + delta d, oh + i + c height)
+ *                               * w(i + d kernel_height + c kernel_height kernel_width, g))
+ * for s < rows, oh < OH = height - kernel_height + 1, g < group = w_dim.cols,
+ * w the component's LinearParams() read as fp32.  act: the identity, or with
+ * relu != 0 x < 0 -> 0 (NaN and -0 stay).  An implicit GEMM, M = (s, oh), N =
+ * g, K = (d, c, i): bf16x6 products (x6::mfma6 on the truncating three-way
+ * split of both operands, made in the kernel on every call; no statistics
+ * pass), fp32 accumulation in a fixed order, the bias added in fp32 at the
+ * store.  Any sizes >= 1 and any strides >= the columns, up to
+ * KN_TIMEMAP_MAX_ROW_HEIGHTS for rows OH and 65535 * 32 filters.  Refused with
+ * hipErrorInvalidValue before any launch: null operands, a highest tap rows -
+ * 1 + delta (kernel_width - 1) that is not a row of `in`, a highest weight
+ * row kernel_width channels kernel_height - 1 that is not one of `w`,
+ * in_dim.cols < height channels, out_dim.cols != OH group, out_dim.rows <
+ * rows. */
+int kn_timemap_conv2d(const float *in, MatrixDim in_dim, const float *w, MatrixDim w_dim,
+                      const float *bias, float *out, MatrixDim out_dim, int rows, int height,
+                      int channels, int kernel_height, int kernel_width, int delta, int relu,
+                      kcnn_stream_t st);
+
+/* A MaxpoolComponent pool_height x pool_width x pool_channel level, not
+ * overlapping, on a map of in_dim.cols = height C columns (pool_height |
+ * height, pool_channel | C): with H' = height / pool_height,
+ * pooled(s, oh + oc H') is the reference's fold (start -1e20f, replace when v
+ * < x) over c < pool_channel (outer), w < pool_width, h < pool_height (inner)
+ * of in(s + delta w, oh pool_height + h + (oc pool_channel + c) height), for s
+ * < rows; in_dim.rows must hold the last row's highest tap.  With relu !=
+ * NULL also RectifiedLinearComponent::Propagate (x < 0 -> 0) of the pooled
+ * values to relu(s, .): the pool level and the ReLU level from one read. */
+int kn_timemap_pool2d(const float *in, MatrixDim in_dim, float *pooled, MatrixDim p_dim,
+                      float *relu, MatrixDim r_dim, int rows, int height, int pool_height,
+                      int pool_width, int pool_channel, int delta, kcnn_stream_t st);
+
+/* The window layout of the last time map when it keeps a height: out(r, h + k
+ * height + c height positions) = map(r + u ext + dilation k, h + c height)
+ * for result row r of utterance u, k < positions, h < height, c <
+ * map_dim.cols / height; utt_start, ext and the clamping of a source row into
+ * the map as for kn_timemap_gather.  The output is written contiguously, the
+ * map read in runs of `height` floats; no limit on positions. */
+int kn_timemap_gather2d(const float *map, MatrixDim map_dim, float *out, MatrixDim out_dim,
+                        const int *utt_start, int num_utts, int ext, int height, int positions,
+                        int dilation, kcnn_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif

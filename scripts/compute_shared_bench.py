@@ -16,7 +16,13 @@ tests/test_gpu_compute_shared.py (E the 1e-5 S bar of each convolution
 propagated in fp64 through the time maps, here on the device), and the
 log-likelihoods and the posteriors by their largest difference; and reports the
 activation floats below the first FC of either pass from the buffer sizes.
---no-check leaves the comparison out (a run under rocprofv3).
+--no-check leaves the comparison out (a run under rocprofv3).  --kernels
+instead runs --steps warm calls under the library's own per-function hipEvent
+profile and prints it: the kernels of one call.  (Profiling synchronises around
+every scope: not a call time.)
+
+--config takes any network the plan covers, tests/golden/freq_conv.config (a
+convolution along frequency: levels that keep a height) among them.
 """
 import argparse
 import json
@@ -42,6 +48,7 @@ def error_bar(net, torch, lengths, prefix):
     base = np.cumsum([0] + [t + context for t in lengths[:-1]])
     start = np.cumsum([0] + list(lengths[:-1]))
     views = [net.TimeMap(lvl) for lvl in range(prefix)]
+    heights = [net.TimeMapHeight(lvl) for lvl in range(prefix)]
     err = torch.zeros(views[0][0].shape, dtype=torch.float64, device="cuda")
     for lvl in range(1, prefix):
         comp = net.components[lvl]
@@ -49,7 +56,24 @@ def error_bar(net, torch, lengths, prefix):
         d_in = views[lvl - 1][3]
         rows = views[lvl][0].shape[0]
         kind = comp.Type()
-        if kind == "ConvolutionComponent":
+        tall = heights[lvl] > 1 or (lvl > 1 and heights[lvl - 1] > 1)
+        if kind == "ConvolutionComponent" and tall:
+            # a level that keeps a height: column oh + g OH, weight row i + d kh + c kh kw
+            w = comp.LinearParams().double().abs()
+            h_in, c_in, oh = heights[lvl - 1], views[lvl - 1][1], heights[lvl]
+            kh, g = h_in - oh + 1, w.shape[1]
+            kw = w.shape[0] // (kh * c_in)
+            s = comp.BiasParams().double().abs()[None, :, None].repeat(rows, 1, oh)
+            e = torch.zeros_like(s)
+            for c in range(c_in):
+                for d in range(kw):
+                    for i in range(kh):
+                        wr = w[i + d * kh + c * kh * kw][None, :, None]
+                        cols = slice(i + c * h_in, i + c * h_in + oh)
+                        s += a[d_in * d:d_in * d + rows, cols].abs()[:, None, :] * wr
+                        e += err[d_in * d:d_in * d + rows, cols][:, None, :] * wr
+            err = (e + RTOL * s).reshape(rows, g * oh)
+        elif kind == "ConvolutionComponent":
             w = comp.LinearParams().double().abs()
             width = a.shape[1]
             kw = w.shape[0] // width
@@ -60,6 +84,13 @@ def error_bar(net, torch, lengths, prefix):
                 s += a[d_in * d:d_in * d + rows].abs() @ wd
                 e += err[d_in * d:d_in * d + rows] @ wd
             err = e + RTOL * s
+        elif kind == "MaxpoolComponent" and heights[lvl - 1] > 1:
+            h_in, c_in, c_out = heights[lvl - 1], views[lvl - 1][1], views[lvl][1]
+            ph, pc, pw = h_in // heights[lvl], c_in // c_out, views[lvl][3] // d_in
+            e3 = err.reshape(err.shape[0], c_in, h_in)
+            err = torch.stack([e3[d_in * w:d_in * w + rows, c::pc, h::ph]
+                               for c in range(pc) for w in range(pw)
+                               for h in range(ph)]).amax(dim=0).reshape(rows, -1)
         elif kind == "MaxpoolComponent":
             c_out = views[lvl][1]
             pc = a.shape[1] // c_out
@@ -69,11 +100,12 @@ def error_bar(net, torch, lengths, prefix):
         else:
             err = err[:rows]
     _, c, n, d = views[-1]
-    bar = torch.empty((sum(lengths), c * n), dtype=torch.float64, device="cuda")
+    h = heights[-1]  # window layout: column h + k H + c H n
+    bar = torch.empty((sum(lengths), c, n, h), dtype=torch.float64, device="cuda")
     for b, s0, t in zip(base, start, lengths):
         for k in range(n):
-            bar[s0:s0 + t, k::n] = err[b + d * k:b + d * k + t]
-    return 2.0 * bar
+            bar[s0:s0 + t, :, k, :] = err[b + d * k:b + d * k + t].reshape(t, c, h)
+    return 2.0 * bar.reshape(sum(lengths), c * n * h)
 
 
 def main():
@@ -86,6 +118,7 @@ def main():
     ap.add_argument("--max-frames", type=int, default=600)
     ap.add_argument("--seed", type=int, default=20261020)
     ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--config", default=os.path.join(ROOT, "tests", "golden", "nnet.config"))
     ap.add_argument("--scales", default=os.path.join(ROOT, "tests", "golden",
                                                      "dropout_scale.config"))
@@ -113,6 +146,21 @@ def main():
     shared = args.which == "shared"
     if shared:
         kw["share_time"] = True
+
+    if args.kernels:
+        for _ in range(args.warmup):
+            net.Compute(x, lengths, **kw)
+        torch.cuda.synchronize()
+        kcnn.reset_profile()
+        kcnn.set_profiling(True)
+        for _ in range(args.steps):
+            net.Compute(x, lengths, **kw)
+        torch.cuda.synchronize()
+        kcnn.set_profiling(False)
+        print(f"per-function hipEvent profile of {args.steps} warm calls (--pass {args.which}, "
+              f"{len(lengths)} utterances, {frames} frames):")
+        print(kcnn.profile_string())
+        return 0
 
     ms = []
     for k in range(args.warmup + args.steps):
