@@ -984,25 +984,10 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
                                     bool pad_input, const TimePlan &plan, const TimeRows &rows) {
   const int p = plan.prefix();
   const int context = plan.levels[0].positions - 1;
-  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
   time_views_.assign((size_t)p, TimeMapInfo());
   auto view_of = [&](int l, const float *data, MatrixDim dim) {
     const TimeLevel &lev = plan.levels[l];
-    TimeMapInfo &v = time_views_[l];
-    v.data = data;
-    v.dim = dim;
-    v.channels = lev.channels;
-    v.positions = lev.positions;
-    v.dilation = lev.dilation;
-    v.height = lev.height;
-  };
-  // a level's own map, sized as Compute sizes its outputs: without the fill
-  auto map_of = [&](int l) -> CuMatrix<BaseFloat> & {
-    CuMatrix<BaseFloat> &m = time_maps_[l];
-    const int r = (int)rows.computed[l], c = plan.levels[l].width;
-    if (m.NumRows() != r || m.NumCols() != c) m.Resize(r, c, kUndefined);
-    view_of(l, m.Data(), m.Dim());
-    return m;
+    time_views_[l] = TimeMapInfo{data, dim, lev.channels, lev.positions, lev.dilation, lev.height};
   };
   // level 0: the frames themselves, clamped when padded
   if (pad_input && context > 0) {
@@ -1012,93 +997,88 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     view_of(0, input, in_dim);
   }
   KALDI_ASSERT(time_views_[0].dim.rows == rows.input_rows);
-  for (int l = 1; l < p; l++) {
-    const TimeLevel &lev = plan.levels[l], &below = plan.levels[l - 1];
-    const TimeMapInfo in = time_views_[l - 1];
-    const int nrows = (int)rows.computed[l];
-    if (lev.kind == TimeComp::kConv && time_level_2d(plan, l)) {
-      // a filter shorter than its input is high, or a level with a height below
-      cnsl::nnet0::ConvolutionComponent *conv = comps_[l].conv;
-      const CuMatrix<BaseFloat> &W = conv->LinearParams();
-      CuMatrix<BaseFloat> &m = map_of(l);
-      MatrixDim in_rows = in.dim;
-      in_rows.rows = (int)rows.computed[l - 1];
-      CuProfileScope prof("kn_timemap_conv2d");
-      CNSL_SAFE_CALL(kn_timemap_conv2d(in.data, in_rows, W.Data(), W.Dim(),
-                                       conv->BiasParams().Data(), m.Data(), m.Dim(), nrows,
-                                       below.height, below.channels,
-                                       below.height - lev.height + 1, lev.taps, below.dilation,
-                                       0, st));
-      continue;
-    }
-    if (lev.kind == TimeComp::kConv) {
-      // tap d: map'[rows] (+)= map[rows + delta d] W_d, GEMMs of the matrix layer
-      cnsl::nnet0::ConvolutionComponent *conv = comps_[l].conv;
-      const CuMatrix<BaseFloat> &W = conv->LinearParams();
-      CuMatrix<BaseFloat> &m = map_of(l);
-      CuSubMatrix<BaseFloat> y(m.Data(), nrows, lev.channels, m.Stride());
-      const bool on_splice = below.kind == TimeComp::kSplice;
-      for (int d = 0; d < lev.taps; d++) {
-        CuSubMatrix<BaseFloat> a(
-            const_cast<float *>(in.data) + (int64_t)below.dilation * d * in.dim.stride, nrows,
-            below.width, in.dim.stride);
-        // weight row i + d kh + c kh kw: a whole frame's block on the Splice
-        // (c = 0, kh = the frame), every kw-th row from d above (kh = 1)
-        float *w0 = const_cast<float *>(W.Data());
-        CuSubMatrix<BaseFloat> wd =
-            on_splice ? CuSubMatrix<BaseFloat>(w0 + (int64_t)d * below.width * W.Stride(),
-                                               below.width, lev.channels, W.Stride())
-                      : CuSubMatrix<BaseFloat>(w0 + (int64_t)d * W.Stride(), below.width,
-                                               lev.channels, lev.taps * W.Stride());
-        if (d == 0)
-          y.AddMatMatBias(1.0f, a, kNoTrans, wd, kNoTrans, conv->BiasParams());
-        else
-          y.AddMatMat(1.0f, a, kNoTrans, wd, kNoTrans, 1.0f);
-      }
-      continue;
-    }
-    // a pool, a ReLU, or a pool and the ReLU on it in one pass
-    const bool pool = lev.kind == TimeComp::kPool;
-    const bool both = pool && l + 1 < p && plan.levels[l + 1].kind == TimeComp::kRelu;
-    MatrixDim in_rows = in.dim;
-    in_rows.rows = (int)rows.computed[l - 1];
-    CuMatrix<BaseFloat> &m = map_of(l);
-    CuMatrix<BaseFloat> *act = both ? &map_of(l + 1) : (pool ? nullptr : &m);
-    if (pool && time_level_2d(plan, l)) {
-      CuProfileScope prof("kn_timemap_pool2d");
-      CNSL_SAFE_CALL(kn_timemap_pool2d(in.data, in_rows, m.Data(), m.Dim(),
-                                       act ? act->Data() : nullptr,
-                                       act ? act->Dim() : MatrixDim{0, 0, 0}, nrows,
-                                       below.height, lev.pool_height, lev.taps,
-                                       lev.pool_channel, below.dilation, st));
-      if (both) l++;
-      continue;
-    }
-    CuProfileScope prof("kn_timemap_epilogue");
-    CNSL_SAFE_CALL(kn_timemap_epilogue(
-        in.data, in_rows, pool ? m.Data() : nullptr, pool ? m.Dim() : MatrixDim{0, 0, 0},
-        act ? act->Data() : nullptr, act ? act->Dim() : MatrixDim{0, 0, 0}, nrows,
-        pool ? lev.taps : 1, pool ? lev.pool_channel : 1, below.dilation, st));
-    if (both) l++;
-  }
   const TimeLevel &top = plan.levels[p - 1];
   CuMatrix<BaseFloat> &y = out(p - 1).value;
   const int top_dim = top.width * top.positions;
   KALDI_ASSERT(comps_[p - 1].c->OutputDim() == top_dim);
   if (y.NumRows() != total || y.NumCols() != top_dim)
     y.Resize(total, top_dim, kUndefined);  // written whole
-  MatrixDim map_dim = time_views_[p - 1].dim;
-  map_dim.rows = (int)rows.computed[p - 1];
-  if (top.height > 1) {
-    CuProfileScope prof("kn_timemap_gather2d");
-    CNSL_SAFE_CALL(kn_timemap_gather2d(time_views_[p - 1].data, map_dim, y.Data(), y.Dim(),
-                                       utt_start, num_utts, context, top.height, top.positions,
-                                       top.dilation, st));
-    return;
+  // a level's own map, sized as Compute sizes its outputs: without the fill
+  auto map_of = [&](int l, int r, MatrixDim *dim) {
+    CuMatrix<BaseFloat> &m = time_maps_[l];
+    const int c = plan.levels[l].width;
+    if (m.NumRows() != r || m.NumCols() != c) m.Resize(r, c, kUndefined);
+    view_of(l, m.Data(), *dim = m.Dim());
+    return m.Data();
+  };
+  RunTimeSchedule(time_schedule(plan, rows, kUtteranceRoute), time_views_[0].data,
+                  time_views_[0].dim, map_of, &y, utt_start, num_utts);
+}
+
+void NnetStack::RunTimeSchedule(const std::vector<TimeLaunch> &sched, const float *in0,
+                                MatrixDim in0_dim, const TimeMapFn &map_of,
+                                CuMatrix<BaseFloat> *y, const int32_t *d_starts, int num_starts) {
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  struct View { float *data; MatrixDim dim; };
+  std::vector<View> views((size_t)sched.back().in_level + 1, View{nullptr, {0, 0, 0}});
+  views[0] = View{const_cast<float *>(in0), in0_dim};
+  auto form = [&](int l, int rows) {  // level l's map from the caller; -1: no map
+    if (l >= 0) views[(size_t)l].data = map_of(l, rows, &views[(size_t)l].dim);
+    return l >= 0 ? views[(size_t)l] : View{nullptr, {0, 0, 0}};
+  };
+  for (const TimeLaunch &t : sched) {
+    View in = views[(size_t)t.in_level];
+    KALDI_ASSERT(in.data != nullptr);
+    in.dim.rows = t.in_rows;
+    const View m = form(t.out_level, t.rows), act = form(t.act_level, t.rows);
+    const View &o = m.data ? m : act;  // where a convolution stores
+    cnsl::nnet0::ConvolutionComponent *conv = comps_[t.comp].conv;
+    KALDI_ASSERT(conv != nullptr || t.op > TimeLaunch::kConv2d);
+    const CuMatrix<BaseFloat> *W = conv ? &conv->LinearParams() : nullptr;
+    if (t.op == TimeLaunch::kConvTaps) {
+      // tap d: map'[rows] (+)= map[rows + delta d] W_d, GEMMs of the matrix layer
+      CuSubMatrix<BaseFloat> out(o.data, t.rows, o.dim.cols, o.dim.stride);
+      for (int d = 0; d < t.taps; d++) {
+        CuSubMatrix<BaseFloat> a(in.data + (int64_t)t.dilation * d * in.dim.stride, t.rows,
+                                 in.dim.cols, in.dim.stride);
+        CuSubMatrix<BaseFloat> wd(const_cast<float *>(W->Data()) + (int64_t)d * t.wd * W->Stride(),
+                                  in.dim.cols, o.dim.cols, t.wc * W->Stride());
+        if (d == 0)
+          out.AddMatMatBias(1.0f, a, kNoTrans, wd, kNoTrans, conv->BiasParams());
+        else
+          out.AddMatMat(1.0f, a, kNoTrans, wd, kNoTrans, 1.0f);
+      }
+    } else if (t.op == TimeLaunch::kConv) {
+      CuProfileScope prof("kn_timemap_conv");
+      CNSL_SAFE_CALL(kn_timemap_conv(in.data, in.dim, W->Data(), W->Dim(),
+                                     conv->BiasParams().Data(), o.data, o.dim, t.rows, t.taps,
+                                     t.dilation, t.wc, t.wd, t.relu, st));
+    } else if (t.op == TimeLaunch::kConv2d) {
+      CuProfileScope prof("kn_timemap_conv2d");
+      CNSL_SAFE_CALL(kn_timemap_conv2d(in.data, in.dim, W->Data(), W->Dim(),
+                                       conv->BiasParams().Data(), o.data, o.dim, t.rows, t.height,
+                                       t.channels, t.kernel_height, t.taps, t.dilation, t.relu,
+                                       st));
+    } else if (t.op == TimeLaunch::kPool2d) {
+      CuProfileScope prof("kn_timemap_pool2d");
+      CNSL_SAFE_CALL(kn_timemap_pool2d(in.data, in.dim, m.data, m.dim, act.data, act.dim, t.rows,
+                                       t.height, t.pool_height, t.taps, t.pool_channel,
+                                       t.dilation, st));
+    } else if (t.op == TimeLaunch::kEpilogue) {
+      CuProfileScope prof("kn_timemap_epilogue");
+      CNSL_SAFE_CALL(kn_timemap_epilogue(in.data, in.dim, m.data, m.dim, act.data, act.dim,
+                                         t.rows, t.taps, t.pool_channel, t.dilation, st));
+    } else if (t.op == TimeLaunch::kGather) {
+      CuProfileScope prof("kn_timemap_gather");
+      CNSL_SAFE_CALL(kn_timemap_gather(in.data, in.dim, y->Data(), y->Dim(), d_starts,
+                                       num_starts, t.context, t.positions, t.dilation, st));
+    } else {
+      CuProfileScope prof("kn_timemap_gather2d");
+      CNSL_SAFE_CALL(kn_timemap_gather2d(in.data, in.dim, y->Data(), y->Dim(), d_starts,
+                                         num_starts, t.context, t.height, t.positions,
+                                         t.dilation, st));
+    }
   }
-  CuProfileScope prof("kn_timemap_gather");
-  CNSL_SAFE_CALL(kn_timemap_gather(time_views_[p - 1].data, map_dim, y.Data(), y.Dim(), utt_start,
-                                   num_utts, context, top.positions, top.dilation, st));
 }
 
 void NnetStack::CheckPriors(const float *priors, int num_priors, bool apply_log,

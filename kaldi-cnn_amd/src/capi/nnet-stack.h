@@ -16,6 +16,7 @@
 #ifndef KCNN_CAPI_NNET_STACK_H_
 #define KCNN_CAPI_NNET_STACK_H_
 
+#include <functional>
 #include <iosfwd>
 #include <memory>
 #include <vector>
@@ -187,7 +188,9 @@ class NnetStack {
   // own.  A level may keep a height (frequency) axis H, its map row H C
   // floats (time-plan.h): a Convolution with kernel-height < in-height, or on
   // such a level, is one kn_timemap_conv2d, a Maxpool on one kn_timemap_pool2d
-  // and the gather kn_timemap_gather2d (nnet2/nnet-timemap-2d.hip).
+  // and the gather kn_timemap_gather2d (nnet2/nnet-timemap-2d.hip).  The
+  // launches are time_schedule's under kUtteranceRoute (time-plan.h), run by
+  // RunTimeSchedule; the maps are a CuMatrix a level, sized per call.
   // Same arguments, checks, result and state as Compute; to the error
   // bar of the GEMMs, not the bits, the same values.  Output(i) below prefix -
   // 1 throws afterwards (those activations are never formed); TimeMap gives
@@ -264,10 +267,17 @@ class NnetStack {
   const CuMatrix<BaseFloat> &ComputeExamplesFrom(int first, const float *feats, MatrixDim dim,
                                                  int num, bool apply_log,
                                                  const double *prior_offsets);
-  // component i when it is a ConvolutionComponent, else NULL
-  cnsl::nnet0::ConvolutionComponent *ConvAt(int i) const {
-    return i >= 0 && i < NumComponents() ? comps_[i].conv : nullptr;
-  }
+  // Runs one pass over time maps, the launches of time_schedule (time-plan.h)
+  // in order: the one place that names the kn_timemap_* kernels, for
+  // ComputeShared and for an OnlineComputer's time-shared step.  Storage is
+  // the caller's: (in0, in0_dim) is the level-0 map, map_of(level, rows, &dim)
+  // gives the map a launch writes, of `rows` rows at least (the launches that
+  // follow read it where it was given), `y` is the gather's destination,
+  // sized, and d_starts (device) the num_starts + 1 starts of its results.
+  using TimeMapFn = std::function<float *(int level, int rows, MatrixDim *dim)>;
+  void RunTimeSchedule(const std::vector<TimeLaunch> &sched, const float *in0,
+                       MatrixDim in0_dim, const TimeMapFn &map_of, CuMatrix<BaseFloat> *y,
+                       const int32_t *d_starts, int num_starts);
   int InputDim() const { return comps_.front().c->InputDim(); }
   int OutputDim() const { return comps_.back().c->OutputDim(); }
 

@@ -129,96 +129,24 @@ const CuMatrix<BaseFloat> &OnlineComputer::AcceptShared(const TimePlan &plan,
   const int p = plan.prefix();
   const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
   if (maps_.size() < (size_t)p) maps_.resize((size_t)p);
-  // the first rows.computed[l] rows of level l's buffer
-  auto map_of = [&](int l, MatrixDim *dim) {
+  // the first `r` rows of level l's buffer
+  auto map_of = [&](int l, int r, MatrixDim *dim) {
     const int width = plan.levels[l].width;
-    *dim = MatrixDim{(int)rows.computed[l], width, width};
+    *dim = MatrixDim{r, width, width};
     return static_cast<float *>(
         maps_[l].reserve(sizeof(float) * (size_t)state_.max_map_rows() * (size_t)width));
   };
   MatrixDim in_dim;
-  const float *in = nullptr;
+  float *m0 = map_of(0, (int)rows.input_rows, &in_dim);
   {
-    float *m0 = map_of(0, &in_dim);
     CuProfileScope prof("kn_stream_segments");
     CNSL_SAFE_CALL(kn_stream_segments(arena, arena_dim, m0, in_dim, d_desc, segs.num, st));
-    in = m0;
-  }
-  for (int l = 1; l < p; l++) {
-    const TimeLevel &lev = plan.levels[l], &below = plan.levels[l - 1];
-    const int nrows = (int)rows.computed[l];
-    const bool relu_next = l + 1 < p && plan.levels[l + 1].kind == TimeComp::kRelu;
-    MatrixDim out_dim;
-    if (lev.kind == TimeComp::kConv && time_level_2d(plan, l)) {
-      // a filter shorter than its input is high, or a level with a height below
-      cnsl::nnet0::ConvolutionComponent *conv = net_->ConvAt(l);
-      KALDI_ASSERT(conv != nullptr);
-      const CuMatrix<BaseFloat> &W = conv->LinearParams();
-      float *m = map_of(relu_next ? l + 1 : l, &out_dim);
-      CuProfileScope prof("kn_timemap_conv2d");
-      CNSL_SAFE_CALL(kn_timemap_conv2d(in, in_dim, W.Data(), W.Dim(), conv->BiasParams().Data(),
-                                       m, out_dim, nrows, below.height, below.channels,
-                                       below.height - lev.height + 1, lev.taps, below.dilation,
-                                       relu_next ? 1 : 0, st));
-      in = m;
-      in_dim = out_dim;
-      if (relu_next) l++;
-      continue;
-    }
-    if (lev.kind == TimeComp::kConv) {
-      cnsl::nnet0::ConvolutionComponent *conv = net_->ConvAt(l);
-      KALDI_ASSERT(conv != nullptr);
-      const CuMatrix<BaseFloat> &W = conv->LinearParams();
-      const bool on_splice = below.kind == TimeComp::kSplice;
-      // weight row i + d kh + c kh kw: a whole frame's block a tap on the Splice
-      // (c = 0, kh = the frame), every kw-th row from d above (kh = 1)
-      const int wc = on_splice ? 1 : lev.taps, wd = on_splice ? below.width : 1;
-      // the ReLU on it in the store: the conv's own level is then never formed
-      float *m = map_of(relu_next ? l + 1 : l, &out_dim);
-      CuProfileScope prof("kn_timemap_conv");
-      CNSL_SAFE_CALL(kn_timemap_conv(in, in_dim, W.Data(), W.Dim(), conv->BiasParams().Data(), m,
-                                     out_dim, nrows, lev.taps, below.dilation, wc, wd,
-                                     relu_next ? 1 : 0, st));
-      in = m;
-      in_dim = out_dim;
-      if (relu_next) l++;
-      continue;
-    }
-    // a pool, a ReLU, or a pool and the ReLU on it in one pass
-    const bool pool = lev.kind == TimeComp::kPool, both = pool && relu_next;
-    MatrixDim act_dim = {0, 0, 0};
-    float *m = map_of(l, &out_dim);
-    float *act = both ? map_of(l + 1, &act_dim) : nullptr;
-    if (!pool) { act = m; act_dim = out_dim; }
-    if (pool && time_level_2d(plan, l)) {
-      CuProfileScope prof("kn_timemap_pool2d");
-      CNSL_SAFE_CALL(kn_timemap_pool2d(in, in_dim, m, out_dim, act, act_dim, nrows,
-                                       below.height, lev.pool_height, lev.taps,
-                                       lev.pool_channel, below.dilation, st));
-    } else {
-      CuProfileScope prof("kn_timemap_epilogue");
-      CNSL_SAFE_CALL(kn_timemap_epilogue(in, in_dim, pool ? m : nullptr,
-                                         pool ? out_dim : MatrixDim{0, 0, 0}, act, act_dim,
-                                         nrows, pool ? lev.taps : 1,
-                                         pool ? lev.pool_channel : 1, below.dilation, st));
-    }
-    in = both || !pool ? act : m;
-    in_dim = both || !pool ? act_dim : out_dim;
-    if (both) l++;
   }
   const TimeLevel &top = plan.levels[p - 1];
-  const int context = plan.levels[0].positions - 1;
   CuMatrix<BaseFloat> &y = net_->ExamplesInput(p, segs.out_rows);
   KALDI_ASSERT(y.NumCols() == top.width * top.positions && y.NumRows() == segs.out_rows);
-  if (top.height > 1) {
-    CuProfileScope prof("kn_timemap_gather2d");
-    CNSL_SAFE_CALL(kn_timemap_gather2d(in, in_dim, y.Data(), y.Dim(), d_out_start, segs.num,
-                                       context, top.height, top.positions, top.dilation, st));
-  } else {
-    CuProfileScope prof("kn_timemap_gather");
-    CNSL_SAFE_CALL(kn_timemap_gather(in, in_dim, y.Data(), y.Dim(), d_out_start, segs.num,
-                                     context, top.positions, top.dilation, st));
-  }
+  net_->RunTimeSchedule(time_schedule(plan, rows, kStreamRoute), m0, in_dim, map_of, &y,
+                        d_out_start, segs.num);
   return net_->ComputeExamplesFrom(p, arena, arena_dim, segs.out_rows, apply_log_,
                                    static_cast<const double *>(d_offsets_.p));
 }

@@ -18,11 +18,12 @@
 // a small whole-utterance pass over time maps instead: each emitting slot's
 // frames [e0 - L, e0 + k + R), clamped, are one segment of the level-0 map
 // (kn_stream_segments from the arena; stream-state.h StepSegments), the packed
-// segments an unpadded ComputeShared input.  Every Convolution level is one
-// kn_timemap_conv (kn_timemap_conv2d where the level or its input keeps a
-// height), the ReLU on it fused; pools and the gather are
-// ComputeShared's kernels; the components above the prefix run as in any other
-// step (NnetStack::ComputeExamplesFrom).  The maps are the computer's own, one
+// segments an unpadded ComputeShared input.  The launches are ComputeShared's
+// (time_schedule, run by NnetStack::RunTimeSchedule) under kStreamRoute
+// (time-plan.h, which says why the routes differ): every Convolution level is
+// one kn_timemap_conv (kn_timemap_conv2d where the level or its input keeps a
+// height), the ReLU on it fused; the components above the prefix run as in any
+// other step (NnetStack::ComputeExamplesFrom).  The maps are the computer's own, one
 // buffer a level allocated once for the most rows a step can have, so a step
 // of another size allocates nothing below the first FC and the net's other
 // forward calls, ComputeShared included, disturb nothing.  Nothing is carried

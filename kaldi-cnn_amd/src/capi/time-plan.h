@@ -7,6 +7,20 @@
 // an out-of-range device access.  Header-only so that a stand-alone program
 // can run it under a host sanitizer (scripts/time_plan_check.cc).
 //
+// time_schedule turns a plan and its rows into the ordered launches of one
+// pass; NnetStack::RunTimeSchedule runs them.  Two callers, two routes:
+//   kUtteranceRoute, ComputeShared: a 1-D Convolution level is kw GEMMs of the
+//     matrix layer on row-shifted views and every level is formed (TimeMap
+//     exposes them).  At tens of thousands of rows the GEMM's tiles and
+//     operand statistics pay (profiles/compute_shared.md).
+//   kStreamRoute, an OnlineComputer's share_time step: such a level is one
+//     kn_timemap_conv, and a ReLU on any Convolution goes into its store, the
+//     convolution's own level never formed.  At about a thousand rows a launch
+//     and its latency are the cost (profiles/online_compute_shared.md).
+// Everything else -- the height-map kernels, the weight rows of a tap, a pool
+// with the ReLU on it, the gather -- is the same and decided here, where
+// scripts/time_schedule_check.cc checks it without a GPU.
+//
 // A level is the output of one component of the prefix, described by (C, n,
 // delta): channels, positions per window, dilation.  The window-layout row of
 // result frame t of utterance u has element (position k, channel c) at column
@@ -310,6 +324,86 @@ inline std::string plan_time_rows(const TimePlan &plan, const int32_t *lengths, 
   }
   *rows = r;
   return "";
+}
+
+// Which launches a caller's pass is made of (the header of this file).
+struct TimeRoute {
+  bool conv_kernel;     // a 1-D Convolution level is one kn_timemap_conv, not per-tap GEMMs
+  bool fuse_conv_relu;  // a ReLU on a Convolution goes into the convolution's store
+};
+constexpr TimeRoute kUtteranceRoute = {false, false}, kStreamRoute = {true, true};
+
+// One launch of a pass.  An argument the op's kernel does not take is 0.
+struct TimeLaunch {
+  enum Op { kConvTaps, kConv, kConv2d, kPool2d, kEpilogue, kGather, kGather2d };
+  Op op;
+  int comp;                  // the component whose level this is (a conv: whose W and bias)
+  int in_level, in_rows;     // reads the first in_rows rows of that level
+  // the map written (a pool's, a convolution's own) and the ReLU'd map written
+  // with it or instead of it; -1: none (both for the gather)
+  int out_level, act_level;
+  int rows;                  // rows computed; the gather: result rows
+  int height, channels, kernel_height;  // kConv2d: (H, C) below and kh; kPool2d, kGather2d: H
+  int taps, dilation;                   // kw or pw, and the dilation of the map read
+  int wc, wd;                           // kConvTaps, kConv: weight row c wc + d wd
+  int relu;                             // the convolutions: the ReLU in the store
+  int pool_height, pool_channel;
+  int positions, context;               // the gathers
+};
+
+// The launches of one pass over `plan` in order, the gather last; `rows` is
+// plan_time_rows' for it.  An empty plan gives none.
+inline std::vector<TimeLaunch> time_schedule(const TimePlan &plan, const TimeRows &rows,
+                                             TimeRoute route) {
+  std::vector<TimeLaunch> out;
+  const int p = plan.prefix();
+  if (p == 0) return out;
+  out.reserve((size_t)p);
+  for (int l = 1; l < p; l++) {
+    const TimeLevel &lev = plan.levels[(size_t)l], &below = plan.levels[(size_t)l - 1];
+    const bool conv = lev.kind == TimeComp::kConv, pool = lev.kind == TimeComp::kPool;
+    // The launch forms level l + 1 too: a pool and the ReLU on it from one read,
+    // or a convolution with the ReLU in its store, its own level never formed.
+    const bool with_relu = l + 1 < p && plan.levels[(size_t)l + 1].kind == TimeComp::kRelu &&
+                           (pool || (conv && route.fuse_conv_relu));
+    TimeLaunch t = {TimeLaunch::kEpilogue, l, l - 1, (int)rows.computed[(size_t)l - 1], l, -1,
+                    (int)rows.computed[(size_t)l]};
+    t.taps = lev.taps;  // (a lone ReLU: taps = pool_channel = 1)
+    t.dilation = below.dilation;
+    if (with_relu || !(conv || pool)) t.act_level = with_relu ? l + 1 : l;
+    if (!pool && t.act_level >= 0) t.out_level = -1;
+    if (conv && time_level_2d(plan, l)) {
+      // a filter shorter than its input is high, or a level with a height below
+      t.op = TimeLaunch::kConv2d;
+      t.height = below.height;
+      t.channels = below.channels;
+      t.kernel_height = below.height - lev.height + 1;
+    } else if (conv) {
+      // weight row i + d kh + c kh kw: a whole frame's block a tap on the Splice
+      // (c = 0, kh = the frame), every kw-th row from d above (kh = 1)
+      const bool on_splice = below.kind == TimeComp::kSplice;
+      t.op = route.conv_kernel ? TimeLaunch::kConv : TimeLaunch::kConvTaps;
+      t.wc = on_splice ? 1 : lev.taps;
+      t.wd = on_splice ? below.width : 1;
+    } else if (pool && time_level_2d(plan, l)) {
+      t.op = TimeLaunch::kPool2d;
+      t.height = below.height;
+      t.pool_height = lev.pool_height;
+    }
+    if (conv) t.relu = with_relu;
+    else t.pool_channel = lev.pool_channel;
+    out.push_back(t);
+    l += with_relu;
+  }
+  const TimeLevel &top = plan.levels[(size_t)p - 1];
+  TimeLaunch g = {top.height > 1 ? TimeLaunch::kGather2d : TimeLaunch::kGather, p - 1, p - 1,
+                  (int)rows.computed[(size_t)p - 1], -1, -1, (int)rows.result_rows};
+  g.height = top.height > 1 ? top.height : 0;
+  g.dilation = top.dilation;
+  g.positions = top.positions;
+  g.context = plan.levels[0].positions - 1;
+  out.push_back(g);
+  return out;
 }
 
 // The rows of level `l` that utterance u's windows read: [first, first + num).
