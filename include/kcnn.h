@@ -609,6 +609,44 @@ int kcnn_nnet_propagate_frames(kcnn_nnet *n, const kcnn_corpus *corpus, const in
 int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
                                   const int32_t *frames, int num_frames, const int32_t *rows,
                                   const int32_t *cols, const float *weights, int num);
+/* kcnn_nnet_propagate_frames with the leading Splice -> {Convolution | Maxpool
+ * | ReLU}... components (kcnn_nnet_time_train_prefix of them) run as TIME MAPS,
+ * once per time step of each RUN of the list: a maximal stretch of entries
+ * with frames[i + 1] == frames[i] + 1 in one utterance.  Any list is legal (any
+ * order, repeats, runs of one frame) and output row n stays example frames[n].
+ * A run of k frames is a segment of k + L + R level-0 rows, corpus rows clamp(r0
+ * - L + j, s, e - 1); the maps, their levels and kcnn_nnet_time_map are those
+ * of kcnn_nnet_compute_shared, and kcnn_nnet_output below prefix - 1 is an
+ * error.  The values are kcnn_nnet_propagate_frames' to the error bar of the
+ * GEMMs, not the bits.  kcnn_nnet_backprop / _backprop_xent then run the
+ * components from the prefix upwards as always and the prefix once, over the
+ * maps: the adjoint of the gather, the pool and ReLU backward on a map, and per
+ * Convolution the weight, bias and data gradients as per-tap GEMMs on
+ * row-shifted views, each Convolution stepping by kcnn_component_apply_gradient's rule
+ * with num_sample = num_frames.  The prefix's RectifiedLinearComponents
+ * accumulate no <ValueSum> / <DerivSum> / <Count> in such a step.  Until the
+ * next forward call kcnn_nnet_backprop_component, _backprop_split and
+ * _input_deriv of a prefix component are errors that change nothing.  The
+ * checks of kcnn_nnet_propagate_frames, then the maps' (every map below 2^31
+ * rows and elements), precede every launch.  With a training prefix of 0 the
+ * call is kcnn_nnet_propagate_frames itself. */
+int kcnn_nnet_propagate_frames_shared(kcnn_nnet *n, const kcnn_corpus *corpus,
+                                      const int32_t *frames, int num_frames);
+/* The leading components kcnn_nnet_propagate_frames_shared runs as time maps as
+ * the literal path now stands: kcnn_nnet_time_shared_prefix, or 0 when a level
+ * of that prefix keeps a height (convolutions along frequency do not train
+ * this way). */
+int kcnn_nnet_time_train_prefix(const kcnn_nnet *n);
+/* After kcnn_nnet_propagate_frames_shared and a backward pass, until the next
+ * forward call: the derivative map of `level`, as kcnn_nnet_time_map gives the
+ * map (rows that no window reads are 0).  Level 0, and a Maxpool's own level
+ * when a ReLU follows it, have none: an error.  For tests and debugging. */
+int kcnn_nnet_time_map_deriv(const kcnn_nnet *n, int level, const float **data, MatrixDim *dim,
+                             int *channels, int *positions, int *dilation);
+/* The flat gradient ([KernelDim x Group] then Group biases, kcnn_component_compute_gradient's
+ * layout) that backward applied to Convolution i of the prefix: *num floats on
+ * the DEVICE. */
+int kcnn_nnet_time_gradient(const kcnn_nnet *n, int i, const float **data, int *num);
 
 /* ---- streaming forward pass over concurrent utterances -------------------- */
 /* Upstream NnetOnlineComputer(nnet, pad_input = true), the decodable of

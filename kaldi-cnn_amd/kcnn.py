@@ -91,6 +91,10 @@ def lib():
             L.kcnn_nnet_compute_prob_frames.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        if hasattr(L, "kcnn_nnet_propagate_frames_shared"):  # (absent before time-shared training)
+            L.kcnn_nnet_propagate_frames_shared.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.c_void_p, ctypes.c_int]
+            L.kcnn_nnet_time_train_prefix.argtypes = [ctypes.c_void_p]
         if hasattr(L, "kcnn_online_new"):  # (absent from builds before the streaming pass)
             L.kcnn_online_new.restype = ctypes.c_void_p
             L.kcnn_online_new.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -993,17 +997,59 @@ class Nnet:
             ctypes.byref(p), ctypes.byref(d)))
         return _device_view(p.value, d)
 
-    def PropagateFrames(self, corpus: "Corpus", frames):
+    def PropagateFrames(self, corpus: "Corpus", frames, share_time=False):
         """Propagate on a minibatch given as rows of a device-resident corpus
         (kcnn_nnet_propagate_frames).  `frames`: host int32 indices of corpus
         rows, any order, repeats allowed; example n is frames[n], and its
         context window (clamped at its utterance's ends) is gathered on the
         device.  Output row n, and the labels' rows of a following
-        BackpropXent, are example n.  Does not synchronise."""
+        BackpropXent, are example n.  Does not synchronise.
+        share_time (kcnn_nnet_propagate_frames_shared): the leading
+        TimeSharedTrainPrefix() components run once per time step of each run
+        of consecutive rows in the list (time maps) instead of once per
+        example's window, and Backprop / BackpropXent run their backward once
+        over the maps -- the same step to the error bar of the GEMMs, not the
+        same bits.  Output(i) of those components but the last then raises, as
+        do BackpropComponent and InputDeriv of them; their ReLUs accumulate no
+        statistics in such a step.  TimeMap, TimeMapDeriv and TimeGradient show
+        the maps, their derivatives and the gradients applied.  Any list is
+        legal; the saving grows with the length of its runs.  A network this
+        does not cover (TimeSharedTrainPrefix() == 0) runs as without it."""
         fr = _frame_array(frames)
         self._input = corpus  # the library borrows its matrix until Backprop
-        check(lib().kcnn_nnet_propagate_frames(
-            self._h, corpus._h, fr.ctypes.data_as(ctypes.c_void_p), len(fr)))
+        fn = (lib().kcnn_nnet_propagate_frames_shared if share_time
+              else lib().kcnn_nnet_propagate_frames)
+        check(fn(self._h, corpus._h, fr.ctypes.data_as(ctypes.c_void_p), len(fr)))
+
+    def TimeSharedTrainPrefix(self):
+        """The number of leading components PropagateFrames(share_time=True)
+        runs as time maps (kcnn_nnet_time_train_prefix): TimeSharedPrefix(), or
+        0 when one of them keeps a frequency axis."""
+        return lib().kcnn_nnet_time_train_prefix(self._h)
+
+    def TimeMapDeriv(self, level):
+        """The derivative map of `level` after PropagateFrames(share_time=True)
+        and a backward pass (kcnn_nnet_time_map_deriv), as TimeMap gives the
+        map: (torch view, channels, positions, dilation).  Level 0 and a
+        Maxpool's own level under a ReLU have none and raise.  Valid until the
+        next forward call; for tests and debugging."""
+        p = ctypes.c_void_p()
+        d = MatrixDim()
+        c, n, dil = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib().kcnn_nnet_time_map_deriv(self._h, int(level), ctypes.byref(p),
+                                             ctypes.byref(d), ctypes.byref(c), ctypes.byref(n),
+                                             ctypes.byref(dil)))
+        return _device_view(p.value, d), c.value, n.value, dil.value
+
+    def TimeGradient(self, i):
+        """The flat gradient that backward applied to Convolution i of the
+        prefix (kcnn_nnet_time_gradient): a torch view of KernelDim * Group
+        weight entries, row-major, then Group biases, ComputeGradient's
+        layout."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int()
+        check(lib().kcnn_nnet_time_gradient(self._h, int(i), ctypes.byref(p), ctypes.byref(n)))
+        return _device_view(p.value, MatrixDim(1, n.value, n.value))[0]
 
     def ComputeProbFrames(self, corpus: "Corpus", frames, labels):
         """ComputeProb on such a minibatch (kcnn_nnet_compute_prob_frames);
@@ -1155,13 +1201,31 @@ class OnlineComputer:
         return int(out[0]), int(out[1])
 
 
-def train_epoch(net: Nnet, corpus: Corpus, pdfs, minibatch_size: int, srand: int = 0):
+def chunk_runs(lengths, chunk):
+    """The runs train_epoch(chunk=k) cuts a corpus into: every utterance in
+    order as (first corpus row, rows) stretches of `chunk` consecutive rows,
+    its last one possibly shorter."""
+    runs, start = [], 0
+    for t in lengths:
+        t = int(t)
+        runs += [(start + at, min(chunk, t - at)) for at in range(0, t, chunk)]
+        start += t
+    return runs
+
+
+def train_epoch(net: Nnet, corpus: Corpus, pdfs, minibatch_size: int, srand: int = 0,
+                chunk=None):
     """One epoch over the corpus, as nnet-shuffle-egs --srand followed by the
     nnet-train loop: one numpy permutation of all corpus rows seeded by
     `srand`, minibatches of `minibatch_size` (the remainder trained as a last,
     smaller one), labels (n, pdfs[frames[n]], 1.0).  `pdfs`: one class per
     corpus row (host).  Returns (objf, frames) of ObjfTotal(reset=True), which
-    synchronises; totals accumulated before the call are included."""
+    synchronises; totals accumulated before the call are included.
+    With chunk=k the examples are shuffled in runs (chunk_runs: each utterance
+    cut into stretches of k consecutive rows): one permutation of the runs,
+    minibatches of max(1, minibatch_size // k) runs (the remainder a last one),
+    each trained by PropagateFrames(share_time=True) and BackpropXent, so the
+    convolutional prefix runs once per time step of a run."""
     import numpy as np
     pdfs = np.ascontiguousarray(pdfs, np.int32).ravel()
     rows = corpus.NumRows()
@@ -1169,6 +1233,20 @@ def train_epoch(net: Nnet, corpus: Corpus, pdfs, minibatch_size: int, srand: int
         raise KcnnError(f"train_epoch: {len(pdfs)} pdfs for a corpus of {rows} rows")
     if minibatch_size < 1:
         raise KcnnError(f"train_epoch: minibatch_size {minibatch_size}")
+    if chunk is not None:
+        if int(chunk) < 1:
+            raise KcnnError(f"train_epoch: chunk {chunk}")
+        runs = chunk_runs(corpus.lengths, int(chunk))
+        order = np.random.default_rng(srand).permutation(len(runs))
+        per = max(1, minibatch_size // int(chunk))
+        for at in range(0, len(runs), per):
+            frames = np.concatenate([np.arange(runs[j][0], runs[j][0] + runs[j][1],
+                                               dtype=np.int32) for j in order[at:at + per]])
+            n = len(frames)
+            net.PropagateFrames(corpus, frames, share_time=True)
+            net.BackpropXent((np.arange(n, dtype=np.int32), pdfs[frames],
+                              np.ones(n, np.float32)))
+        return net.ObjfTotal(reset=True)
     order = np.random.default_rng(srand).permutation(rows).astype(np.int32)
     for at in range(0, rows, minibatch_size):
         frames = order[at:at + minibatch_size]

@@ -2,7 +2,9 @@
 // as corpus row indices (kcnn_nnet_propagate_frames / _compute_prob_frames):
 // the corpus handle's utterance starts, the checks of a frame list against
 // them, and the {row, first row, last row of its utterance} triple per example
-// that kn_splice_frames_prop reads (nnet2/nnet-kernels.h).  Pure host code
+// that kn_splice_frames_prop reads (nnet2/nnet-kernels.h); and the runs of
+// consecutive rows of such a list, with their device image, for a training
+// step over time maps (kcnn_nnet_propagate_frames_shared).  Pure host code
 // with no GPU call: a bad index is refused here, before any launch, so it can
 // never become an out-of-range device access.  Header-only so that a
 // stand-alone program can run it under a host sanitizer
@@ -109,6 +111,49 @@ inline void stage_frames(const CorpusIndex &corpus, const int32_t *frames, int n
     out[3 * (size_t)i] = frames[i];
     out[3 * (size_t)i + 1] = s[u];
     out[3 * (size_t)i + 2] = s[u + 1] - 1;
+  }
+}
+
+// A run of a CHECKED frame list (kcnn_nnet_propagate_frames_shared): a maximal
+// stretch of list entries with frames[i + 1] == frames[i] + 1 and both rows in
+// one utterance.  Any list is legal -- any order, repeats, runs of one frame --
+// and the runs are stretches of the list itself, so example n stays frames[n].
+struct FrameRun {
+  int32_t first, length;  // r0, the corpus row of its first example, and k
+  int32_t lo, hi;         // the first and the last row of its utterance
+};
+
+inline std::vector<FrameRun> frame_runs(const CorpusIndex &corpus, const int32_t *frames,
+                                        int num) {
+  std::vector<FrameRun> runs;
+  const std::vector<int32_t> &s = corpus.starts;
+  for (int i = 0; i < num; i++) {
+    if (!runs.empty()) {
+      FrameRun &r = runs.back();
+      if (frames[i] == r.first + r.length && frames[i] <= r.hi) {
+        r.length++;
+        continue;
+      }
+    }
+    const size_t u = (size_t)(std::upper_bound(s.begin(), s.end() - 1, frames[i]) - s.begin()) - 1;
+    runs.push_back(FrameRun{frames[i], 1, s[u], s[u + 1] - 1});
+  }
+  return runs;
+}
+
+// The device image of the runs, which kn_timemap_layout reads: the num_runs + 1
+// starts of the runs' result rows (the prefix of their lengths), then {r0,
+// first row, last row} per run, as stage_frames stages an example's triple.
+inline size_t run_image_bytes(size_t num_runs) { return sizeof(int32_t) * (4 * num_runs + 1); }
+
+inline void stage_runs(const std::vector<FrameRun> &runs, void *staging) {
+  int32_t *starts = static_cast<int32_t *>(staging), *tri = starts + runs.size() + 1;
+  starts[0] = 0;
+  for (size_t j = 0; j < runs.size(); j++) {
+    starts[j + 1] = starts[j] + runs[j].length;
+    tri[3 * j] = runs[j].first;
+    tri[3 * j + 1] = runs[j].lo;
+    tri[3 * j + 2] = runs[j].hi;
   }
 }
 

@@ -887,6 +887,41 @@ int kcnn_nnet_compute_prob_frames(kcnn_nnet *n, const kcnn_corpus *corpus,
   });
 }
 
+int kcnn_nnet_propagate_frames_shared(kcnn_nnet *n, const kcnn_corpus *corpus,
+                                      const int32_t *frames, int num_frames) {
+  return guard([&] {
+    if (corpus == nullptr) KALDI_ERR << "kcnn_nnet_propagate_frames_shared: no corpus";
+    n->stack.PropagateFramesShared(corpus->feats, corpus->dim, corpus->index, frames,
+                                   num_frames);
+  });
+}
+int kcnn_nnet_time_train_prefix(const kcnn_nnet *n) {
+  int prefix = 0;
+  guard([&] { prefix = n->stack.TimeSharedTrainPlan().prefix(); });
+  return prefix;
+}
+int kcnn_nnet_time_map_deriv(const kcnn_nnet *n, int level, const float **data, MatrixDim *dim,
+                             int *channels, int *positions, int *dilation) {
+  return guard([&] {
+    if (data == nullptr || dim == nullptr || channels == nullptr || positions == nullptr ||
+        dilation == nullptr)
+      KALDI_ERR << "kcnn_nnet_time_map_deriv: no result pointers";
+    const kcnn::NnetStack::TimeMapInfo m = n->stack.TimeMapDeriv(level);
+    *data = m.data;
+    *dim = m.dim;
+    *channels = m.channels;
+    *positions = m.positions;
+    *dilation = m.dilation;
+  });
+}
+int kcnn_nnet_time_gradient(const kcnn_nnet *n, int i, const float **data, int *num) {
+  return guard([&] {
+    if (data == nullptr || num == nullptr)
+      KALDI_ERR << "kcnn_nnet_time_gradient: no result pointers";
+    *data = n->stack.TimeGradient(i, num);
+  });
+}
+
 // ---- streaming forward pass (kcnn::OnlineComputer) ---------------------------------
 kcnn_online *kcnn_online_new(kcnn_nnet *n, int num_streams, int max_chunk, const float *priors,
                              int num_priors, float prior_scale, int apply_log) {

@@ -115,6 +115,8 @@ void NnetStack::Init(std::vector<std::unique_ptr<Component>> parsed) {
   comps_.resize(nc);
   acts_.resize(nc + 1);
   time_maps_.resize(nc);
+  time_derivs_.resize(nc);
+  time_grads_.resize(nc);
   for (size_t i = 0; i < nc; i++) {
     Comp &c = comps_[i];
     c.c = std::move(parsed[i]);
@@ -291,7 +293,7 @@ void NnetStack::PropagateFirst(const float *input, MatrixDim in_dim, int count,
   num_chunks_ = fl ? fl->num : checked_num_chunks(in_dim, comps_[0].c->InputDim(), in_cs);
   acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
   ForgetMinibatch();
-  prob_forward_ = whole_utts_ = frames_fused_ = time_shared_ = false;
+  prob_forward_ = whole_utts_ = frames_fused_ = time_shared_ = time_train_ = false;
   examples_first_ = 0;
   int first = 0;  // the component the loop starts at
   if (fl != nullptr) {
@@ -384,6 +386,190 @@ void NnetStack::PropagateFrames(const float *feats, MatrixDim dim, const CorpusI
   PropagateFirst(feats, dim, NumComponents(), &fl);
 }
 
+TimePlan NnetStack::TimeSharedTrainPlan() const {
+  TimePlan plan = time_train_plan(TimeSharedPlan());
+  if (plan.prefix() == NumComponents()) {
+    // the backward over the maps starts from the input derivative of the
+    // component above them
+    plan.levels.clear();
+    plan.declined = "no component follows the prefix";
+  }
+  return plan;
+}
+
+void NnetStack::PropagateFramesShared(const float *feats, MatrixDim dim,
+                                      const CorpusIndex &corpus, const int32_t *frames, int num) {
+  const char *who = "kcnn_nnet_propagate_frames_shared";
+  FrameList fl = {feats, dim, &corpus, frames, num, nullptr};
+  CheckFrames(fl, who);  // every check before any launch
+  const TimePlan plan = TimeSharedTrainPlan();
+  const int p = plan.prefix(), nc = NumComponents();
+  if (p == 0) {  // PropagateFrames itself
+    StageFrames(&fl);
+    PropagateFirst(feats, dim, nc, &fl);
+    return;
+  }
+  const std::vector<FrameRun> runs = frame_runs(corpus, frames, num);
+  const int num_runs = (int)runs.size();
+  std::vector<int32_t> lengths(runs.size());
+  for (size_t j = 0; j < runs.size(); j++) lengths[j] = runs[j].length;
+  TimeRows rows;
+  const std::string bad = plan_train_rows(plan, lengths.data(), num_runs, &rows);
+  if (!bad.empty()) KALDI_ERR << who << ": " << bad;
+  KALDI_ASSERT(rows.result_rows == num && p < nc);
+  // the runs' starts and triples, staged as PropagateFrames stages its examples
+  const size_t bytes = run_image_bytes(runs.size());
+  stage_runs(runs, frames_.Begin(bytes));
+  const int32_t *d_starts = reinterpret_cast<const int32_t *>(
+      frames_.Commit(bytes, CuDevice::Instantiate().Stream()));
+  const int32_t *d_runs = d_starts + runs.size() + 1;
+
+  num_chunks_ = num;
+  acts_[0].value.Borrow(const_cast<float *>(feats), dim.rows, dim.cols, dim.stride);
+  ForgetMinibatch();
+  prob_forward_ = whole_utts_ = false;
+  examples_first_ = 0;
+  // component 0 reads the corpus and has no Backprop, as after PropagateFrames
+  frames_fused_ = time_shared_ = time_train_ = true;
+  time_backward_done_ = false;
+  train_plan_ = plan;
+  train_rows_ = rows;
+  train_starts_ = d_starts;
+  train_runs_ = num_runs;
+  time_dviews_.assign((size_t)p, TimeMapInfo());
+
+  // level 0: each run's k + L + R rows, clamped into its utterance
+  const int context = plan.levels[0].positions - 1;
+  CuMatrix<BaseFloat> &m0 = time_maps_[0];
+  if (m0.NumRows() != rows.input_rows || m0.NumCols() != dim.cols)
+    m0.Resize((int)rows.input_rows, dim.cols, kUndefined);  // written whole
+  {
+    CuProfileScope prof("kn_timemap_layout");
+    CNSL_SAFE_CALL(kn_timemap_layout(
+        feats, dim, m0.Data(), m0.Dim(), d_starts, d_runs, num_runs, LeftContext(), context,
+        reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream())));
+  }
+  time_views_.assign((size_t)p, TimeMapInfo());
+  const TimeLevel &l0 = plan.levels[0];
+  time_views_[0] = TimeMapInfo{m0.Data(), m0.Dim(), l0.channels, l0.positions, l0.dilation,
+                               l0.height};
+  FormTimeLevels(plan, rows, d_starts, num_runs, num);
+  for (int i = p; i < nc; i++) {  // PropagateFirst's loop
+    if (PropagateMaxpoolPair(i) || PropagateReluPair(i)) { i++; continue; }
+    ChunkInfo ii = in_info(i), oi = out_info(i);
+    auto hint = input_stats(i);
+    comps_[i].c->Propagate(ii, oi, in(i).value, &out(i).value);
+  }
+}
+
+NnetStack::TimeMapInfo NnetStack::TimeMapDeriv(int level) const {
+  const char *who = "kcnn_nnet_time_map_deriv";
+  if (!time_train_ || !time_backward_done_)
+    KALDI_ERR << who << ": no backward pass has run over the time maps of a "
+              << "kcnn_nnet_propagate_frames_shared";
+  if (level < 0 || level >= (int)time_dviews_.size())
+    KALDI_ERR << who << ": level " << level << " outside [0, " << time_dviews_.size() << ")";
+  if (time_dviews_[level].data == nullptr)
+    KALDI_ERR << who << ": level " << level << " has no derivative map (level 0, and a pool's "
+              << "own level under a ReLU, are never formed)";
+  return time_dviews_[level];
+}
+
+const float *NnetStack::TimeGradient(int i, int *num) const {
+  const char *who = "kcnn_nnet_time_gradient";
+  if (!time_train_ || !time_backward_done_)
+    KALDI_ERR << who << ": no backward pass has run over the time maps of a "
+              << "kcnn_nnet_propagate_frames_shared";
+  if (i < 0 || i >= train_plan_.prefix() || comps_[i].conv == nullptr)
+    KALDI_ERR << who << ": component " << i << " is not a Convolution of the "
+              << train_plan_.prefix() << " components run as time maps";
+  *num = comps_[i].conv->NumGradientParams();
+  return time_grads_[i].Data();
+}
+
+// The launches of time_backward_schedule in order.  A derivative map has its
+// level's geometry and the rows its launch writes; rows no window reads come
+// out 0 at every level, since the scatter zeroes them at the top.
+void NnetStack::BackpropTimeMaps() {
+  const TimePlan &plan = train_plan_;
+  const int p = plan.prefix();
+  const kcnn_stream_t st = reinterpret_cast<kcnn_stream_t>(CuDevice::Instantiate().Stream());
+  const CuMatrix<BaseFloat> &dy = InputDeriv(p);
+  KALDI_ASSERT(dy.NumRows() == num_chunks_ && dy.NumCols() == comps_[p - 1].c->OutputDim());
+  time_dviews_.assign((size_t)p, TimeMapInfo());
+  auto deriv_of = [&](int l, int rows) -> CuMatrix<BaseFloat> & {
+    CuMatrix<BaseFloat> &m = time_derivs_[l];
+    const TimeLevel &lev = plan.levels[l];
+    if (m.NumRows() != rows || m.NumCols() != lev.width) m.Resize(rows, lev.width, kUndefined);
+    time_dviews_[l] = TimeMapInfo{m.Data(), m.Dim(), lev.channels, lev.positions, lev.dilation,
+                                  lev.height};
+    return m;
+  };
+  auto map_at = [&](int l, int rows) {  // the first `rows` rows of a forward map
+    const TimeMapInfo &v = time_views_[l];
+    KALDI_ASSERT(v.data != nullptr && v.dim.rows >= rows);
+    return CuSubMatrix<BaseFloat>(const_cast<float *>(v.data), rows, v.dim.cols, v.dim.stride);
+  };
+  for (const TimeBackLaunch &t : time_backward_schedule(plan, train_rows_)) {
+    if (t.op == TimeBackLaunch::kScatter) {
+      CuMatrix<BaseFloat> &dm = deriv_of(t.din_level, t.in_rows);
+      CuProfileScope prof("kn_timemap_scatter");
+      CNSL_SAFE_CALL(kn_timemap_scatter(dy.Data(), dy.Dim(), dm.Data(), dm.Dim(), train_starts_,
+                                        train_runs_, t.context, t.positions, t.dilation,
+                                        t.in_rows, st));
+      continue;
+    }
+    const CuMatrix<BaseFloat> &dout = time_derivs_[t.dout_level];
+    KALDI_ASSERT(time_dviews_[t.dout_level].data != nullptr && dout.NumRows() == t.rows);
+    if (t.op == TimeBackLaunch::kEpilogueBwd) {
+      CuMatrix<BaseFloat> &din = deriv_of(t.din_level, t.in_rows);
+      KALDI_ASSERT(t.in_rows == t.rows + t.dilation * (t.taps - 1));
+      const CuSubMatrix<BaseFloat> x = map_at(t.in_level, t.in_rows);
+      const bool pool = t.pooled_level >= 0, act = t.act_level >= 0;
+      const CuSubMatrix<BaseFloat> pm = map_at(pool ? t.pooled_level : t.in_level, t.rows),
+                                   am = map_at(act ? t.act_level : t.in_level, t.rows);
+      CuProfileScope prof("kn_timemap_epilogue_bwd");
+      CNSL_SAFE_CALL(kn_timemap_epilogue_bwd(
+          x.Data(), x.Dim(), pool ? pm.Data() : nullptr, pm.Dim(), act ? am.Data() : nullptr,
+          am.Dim(), dout.Data(), dout.Dim(), din.Data(), din.Dim(), t.rows, t.taps,
+          pool ? t.pool_channel : 1, t.dilation, st));
+      continue;
+    }
+    // a Convolution: per tap d, the gradient block map_in[delta d ..)^T dout
+    // into rows c wc + d wd of the flat gradient, and din[delta d ..) += dout
+    // W_d^T with the weights as they stand; then the step
+    cnsl::nnet0::ConvolutionComponent *conv = comps_[t.comp].conv;
+    KALDI_ASSERT(conv != nullptr);
+    const int G = conv->Group(), K = conv->KernelDim();
+    CuMatrix<BaseFloat> &grad = time_grads_[t.comp];
+    if (grad.NumRows() != 1 || grad.NumCols() != conv->NumGradientParams())
+      grad.Resize(1, conv->NumGradientParams(), kUndefined);  // written whole
+    const CuSubMatrix<BaseFloat> x = map_at(t.in_level, t.in_rows);
+    KALDI_ASSERT(dout.NumCols() == G && x.NumCols() * t.taps == K &&
+                 t.in_rows == t.rows + t.dilation * (t.taps - 1));
+    for (int d = 0; d < t.taps; d++) {
+      const CuSubMatrix<BaseFloat> xd = x.RowRange(t.dilation * d, t.rows);
+      CuSubMatrix<BaseFloat> gd(grad.Data() + (int64_t)d * t.wd * G, x.NumCols(), G, t.wc * G);
+      gd.AddMatMat(1.0f, xd, kTrans, dout, kNoTrans, 0.0f);
+    }
+    CuSubVector<BaseFloat> gb(grad.Data() + (size_t)K * G, G);
+    gb.AddRowSumMat(1.0f, dout, 0.0f);
+    if (t.din_level >= 0) {
+      CuMatrix<BaseFloat> &din = deriv_of(t.din_level, t.in_rows);
+      din.SetZero();
+      const CuMatrix<BaseFloat> &W = conv->LinearParams();
+      for (int d = 0; d < t.taps; d++) {
+        CuSubMatrix<BaseFloat> dd = din.RowRange(t.dilation * d, t.rows);
+        const CuSubMatrix<BaseFloat> wd(const_cast<float *>(W.Data()) + (int64_t)d * t.wd * W.Stride(),
+                                        x.NumCols(), G, t.wc * W.Stride());
+        dd.AddMatMat(1.0f, dout, kNoTrans, wd, kTrans, 1.0f);
+      }
+    }
+    conv->ApplyGradient(grad.Data(), num_chunks_);
+  }
+  time_backward_done_ = true;
+}
+
 void NnetStack::ComputeProbFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
                                   const int32_t *frames, int num, const int32_t *rows,
                                   const int32_t *cols, const float *weights, int num_labels) {
@@ -437,7 +623,7 @@ const CuMatrix<BaseFloat> &NnetStack::ComputeExamplesFrom(int first, const float
   num_chunks_ = num;
   acts_[0].value.Borrow(const_cast<float *>(feats), dim.rows, dim.cols, dim.stride);
   ForgetMinibatch();
-  whole_utts_ = time_shared_ = false;
+  whole_utts_ = time_shared_ = time_train_ = false;
   frames_fused_ = true;  // as after ComputeExamples through a first Splice
   examples_first_ = first;
   for (int i = first; i < count; i++) {
@@ -457,8 +643,9 @@ const CuMatrix<BaseFloat> &NnetStack::Output(int i) {
     KALDI_ERR << "output of component " << i << " was not formed: the streaming step ran "
               << "components 0 to " << examples_first_ - 1 << " as time maps";
   if (time_shared_ && i >= 0 && i + 1 < (int)time_views_.size())
-    KALDI_ERR << "output of component " << i << " was not formed: kcnn_nnet_compute_shared ran "
-              << "components 0 to " << time_views_.size() - 1 << " as time maps; see "
+    KALDI_ERR << "output of component " << i << " was not formed: "
+              << (time_train_ ? "kcnn_nnet_propagate_frames_shared" : "kcnn_nnet_compute_shared")
+              << " ran components 0 to " << time_views_.size() - 1 << " as time maps; see "
               << "kcnn_nnet_time_map";
   if (a.stale == kGone)
     KALDI_ERR << "output of component " << i << " was not stored (fused with the "
@@ -484,6 +671,7 @@ void NnetStack::MaterialisePoolDeriv(int i) {
 
 const CuMatrix<BaseFloat> &NnetStack::InputDeriv(int i) {
   KALDI_ASSERT(i >= 0 && i < NumComponents());
+  RequireAbovePrefix(i, "kcnn_nnet_input_deriv");
   if (i == 0 && frames_fused_)
     KALDI_ERR << "input derivative of component 0: after kcnn_nnet_propagate_frames a first "
               << "SpliceComponent reads the corpus itself and its Backprop is not run (it has "
@@ -498,6 +686,7 @@ void NnetStack::BackpropComponent(int i, const float *out_deriv, MatrixDim od_di
   KALDI_ASSERT(i >= 0 && i < nc);
   RequireTrainingForward("kcnn_nnet_backprop_component");
   RequireLastNotFused(i, "kcnn_nnet_backprop_component");
+  RequireAbovePrefix(i, "kcnn_nnet_backprop_component");
   // a first Splice that gathered from the corpus: nothing to update, and its
   // input derivative would be a window matrix of rows that examples share
   if (i == 0 && frames_fused_) return;
@@ -550,6 +739,7 @@ void NnetStack::BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, f
   KALDI_ASSERT(i >= 0 && i < nc && grad != NULL);
   RequireTrainingForward("kcnn_nnet_backprop_split");
   RequireLastNotFused(i, "kcnn_nnet_backprop_split");
+  RequireAbovePrefix(i, "kcnn_nnet_backprop_split");
   Comp &c = comps_[i];
   if (c.affine == NULL) KALDI_ERR << "kcnn_nnet_backprop_split: component " << i << " is not affine";
   KALDI_ASSERT(!(i + 1 < nc && comps_[i + 1].deriv_deferred) && !c.mask_valid);
@@ -566,8 +756,11 @@ void NnetStack::BackpropSplit(int i, const float *out_deriv, MatrixDim od_dim, f
 }
 
 void NnetStack::Backprop(const float *out_deriv, MatrixDim od_dim) {
-  for (int i = NumComponents() - 1; i >= 0; i--)
+  // after PropagateFramesShared the prefix runs once, over its time maps
+  const int stop = time_train_ ? train_plan_.prefix() : 0;
+  for (int i = NumComponents() - 1; i >= stop; i--)
     BackpropComponent(i, out_deriv, od_dim, kUpdate, nullptr, false);
+  if (time_train_) BackpropTimeMaps();
 }
 
 double *NnetStack::objf_totals() {
@@ -651,8 +844,10 @@ void NnetStack::BackpropXent(const int32_t *rows, const int32_t *cols, const flo
   MatrixDim od_dim = {0, 0, 0};
   const int first =
       XentDeriv(rows, cols, weights, num, &od, &od_dim, "kcnn_nnet_backprop_xent");
-  for (int i = first; i >= 0; i--)
+  const int stop = time_train_ ? train_plan_.prefix() : 0;
+  for (int i = first; i >= stop; i--)
     BackpropComponent(i, od, od_dim, kUpdate, nullptr, skip_first_dx);
+  if (time_train_) BackpropTimeMaps();
   // the whole backward has run: the last component is the caller's again
   xent_fused_ = false;
 }
@@ -687,6 +882,13 @@ void NnetStack::RequireTrainingForward(const char *who) const {
     KALDI_ERR << who << ": the last forward pass was kcnn_nnet_compute_prob's or "
               << "kcnn_nnet_compute's, which keep nothing for a backprop; run "
               << "kcnn_nnet_propagate first";
+}
+
+void NnetStack::RequireAbovePrefix(int i, const char *who) const {
+  if (time_train_ && i < train_plan_.prefix())
+    KALDI_ERR << who << ": component " << i << " is one of the " << train_plan_.prefix()
+              << " that kcnn_nnet_propagate_frames_shared ran as time maps; their backward runs "
+              << "once, over the maps, in kcnn_nnet_backprop / kcnn_nnet_backprop_xent";
 }
 
 void NnetStack::RequireLastNotFused(int i, const char *who) const {
@@ -803,6 +1005,7 @@ void NnetStack::PropagateUtterances(const float *input, MatrixDim in_dim,
   frames_fused_ = false;
   examples_first_ = 0;
   time_shared_ = first > 0;
+  time_train_ = false;
   if (first > 0) {
     // the time maps have run and the gather has written component first's input
     acts_[0].value.Borrow(const_cast<float *>(input), in_dim.rows, in_dim.cols, in_dim.stride);
@@ -997,6 +1200,16 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     view_of(0, input, in_dim);
   }
   KALDI_ASSERT(time_views_[0].dim.rows == rows.input_rows);
+  FormTimeLevels(plan, rows, utt_start, num_utts, total);
+}
+
+void NnetStack::FormTimeLevels(const TimePlan &plan, const TimeRows &rows, const int32_t *starts,
+                               int num_starts, int total) {
+  const int p = plan.prefix();
+  auto view_of = [&](int l, const float *data, MatrixDim dim) {
+    const TimeLevel &lev = plan.levels[l];
+    time_views_[l] = TimeMapInfo{data, dim, lev.channels, lev.positions, lev.dilation, lev.height};
+  };
   const TimeLevel &top = plan.levels[p - 1];
   CuMatrix<BaseFloat> &y = out(p - 1).value;
   const int top_dim = top.width * top.positions;
@@ -1012,7 +1225,7 @@ void NnetStack::PropagateTimeShared(const float *input, MatrixDim in_dim,
     return m.Data();
   };
   RunTimeSchedule(time_schedule(plan, rows, kUtteranceRoute), time_views_[0].data,
-                  time_views_[0].dim, map_of, &y, utt_start, num_utts);
+                  time_views_[0].dim, map_of, &y, starts, num_starts);
 }
 
 void NnetStack::RunTimeSchedule(const std::vector<TimeLaunch> &sched, const float *in0,

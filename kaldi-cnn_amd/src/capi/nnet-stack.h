@@ -10,7 +10,9 @@
 // the same pass with the convolutional prefix run once per time step
 // (time-plan.h); and what comes
 // before one: PropagateFrames, a minibatch as rows of a corpus that stays on
-// the device (nnet-get-egs and nnet-shuffle-egs without the window matrices).
+// the device (nnet-get-egs and nnet-shuffle-egs without the window matrices),
+// with PropagateFramesShared, such a step with the convolutional prefix run
+// once per time step of each run of consecutive rows, forward and backward.
 // Errors are thrown (KALDI_ASSERT / KALDI_ERR); kcnn-capi.cc turns them into
 // error codes.
 #ifndef KCNN_CAPI_NNET_STACK_H_
@@ -229,6 +231,41 @@ class NnetStack {
   // columns, sizes) precedes every launch; the examples are staged first.
   void PropagateFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
                        const int32_t *frames, int num);
+  // PropagateFrames with the prefix of the training plan (TimeSharedTrainPlan)
+  // run once per time step of each RUN of the list (frame-index.h, frame_runs:
+  // a maximal stretch of consecutive rows of one utterance; any list is legal,
+  // and example n stays frames[n]).  A run of k frames is a segment of k + L +
+  // R rows of the level-0 map, laid out clamped from the corpus by
+  // kn_timemap_layout; the levels are time_schedule's under kUtteranceRoute, so
+  // every level is formed, and the gather writes Output(prefix - 1) as
+  // PropagateFrames would, to the error bar of the GEMMs.  Components prefix ..
+  // run as PropagateFrames runs them (Dropout, row offsets, fused pairs, the
+  // statistics hand-off).  PropagateFrames' checks, then the segments' (the
+  // rows of every map below 2^31, plan_train_rows), precede every launch.
+  // Leaves PropagateFrames' state, but Output(i) below prefix - 1 throws and
+  // TimeMap gives the maps.  Backprop / BackpropXent then run components prefix
+  // .. as always and the prefix ONCE over the maps (time_backward_schedule: the
+  // scatter, kn_timemap_epilogue_bwd, and per Convolution the weight, bias and
+  // data gradients as per-tap GEMMs on row-shifted views), every Convolution of
+  // the prefix stepping by ApplyGradient(gradient, num).  The prefix's
+  // RectifiedLinearComponents accumulate no NonlinearStats in such a step:
+  // their window columns are never formed.  BackpropComponent, BackpropSplit
+  // and InputDeriv of a prefix component throw, changing nothing.  With a
+  // training prefix of 0 (or the literal path on) the call is PropagateFrames.
+  void PropagateFramesShared(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
+                             const int32_t *frames, int num);
+  // The plan of PropagateFramesShared: TimeSharedPlan, declined when a level
+  // keeps a height (time-plan.h, time_train_plan) or when it covers the whole
+  // stack (the backward starts from the component above the prefix).
+  TimePlan TimeSharedTrainPlan() const;
+  // After PropagateFramesShared and a Backprop / BackpropXent, until the next
+  // forward call: the derivative map of `level` (rows and geometry as
+  // TimeMap's; level 0 and a pool's own level under a ReLU have none and
+  // throw), and the flat gradient ([KernelDim x Group | Group], as
+  // ComputeGradient lays it out) that the backward applied to prefix
+  // Convolution i.
+  TimeMapInfo TimeMapDeriv(int level) const;
+  const float *TimeGradient(int i, int *num) const;
   // ComputeProb on such a minibatch; leaves the state ComputeProb leaves.
   void ComputeProbFrames(const float *feats, MatrixDim dim, const CorpusIndex &corpus,
                          const int32_t *frames, int num, const int32_t *rows,
@@ -410,6 +447,15 @@ class NnetStack {
   void PropagateTimeShared(const float *in, MatrixDim in_dim, const int32_t *utt_start,
                            int num_utts, int total, bool pad_input, const TimePlan &plan,
                            const TimeRows &rows);
+  // the levels above level 0 (time_views_[0] is set) and the gather into
+  // Output(prefix - 1), of `total` rows
+  void FormTimeLevels(const TimePlan &plan, const TimeRows &rows, const int32_t *starts,
+                      int num_starts, int total);
+  // the backward over the maps of the last PropagateFramesShared, from
+  // InputDeriv(prefix), and the prefix Convolutions' steps
+  void BackpropTimeMaps();
+  // throws when component i is of the prefix the last forward ran as time maps
+  void RequireAbovePrefix(int i, const char *who) const;
 
   Activation &in(int i) { return acts_[i]; }
   Activation &out(int i) { return acts_[i + 1]; }
@@ -448,6 +494,17 @@ class NnetStack {
   bool time_shared_ = false;
   std::vector<CuMatrix<BaseFloat>> time_maps_;
   std::vector<TimeMapInfo> time_views_;
+  // the last forward was PropagateFramesShared's over time maps (time_shared_
+  // holds too): its plan and rows, the runs' starts on the device (in
+  // frames_), and what its backward leaves -- the derivative maps (views of
+  // time_derivs_, data NULL where none is formed) and the gradients applied
+  bool time_train_ = false, time_backward_done_ = false;
+  TimePlan train_plan_;
+  TimeRows train_rows_;
+  const int32_t *train_starts_ = nullptr;
+  int train_runs_ = 0;
+  std::vector<CuMatrix<BaseFloat>> time_derivs_, time_grads_;
+  std::vector<TimeMapInfo> time_dviews_;
   // the last forward was PropagateFrames' through a first Splice: component
   // 0's input is the corpus, not a window matrix, and it has no Backprop
   bool frames_fused_ = false;

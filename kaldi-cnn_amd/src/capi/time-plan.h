@@ -63,6 +63,8 @@
 #include <string>
 #include <vector>
 
+#include "frame-index.h"  // check_frames_matrix: the limits of a training pass
+
 namespace kcnn {
 
 constexpr int64_t kTimeRowLimit = (int64_t)1 << 31;  // rows of a matrix
@@ -412,6 +414,107 @@ inline void time_valid_rows(const TimePlan &plan, const TimeRows &rows, int l, i
   const TimeLevel &lev = plan.levels[(size_t)l];
   *first = rows.base[(size_t)u];
   *num = rows.frames[(size_t)u] + (int64_t)lev.dilation * (lev.positions - 1);
+}
+
+// ---- training on runs of consecutive corpus rows -------------------------------
+// NnetStack::PropagateFramesShared (kcnn_nnet_propagate_frames_shared) runs the
+// prefix of a TRAINING step as time maps.  A run (r0, k) of the frame list
+// (frame-index.h, frame_runs) in utterance rows [s, e) is one SEGMENT: its
+// level-0 rows are corpus rows clamp(r0 - L + j, s, e - 1), j < k + L + R, and
+// its k result rows start at the sum of the earlier runs' lengths.  These are
+// plan_time_rows' rows of num_runs unpadded "utterances" of k + L + R frames;
+// the forward is time_schedule under kUtteranceRoute, which forms every level,
+// and the backward time_backward_schedule below.
+
+// The plan of a training step: `plan` itself (make_time_plan's), declined when
+// any of its levels runs on the height-map kernels, which have no backward.
+inline TimePlan time_train_plan(TimePlan plan) {
+  for (int l = 1; l < plan.prefix(); l++)
+    if (time_level_2d(plan, l)) {
+      std::ostringstream why;
+      why << "level " << l << " keeps a height; training covers 1-D levels only";
+      plan.levels.clear();
+      plan.declined = why.str();
+      break;
+    }
+  return plan;
+}
+
+// The rows of a training pass over runs of run_lengths[j] = k_j frames: "" and
+// *rows, or what is wrong.  Beyond plan_time_rows' limits, every map, every
+// derivative map and the window-layout output stay below 2^31 rows and elements.
+inline std::string plan_train_rows(const TimePlan &plan, const int32_t *run_lengths,
+                                   int num_runs, TimeRows *rows) {
+  if (plan.levels.empty()) return "no plan";
+  if (run_lengths == nullptr || num_runs < 1) return "no runs";
+  const int64_t context = plan.levels[0].positions - 1;
+  std::vector<int32_t> lengths((size_t)num_runs);
+  for (int j = 0; j < num_runs; j++) {
+    if (run_lengths[j] < 1 || run_lengths[j] + context >= kTimeRowLimit) return "too many rows";
+    lengths[(size_t)j] = (int32_t)(run_lengths[j] + context);
+  }
+  TimeRows r;
+  std::string bad = plan_time_rows(plan, lengths.data(), num_runs, false, &r);
+  for (size_t l = 0; bad.empty() && l < plan.levels.size(); l++)
+    bad = check_frames_matrix("a time map", r.computed[l], plan.levels[l].width);
+  const TimeLevel &top = plan.levels.back();
+  if (bad.empty())
+    bad = check_frames_matrix("the window-layout output", r.result_rows,
+                              (int64_t)top.width * top.positions);
+  if (bad.empty()) *rows = r;
+  return bad;
+}
+
+// One launch of the backward pass over time maps.  Levels name forward maps
+// (`in`, `pooled`, `act`) and derivative maps (`dout` read, `din` written whole);
+// -1: none.
+struct TimeBackLaunch {
+  enum Op { kScatter, kEpilogueBwd, kConvBwd };
+  Op op;
+  int comp;                // the component (a conv: whose W is read and updated)
+  int dout_level;          // kScatter: -1, it reads d(Output(prefix - 1))
+  int rows;                // rows of dout; kScatter: result rows
+  int din_level, in_rows;  // -1: the convolution directly above level 0 has no data gradient
+  int in_level;            // the forward map below: a pool's or a convolution's input
+  int pooled_level, act_level;  // kEpilogueBwd: the pool's own output, the ReLU'd map
+  int taps, dilation;      // kw or pw, and the dilation of the map below
+  int pool_channel;
+  int wc, wd;              // kConvBwd: gradient row c wc + d wd
+  int positions, context;  // kScatter
+};
+
+// The launches of the backward pass in order, top level first: the scatter
+// (the gather's adjoint), then per forward launch, reversed, a pool and/or ReLU
+// backward or a convolution backward.  `plan` is a training plan.
+inline std::vector<TimeBackLaunch> time_backward_schedule(const TimePlan &plan,
+                                                          const TimeRows &rows) {
+  std::vector<TimeBackLaunch> out;
+  const std::vector<TimeLaunch> fwd = time_schedule(plan, rows, kUtteranceRoute);
+  for (size_t i = fwd.size(); i-- > 0;) {
+    const TimeLaunch &t = fwd[i];
+    TimeBackLaunch b = {TimeBackLaunch::kScatter, t.comp, -1, t.rows, t.in_level, t.in_rows,
+                        t.in_level, -1, -1, t.taps, t.dilation, 0, 0, 0, 0, 0};
+    if (t.op == TimeLaunch::kGather) {
+      b.in_level = -1;
+      b.taps = 0;
+      b.positions = t.positions;
+      b.context = t.context;
+    } else if (t.op == TimeLaunch::kEpilogue) {
+      b.op = TimeBackLaunch::kEpilogueBwd;
+      b.dout_level = t.act_level >= 0 ? t.act_level : t.out_level;
+      b.pooled_level = t.out_level;
+      b.act_level = t.act_level;
+      b.pool_channel = t.pool_channel;
+    } else {  // kConvTaps: a training plan has no other convolution
+      b.op = TimeBackLaunch::kConvBwd;
+      b.dout_level = t.out_level;
+      if (t.in_level == 0) b.din_level = -1;
+      b.wc = t.wc;
+      b.wd = t.wd;
+    }
+    out.push_back(b);
+  }
+  return out;
 }
 
 }  // namespace kcnn

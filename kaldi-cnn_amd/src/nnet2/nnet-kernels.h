@@ -351,6 +351,47 @@ int kn_timemap_gather2d(const float *map, MatrixDim map_dim, float *out, MatrixD
                         const int *utt_start, int num_utts, int ext, int height, int positions,
                         int dilation, kcnn_stream_t st);
 
+/* ---- nnet-timemap-bwd.hip: a training step over time maps ---- */
+
+/* Level 0 of a training pass over runs of consecutive corpus rows
+ * (capi/time-plan.h): map(base_j + i, .) = feats(clamp(r0_j - left + i, lo_j,
+ * hi_j), .) for run j < num_runs and every map row, base_j = run_start[j] + j
+ * ext.  run_start (DEVICE): the num_runs + 1 ascending starts of the runs'
+ * result rows; runs (DEVICE): {r0, first row, last row of its utterance} per
+ * run, as kn_splice_frames_prop's triples; ext = L + R >= left.  All
+ * map_dim.rows rows are written; a source row is clamped into `feats` at last,
+ * so a table that disagrees with the matrices still reads inside them. */
+int kn_timemap_layout(const float *feats, MatrixDim dim, float *map, MatrixDim map_dim,
+                      const int *run_start, const int *runs, int num_runs, int left, int ext,
+                      kcnn_stream_t st);
+
+/* The adjoint of kn_timemap_gather: dmap(s, c) = the sum over k ascending of
+ * dy(utt_start[u] + t, k + c positions), t = s - base_u - dilation k, over the
+ * k < positions with 0 <= t < F_u, for every s < rows and c < dmap_dim.cols; u
+ * is the segment of map row s (base_u = utt_start[u] + u ext, F_u its result
+ * rows).  Rows that no window reads get 0.  One writer an element, no atomics.
+ * Refused: dy_dim.cols != dmap_dim.cols positions, dmap_dim.rows < rows, a last
+ * window that passes row rows - 1. */
+int kn_timemap_scatter(const float *dy, MatrixDim dy_dim, float *dmap, MatrixDim dmap_dim,
+                       const int *utt_start, int num_utts, int ext, int positions, int dilation,
+                       int rows, kcnn_stream_t st);
+
+/* The backward of kn_timemap_epilogue in its three forms.  g(s, oc) = dout(s,
+ * oc), or with relu != NULL (the ReLU'd map the forward wrote) relu(s, oc) > 0
+ * ? dout(s, oc) : 0, RectifiedLinearComponent::Backprop on the output value.
+ * With pooled != NULL (the pool's own output; `in` its input): din(r, ch) = the
+ * sum over w ascending of g(r - delta w, ch / pool_channel) over the w <
+ * pool_width with 0 <= r - delta w < rows and in(r, ch) == pooled(r - delta w,
+ * ch / pool_channel), for every r < rows + delta (pool_width - 1): every tied
+ * maximum receives the gradient, a NaN routes nothing.  With pooled == NULL
+ * (pool_width = pool_channel = 1; `in` is not read) din = g.  din_dim.cols =
+ * do_dim.cols pool_channel. */
+int kn_timemap_epilogue_bwd(const float *in, MatrixDim in_dim, const float *pooled,
+                            MatrixDim p_dim, const float *relu, MatrixDim r_dim,
+                            const float *dout, MatrixDim do_dim, float *din, MatrixDim di_dim,
+                            int rows, int pool_width, int pool_channel, int delta,
+                            kcnn_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif
